@@ -14,7 +14,10 @@ data-path collective, and rank 0 gathers the corrected fragments over RCCL at th
 `python bench.py --gpus N` with N > 1 and no torchrun environment re-executes itself under
 `python -m torch.distributed.run --nproc-per-node N` (one rank per GPU, backend nccl = RCCL).
 
-Prints ONE JSON line on rank 0 (see the driver contract), including
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run sets up, warms up, times --steps steps, writes the
+outputs of its last step with --dump-outputs DIR and prints metric, value, unit, higher_is_better, dtype, ms_per_step and the
+workload.  Everything else it measures or checks runs with --full only:
+  value_end_to_end : a second timed loop of dacc_submit_piles (host plan + upload + kernels + download, --e2e-steps)
   roofline     : algorithmic bytes of the dominant kernel / its HIP-event duration vs the 8 TB/s HBM peak, the HBM
                  traffic and issue-slot counters of the same kernel from the committed PMC passes (profiles/)
   cpu_baseline : the CPU oracle (a port of the reference's algorithm, oracle/) timed on this host's cores on a
@@ -48,15 +51,24 @@ def parse():
     ap.add_argument("--k", type=int, default=14)
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the end-to-end loop, roofline / PMC figures, parity digests, "
+                         "live oracle samples, the accuracy report and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (fragment fields, per-fragment base checksums, a seeded "
+                         "sample of the bases) as DIR/<name>.npy in float64 / float32")
     ap.add_argument("--cpu-seconds", type=float, default=25.0, help="target wall time of each CPU baseline leg")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--ont", action="store_true", help="config 5 error mix (ins/del/sub = 1/3 each)")
     ap.add_argument("--e2e-steps", type=int, default=5,
-                    help="steps of the second timed loop (value_end_to_end: dacc_submit_piles per step = host plan + H2D + kernels + D2H); min(--steps, this), 0 = off")
+                    help="steps of the second timed loop (value_end_to_end: dacc_submit_piles per step = host plan + H2D + kernels + D2H); min(--steps, this), 0 = off; with --full")
     ap.add_argument("--live-parity", type=int, default=None,
                     help="piles of rank 0's shard run through oracle/ (and half as many through oracle/_ref) after the timed loop and compared with the "
-                         "GPU output (parity.live); default: 16 for every line the committed digests do not cover (N > 1, other shapes), 0 otherwise and with --no-cpu")
-    return ap.parse_args()
+                         "GPU output (parity.live); default: 16 for every line the committed digests do not cover (N > 1, other shapes), 0 otherwise and with --no-cpu; with --full")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def respawn(args):
@@ -195,6 +207,37 @@ def live_parity(args, p, d, piles, ovl, frags, bases, nlive, nthr, with_referenc
         return {"error": repr(ex)[:200], "identical": False}
 
 
+def dump_outputs(outdir, frags, bases, budget=64 << 20):
+    """What one step returned to its caller -- the fragments and the corrected bases of the whole job -- as float arrays, so that two
+    builds can be compared output for output: every field of every fragment (float64; a seeded sample of the fragments where they would
+    take more than half of `budget`), per fragment the checksum sum_i (i + 1) * base[i] over its bases (float64, exact), and the bases
+    themselves at seeded positions of the base buffer (float32 byte values)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    fields = ("aread", "first", "last", "len", "seq_off")
+    b = np.frombuffer(bases, dtype=np.uint8) if len(bases) else np.zeros(0, np.uint8)
+    rng = np.random.default_rng(20261016)
+    nf_max = (budget // 2) // (8 * (len(fields) + 1))
+    fi = np.arange(len(frags)) if len(frags) <= nf_max else np.sort(rng.choice(len(frags), nf_max, replace=False))
+    fs = frags[fi]
+    out = {"fragment_" + f: fs[f].astype(np.float64) for f in fields}
+    wmax = int(fs["len"].max()) if len(fs) else 0
+    w = np.arange(1, wmax + 1, dtype=np.float64)
+    ck = np.zeros(len(fs), np.float64)
+    for j, (o, n) in enumerate(zip(fs["seq_off"].tolist(), fs["len"].tolist())):
+        ck[j] = float(np.dot(b[o:o + n].astype(np.float64), w[:n]))
+    out["fragment_base_checksum"] = ck
+    if len(fi) < len(frags):
+        out["fragment_index"] = fi.astype(np.float64)
+    left = budget - sum(a.nbytes for a in out.values())
+    nb = min(len(b), left // 4, 1 << 22)
+    bi = np.arange(len(b)) if nb == len(b) else np.sort(rng.integers(0, len(b), nb))
+    out["bases_sample"] = b[bi].astype(np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return {name: int(a.size) for name, a in out.items()}
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -291,12 +334,16 @@ def main():
         dist.all_reduce(nb, op=dist.ReduceOp.SUM)
     dt = float(tmax[0].item()); tfirst_max = float(tmax[1].item())
     total_bases = float(nb.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's result as its caller receives it (rank 0: the gathered fragments of every rank), before anything else runs
+        dumped = dump_outputs(args.dump_outputs, gathered[0], gathered[1])
 
     # ---- second clock (VERDICT r05 task 3): BASELINE.md section 3 defines the wall time as "piles + DB in host RAM -> last fragment on
     # host", excluding only the one-off copy of the read DB.  A step here is dacc_submit_piles on the host arrays (planner, upload of
     # piles / overlaps / trace points, every kernel, download, fragment assembly) + the gather; buffers and the hand-over buffer exist
     # (this is not the context's first batch), nothing is resident but the read store.
-    e2e_steps = max(0, min(args.steps, args.e2e_steps))
+    e2e_steps = max(0, min(args.steps, args.e2e_steps)) if args.full else 0
     dt_e2e = 0.0
     if e2e_steps:
         def step_e2e():
@@ -326,6 +373,8 @@ def main():
     nlive = args.live_parity
     if nlive is None:
         nlive = 0 if (args.no_cpu or default_set) else (16 if world == 1 else max(2, (64 + world - 1) // world))
+    if not args.full:
+        nlive = 0
     live_rank = None
     if nlive > 0:
         live_rank = live_parity(args, p, d, piles, ovl, frags, bases, nlive, max(1, usable_cpus() // max(world, 1)), with_reference=(rank == 0))
@@ -342,6 +391,7 @@ def main():
         assert float(len(allba)) == total_bases, "gathered bases do not add up"
         ms_per_step = 1e3 * dt / args.steps
         value = total_bases * args.steps / dt / 1e6
+    if rank == 0 and args.full:
         # slots of the window kernels: shallow batches run k_classify + k_window_fast<0> (size classes) and k_window_fast<1> in
         # the first slot and k_window_fast<6> in the second; batches of deep piles k_window_fast<4> and k_window_fast<2>
         deep = int(getattr(t, "first_tier", 1)) == 4
@@ -394,17 +444,12 @@ def main():
         # a change to the generic engine leaves the code of the LDS tiers as it was).  Per-kernel numbers are quoted for unchanged kernels only.
         # (the size classes' entry is two kernels; its counters are those of k_window_fast<0>, the pre-pass is 1 ms of it)
         roof.update(pmc_lookup("k_window_fast<0>" if dom == "k_classify+k_window_fast<0>" else dom, args.reads, args.readlen, args.coverage, args.k))
+    if rank == 0:
         res = {
             "metric": "corrected Mbase/s (whole node), synthetic 20x PacBio piles",
             "value": round(value, 3), "unit": "Mbase/s", "n_gpus": world, "ranks": (dist.get_world_size() if world > 1 else 1), "backend": (backend if world > 1 else None),
             "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "value_end_to_end": (round(total_bases * e2e_steps / dt_e2e / 1e6, 3) if e2e_steps and dt_e2e > 0 else None),
-            "value_definition": "value = resident rate the driver's contract asks for (piles, overlaps, trace points and the plan already in HBM when the timed region starts; "
-                                "every kernel, the download and the host fragment assembly run in every step); value_end_to_end = BASELINE.md section 3's clock "
-                                "(piles + DB in host RAM -> last fragment on host, excluding only the one-off copy of the read DB): %d step(s) of dacc_submit_piles = host plan + upload of "
-                                "piles / overlaps / trace points + the same kernels + download, timed the same way" % e2e_steps,
-            "end_to_end": ({"steps": e2e_steps, "ms_per_step": round(1e3 * dt_e2e / e2e_steps, 3), "h2d_ms": round(tm_e2e.h2d_ms, 2), "window_ms": round(tm_e2e.window_ms, 2)} if e2e_steps else None),
             "value_incl_plan_h2d": round(total_bases / max(tfirst_max, 1e-9) / 1e6, 3),
             "preflight": preflight,
             "gather": (shard.last_transport if world > 1 else None),
@@ -419,9 +464,19 @@ def main():
                        "k_range": "3..16; k = 17 is rejected by dacc_create (DACC_EINVAL): no reference semantics -- the reference's k-mer instance word is kmer << 32 | pos << 16 | seq "
                                   "(src/DebruijnGraph.hpp:956-961, 1209-1235), a 34 bit k-mer does not fit it",
                        "sharding": "one data set, A-read ranges as -J g,G (daccord.cpp:1156-1183), no data-path collective; RCCL gather of corrected fragments per step"},
-            "roofline": roof,
             "setup_s": {"generate": round(tgen, 2), "first_pass_incl_plan_h2d": round(tfirst_max, 2), "h2d_ms": round(tm0.h2d_ms, 2)},
         }
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    if rank == 0 and args.full:
+        res.update({
+            "value_end_to_end": (round(total_bases * e2e_steps / dt_e2e / 1e6, 3) if e2e_steps and dt_e2e > 0 else None),
+            "value_definition": "value = resident rate the driver's contract asks for (piles, overlaps, trace points and the plan already in HBM when the timed region starts; "
+                                "every kernel, the download and the host fragment assembly run in every step); value_end_to_end = BASELINE.md section 3's clock "
+                                "(piles + DB in host RAM -> last fragment on host, excluding only the one-off copy of the read DB): %d step(s) of dacc_submit_piles = host plan + upload of "
+                                "piles / overlaps / trace points + the same kernels + download, timed the same way" % e2e_steps,
+            "end_to_end": ({"steps": e2e_steps, "ms_per_step": round(1e3 * dt_e2e / e2e_steps, 3), "h2d_ms": round(tm_e2e.h2d_ms, 2), "window_ms": round(tm_e2e.window_ms, 2)} if e2e_steps else None),
+            "roofline": roof})
         # ---- parity: full-batch digest, the oracle's committed digest of the first 1000 piles, live oracle sample ----
         def fasta_sha256(fr, ba):
             # digest of the FASTA text record by record (the text of 8 x 10 000 reads would be 0.7 GB in one string)
@@ -634,6 +689,7 @@ def main():
                                        "port": port, "like_for_like": cb.get("like_for_like")}
             else:
                 cb["note_kind"] = "oracle/_ref is not available here: the top-level entry is the oracle port"
+    if rank == 0:
         res["post_loop_s"] = round(time.perf_counter() - t_post, 2)
         print(json.dumps(res), flush=True)      # out before any teardown (stdout is block-buffered when it is a file)
     if world > 1:

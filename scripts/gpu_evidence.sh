@@ -5,17 +5,17 @@ R=$GRAFT_REPO_ROOT; TAG=${1:?usage: gpu_evidence.sh <tag>}; O=$R/gpurun_out/$TAG
 ( timeout 900 python -m pytest tests -x -q -m gpu -rs --durations=6 ) > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log
 tail -n 12 $O/pytest_gpu.log
 ( timeout 60 python -c "import __graft_entry__ as g; g.smoke()" ) > $O/smoke.log 2>&1; echo "rc=$?" >> $O/smoke.log; tail -n 2 $O/smoke.log
-( timeout 600 python bench.py ) > $O/bench_default.log 2>&1; echo "rc=$?" >> $O/bench_default.log
+( timeout 600 python bench.py --full ) > $O/bench_default.log 2>&1; echo "rc=$?" >> $O/bench_default.log
 bash scripts/gpu_pmc.sh $TAG 10000 3000 > $O/pmc.log 2>&1
 cp profiles/${TAG}_pmc_summary.json $O/ 2>/dev/null
 mkdir -p $O/pmc_raw; for d in gpurun_out/pmc_$TAG/pmc_*; do [ -f $d/pmc_counter_collection.csv ] && gzip -c $d/pmc_counter_collection.csv > $O/pmc_raw/$(basename $d).csv.gz; done
-( timeout 200 python bench.py --no-cpu ) > $O/bench_default_with_pmc.log 2>&1
+( timeout 200 python bench.py --full --no-cpu ) > $O/bench_default_with_pmc.log 2>&1
 cd /tmp && export TMPDIR=/tmp
-( timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o st -- python $R/bench.py --steps 1 --warmup 0 --no-cpu ) > $O/stats.log 2>&1; echo "rc=$?" >> $O/stats.log
+( timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o st -- python $R/bench.py --steps 1 --warmup 0 --full --no-cpu ) > $O/stats.log 2>&1; echo "rc=$?" >> $O/stats.log
 find $O/stats -name "*kernel_stats.csv" -exec cp {} $O/rocprof_kernel_stats.csv \; ; find $O/stats -name "*.csv" ! -name "*kernel_stats.csv" -delete
 cd $R
-( timeout 300 python bench.py --coverage 54 --reads 2000 --steps 2 --warmup 1 --no-cpu --live-parity 8 ) > $O/bench_54x_2000piles.log 2>&1
-( timeout 300 python bench.py --ont --reads 4000 --steps 2 --warmup 1 --no-cpu --live-parity 16 ) > $O/bench_ont_4000piles.log 2>&1
+( timeout 300 python bench.py --coverage 54 --reads 2000 --steps 2 --warmup 1 --full --no-cpu --live-parity 8 ) > $O/bench_54x_2000piles.log 2>&1
+( timeout 300 python bench.py --ont --reads 4000 --steps 2 --warmup 1 --full --no-cpu --live-parity 16 ) > $O/bench_ont_4000piles.log 2>&1
 for f in $O/bench_default.log $O/bench_default_with_pmc.log $O/bench_54x_2000piles.log $O/bench_ont_4000piles.log; do echo "== $f"; grep '^{' $f | tail -n 1 | python -c "
 import sys, json
 try:

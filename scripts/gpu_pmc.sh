@@ -8,7 +8,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 run_group () {  # name reads counters...
   N=$1; RD=$2; shift 2
-  ( timeout 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/pmc_$N -o pmc -- python $R/bench.py --reads $RD --steps 1 --warmup 0 --no-cpu ) > $O/pmc_$N.log 2>&1; echo "rc=$?" >> $O/pmc_$N.log
+  ( timeout 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/pmc_$N -o pmc -- python $R/bench.py --reads $RD --steps 1 --warmup 0 --full --no-cpu ) > $O/pmc_$N.log 2>&1; echo "rc=$?" >> $O/pmc_$N.log
   f=$(find $O/pmc_$N -name "*counter_collection.csv" | head -1); [ -n "$f" ] && mv $f $O/pmc_$N/pmc_counter_collection.csv
   find $O/pmc_$N -name "*.csv" ! -name "pmc_counter_collection.csv" -delete; find $O/pmc_$N -type d -empty -delete
 }

@@ -35,19 +35,19 @@ for step in "$@"; do
     pmc)
       IFS=: read -r name reads envs ctrs <<< "$rest"
       [ "$envs" = "-" ] && envs=""
-      ( cd /tmp && export TMPDIR=/tmp && env $(echo $envs | tr ',' ' ') timeout 400 rocprofv3 --pmc $(echo $ctrs | tr ',' ' ') --kernel-trace --output-format csv -d $O/pmc_$name -o pmc -- python $R/bench.py --reads $reads --steps 1 --warmup 0 --no-cpu ) > $O/pmc_$name.log 2>&1; echo "rc=$?" >> $O/pmc_$name.log
+      ( cd /tmp && export TMPDIR=/tmp && env $(echo $envs | tr ',' ' ') timeout 400 rocprofv3 --pmc $(echo $ctrs | tr ',' ' ') --kernel-trace --output-format csv -d $O/pmc_$name -o pmc -- python $R/bench.py --reads $reads --steps 1 --warmup 0 --full --no-cpu ) > $O/pmc_$name.log 2>&1; echo "rc=$?" >> $O/pmc_$name.log
       f=$(find $O/pmc_$name -name "*counter_collection.csv" | head -1)
       if [ -n "$f" ]; then python scripts/pmc_by_kernel.py $f > $O/pmc_$name.txt; cat $O/pmc_$name.txt | cut -c1-220; gzip -c $f > $O/pmc_$name.csv.gz; fi
       rm -rf $O/pmc_$name; tail -n 2 $O/pmc_$name.log | cut -c1-300 ;;
     bench)
       nb=$((nb+1)); a=$(echo "$rest" | tr ',' ' ')
-      ( timeout 900 python bench.py $a ) > $O/bench_$nb.log 2>&1; echo "rc=$? args=$a" >> $O/bench_$nb.log
+      ( timeout 900 python bench.py --full $a ) > $O/bench_$nb.log 2>&1; echo "rc=$? args=$a" >> $O/bench_$nb.log
       grep '^{' $O/bench_$nb.log | tail -n 1 | python scripts/bench_brief.py ;;
     ledger)
       IFS=: read -r reads extra <<< "$rest"
       ( timeout 1500 python scripts/ledger.py $O/ledger ${reads:-1500} $(echo $extra | tr ',' ' ') ) > $O/ledger.log 2>&1; echo "rc=$?" >> $O/ledger.log; tail -n 75 $O/ledger.log | cut -c1-230 ;;
     stats)
-      ( cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o st -- python $R/bench.py --steps 1 --warmup 0 --no-cpu ) > $O/stats.log 2>&1; echo "rc=$?" >> $O/stats.log
+      ( cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o st -- python $R/bench.py --steps 1 --warmup 0 --full --no-cpu ) > $O/stats.log 2>&1; echo "rc=$?" >> $O/stats.log
       find $O/stats -name "*kernel_stats.csv" -exec cp {} $O/rocprof_kernel_stats.csv \; ; rm -rf $O/stats; head -8 $O/rocprof_kernel_stats.csv | cut -c1-200 ;;
     *) echo "unknown step $step" ;;
   esac

@@ -26,7 +26,7 @@ def one_pass(out, tag, mask, reads, extra):
     d = os.path.join(out, "pass_" + tag)
     env = dict(os.environ, DACC_LIB=os.path.join(ROOT, "daccord_amd", "libvar_ledger.so"), DACC_LEDGER_MASK=str(mask), TMPDIR="/tmp")
     cmd = ["rocprofv3", "--pmc"] + COUNTERS + ["--kernel-trace", "--output-format", "csv", "-d", d, "-o", "pmc", "--",
-           sys.executable, os.path.join(ROOT, "bench.py"), "--reads", str(reads), "--steps", "1", "--warmup", "0", "--no-cpu", "--e2e-steps", "0"] + extra
+           sys.executable, os.path.join(ROOT, "bench.py"), "--reads", str(reads), "--steps", "1", "--warmup", "0", "--full", "--no-cpu", "--e2e-steps", "0"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd="/tmp", timeout=600)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if r.returncode != 0 or not line:

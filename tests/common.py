@@ -1,5 +1,39 @@
 import collections
+import hashlib
+import json
+import os
 import numpy as np
+
+REF_GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_outputs.json")
+_ref_gold = None
+
+
+def sha(b):
+    return hashlib.sha256(b if isinstance(b, bytes) else b.encode()).hexdigest()
+
+
+def arr_digest(a):
+    return [int(len(a)), sha(np.ascontiguousarray(a).tobytes())]
+
+
+def reference_result(key, fn, k16=False):
+    """What the reference build (oracle/_ref) returns for `key`: computed by fn() where the library is built, and held against the
+    recording in tests/golden/ref_outputs.json; the recording where it is not (DACC_RECORD_REF=1 rewrites the entry from a live run)."""
+    global _ref_gold
+    import pyref
+    if _ref_gold is None:
+        _ref_gold = json.load(open(REF_GOLD)) if os.path.exists(REF_GOLD) else {}
+    if pyref.available(k16=k16):
+        v = json.loads(json.dumps(fn()))
+        if os.environ.get("DACC_RECORD_REF") == "1":
+            _ref_gold[key] = v
+            with open(REF_GOLD, "w") as f:
+                json.dump(_ref_gold, f, indent=0, sort_keys=True)
+        else:
+            assert _ref_gold.get(key) == v, "tests/golden/ref_outputs.json is stale for %s (rewrite it with DACC_RECORD_REF=1)" % key
+        return v
+    assert key in _ref_gold, "no recording of the reference build for %s in tests/golden/ref_outputs.json" % key
+    return _ref_gold[key]
 
 
 def windows_equal(wo, wx):

@@ -14,9 +14,9 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(n, reads, scaling, extra=()):
+def _run(n, reads, scaling, extra=(), full=True):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    common = ["--reads", str(reads), "--readlen", "5000", "--steps", "1", "--warmup", "0", "--no-cpu", "--scaling", scaling] + list(extra)
+    common = ["--reads", str(reads), "--readlen", "5000", "--steps", "1", "--warmup", "0"] + (["--full", "--no-cpu"] if full else []) + ["--scaling", scaling] + list(extra)
     env = dict(os.environ, DACC_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     if n == 1:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + common
@@ -58,3 +58,35 @@ def test_eight_ranks_on_one_device_weak():
     assert eight["parity"]["gpu_fasta_sha256_all"] == one["parity"]["gpu_fasta_sha256_all"]
     assert eight["config"]["corrected_bases_total"] == one["config"]["corrected_bases_total"] and eight["config"]["piles_rank0"] == 40
     assert eight["post_loop_s"] < 60 and "accuracy" in eight
+
+
+def test_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """a plain run (no --full) times --steps steps and prints the headline without any of the checks; --dump-outputs writes what the
+    last timed step returned: the same arrays in a second run, and the very FASTA whose digest the --full run of the same data reports"""
+    import hashlib
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    from daccord_amd import engine
+    from daccord_amd._structs import DaccFragment
+    runs = [_run(1, 240, "weak", extra=["--steps", "3", "--dump-outputs", str(tmp_path / name)], full=False) for name in ("a", "b")]
+    for r in runs:
+        assert r["steps"] == 3 and r["ms_per_step"] > 0 and r["value"] > 0 and r["higher_is_better"] is True
+        assert (r["metric"], r["unit"], r["dtype"]) == ("corrected Mbase/s (whole node), synthetic 20x PacBio piles", "Mbase/s", "u64+f64")
+        for key in ("roofline", "parity", "accuracy", "cpu_baseline", "value_end_to_end", "end_to_end"):
+            assert key not in r, key
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "bases_sample.npy" in names and "fragment_seq_off.npy" in names
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 << 20
+    arr = {}
+    for f in names:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+        arr[f[:-4]] = x
+    # 240 reads x 5 kb: the sample is the whole base buffer, so the dump holds the complete result
+    assert len(arr["bases_sample"]) == runs[0]["config"]["corrected_bases_total"]
+    fr = np.zeros(len(arr["fragment_aread"]), dtype=np.dtype(DaccFragment))
+    for f in ("aread", "first", "last", "len", "seq_off"):
+        fr[f] = arr["fragment_" + f]
+    ba = arr["bases_sample"].astype(np.uint8).tobytes()
+    full = _run(1, 240, "weak")
+    assert hashlib.sha256(engine.fasta(fr, ba).encode()).hexdigest() == full["parity"]["gpu_fasta_sha256_all"]

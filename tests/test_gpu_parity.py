@@ -9,7 +9,7 @@ import pyoracle
 from daccord_amd import engine
 from daccord_amd._structs import default_params
 from daccord_amd.synth import SynthData
-from common import windows_equal, frags_equal, truth_error
+from common import windows_equal, frags_equal, truth_error, reference_result, arr_digest, sha
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -75,19 +75,27 @@ def test_hip_equals_the_reference_build(small_data, kw):
     """The HIP path against oracle/_ref directly: the reference's OWN HandleContext.hpp / DebruijnGraph.hpp / OffsetLikely.hpp ...
     compiled (in the build container, unmodified) against the libmaus2 stand-in; the built library travels with the snapshot, the
     sources do not.  k <= 12 runs the reference's own graph container, larger k our factory around its DebruijnGraph<k>."""
-    import pyref
     p = default_params(**kw)
-    if not pyref.available(k16=(p.khigh > 12)):
-        pytest.skip("oracle/_ref is not built (needs /root/reference at build time)")
     d, ovl, piles = small_data
+    r = reference_result("gpu_parity/%s" % sorted(kw.items()), lambda: _reference_build_result(p, d, ovl, piles), k16=(p.khigh > 12))
+    E = engine.Engine(p); E.set_error_profile(*d.error_profile()); E.load_db(d.bps, d.boff, d.rlen)
+    assert arr_digest(E.tables(200)) == r["tables"]
+    fx, bx = E(piles[:r["piles"]], ovl, d.trace)
+    assert len(bx) > 1000 and _frag_rows(fx) == r["frags"] and sha(bx) == r["bases"] and sha(engine.fasta(fx, bx)) == r["fasta"]
+    E.close()
+
+
+def _frag_rows(f):
+    return [[int(x["aread"]), int(x["first"]), int(x["last"]), int(x["len"]), int(x["seq_off"])] for x in f]
+
+
+def _reference_build_result(p, d, ovl, piles):
+    """oracle/_ref on the first piles of the small data set: its tables, fragments, bases and FASTA (recorded in tests/golden/ref_outputs.json)"""
+    import pyref
     n = 24 if p.khigh <= 14 else 6          # (a DebruijnGraph<16> of the reference holds 16 GiB of node cache per context)
     R = pyref.Reference(p); R.set_error_profile(*d.error_profile()); R.load_db(d.bps, d.boff, d.rlen)
-    E = engine.Engine(p); E.set_error_profile(*d.error_profile()); E.load_db(d.bps, d.boff, d.rlen)
-    assert (R.tables(200) == E.tables(200)).all()
     fr, br = R.run(piles[:n], ovl, d.trace, nthreads=(8 if p.khigh <= 12 else (4 if p.khigh <= 14 else 1)))
-    fx, bx = E(piles[:n], ovl, d.trace)
-    assert len(bx) > 1000 and frags_equal(fr, br, fx, bx) and engine.fasta(fx, bx) == pyoracle.fasta(fr, br)
-    E.close()
+    return {"piles": n, "tables": arr_digest(R.tables(200)), "frags": _frag_rows(fr), "bases": sha(br), "fasta": sha(pyoracle.fasta(fr, br))}
 
 
 @pytest.mark.parametrize("t0inst", ["0", "300", "488", "100000", "100000/nohand"])
