@@ -23,6 +23,9 @@
 
 namespace dacc {
 
+// run time capacities of a tier for a model table of nrows x nsup
+static inline FastCaps tierCaps(uint32_t const tier, uint32_t const nrows, uint32_t const nsup) { return withTier(tier,[&](auto ct) { return fastCapsOf<typename decltype(ct)::type>(nrows,nsup); }); }
+
 static inline uint32_t hostNextPow2(uint32_t v) { uint32_t p = 1; while ( p < v ) p <<= 1; return p; }
 
 // Windows::computeN (HandleContext.hpp:390-408)
@@ -57,15 +60,15 @@ struct BatchPlan
 	std::vector<int32_t> pile_status;         // per submitted pile: DACC_OK or why it was dropped
 	std::vector<std::string> pile_errors;     // first messages of dropped piles
 	ArenaCaps caps;
-	enum { NTIER = 3 };
-	FastCaps ftier[NTIER];    // LDS fast path capacity tiers: 3, 2, 1 wavefronts per CU
-	FastCaps ftier0;          // tier 0: small windows of shallow batches (size classes), runs in the first slot in front of tier 1
-	FastCaps ftier7;          // tier 7: the middle size class (7 wavefronts per CU), between tier 0 and tier 1
-	FastCaps ftierD;          // tier 10 (round 6): the dense-graph tier of shallow batches, between the second slot's tier 6 and tier 3
+	// LDS fast path: capacities of the stages of the tier chain (tier_pipeline.hpp), by name and by TierId
+	FastCaps ftier[TIER_NSLOTS];   // main tier of every slot
+	FastCaps ftier0, ftier7;  // front tiers of the first slot (size classes of shallow batches)
+	FastCaps ftierD;          // front tier of the last slot (dense graphs: tier 10, deep batches 11)
 	FastCaps ftierL;          // tier 5: windows with a string of 65..128 bases (second stream, before the generic engine)
+	FastCaps & stageCaps(uint32_t const id) { FastCaps * const F[TIER_NSTAGES] = { &ftier0,&ftier7,&ftier[0],&ftier[1],&ftierD,&ftier[2],&ftierL }; return *F[id]; }
 	uint64_t ndeepwin;        // windows with more strings / k-mer instances than the first tier of shallow batches holds
-	bool deep;                // most windows are deep: the first tier is FastTier<4> (many strings, small graph) instead of FastTier<1>
-	bool wide;                // window size 64 ... 127: the LDS tiers of the batch are FastTier<8> (second slot) and FastTier<9> (third slot) in front of the generic engine (round 6)
+	bool deep;                // most windows are deep: the chain of deep batches (many strings, small graph in the first slot)
+	bool wide;                // window size 64 ... 127: the chain of wide batches (round 6)
 
 	// Per pile results of the parallel pass of plan(): everything that does not depend on the piles in front of it
 	struct PileTmp
@@ -168,14 +171,15 @@ struct BatchPlan
 			if ( ny ) { diff[y0] += 1; diff[y0+ny] -= 1; }
 		}
 		int32_t cur = 0;
+		FastCaps const shallow = tierCaps(TIER_SHALLOW_FIRST,0,0);
 		for ( uint32_t y = 0; y < T.nwin; ++y )
 		{
 			cur += diff[y]; if ( static_cast<uint32_t>(cur) > T.maxdepth ) T.maxdepth = cur;
-			// strings of the window (A + active overlaps, capped by -d) against what FastTier<1> holds
+				// strings of the window (A + active overlaps, capped by -d) against what the first slot of shallow batches holds
 			uint64_t const nb = par.maxalign > 0 ? static_cast<uint64_t>(par.maxalign-1) : 0;
 			uint64_t const mao = 1 + std::min<uint64_t>(static_cast<uint64_t>(cur),nb);
 			uint64_t const perstr = par.w >= par.klow ? static_cast<uint64_t>(par.w-par.klow+1) : 1;
-			if ( mao > FastTier<1>::maxs || mao*perstr > FastTier<1>::precap ) ++T.ndeep;
+			if ( mao > shallow.maxs || mao*perstr > shallow.precap ) ++T.ndeep;
 		}
 	}
 
@@ -321,15 +325,9 @@ struct BatchPlan
 		// LDS fast path capacity tiers (compile time, fast_window.hpp); windows beyond them are re-run by the generic engine
 		// A batch whose windows are mostly too deep for tier 1 (coverage of 40x and more) starts in the deep tier instead
 		deep = 2*ndeepwin > nwindows;
-		ftier[0] = deep ? fastCapsOf< FastTier<4> >(tab_nrows,tab_nsup) : fastCapsOf< FastTier<1> >(tab_nrows,tab_nsup);
 		// (round 6) wide windows: tier 8 (second slot, no hand-over list in front of it = all windows), tier 9, then the generic engine
 		wide = par.w > 63 && par.w <= 127;
-		ftier[1] = wide ? fastCapsOf< FastTier<8> >(tab_nrows,tab_nsup) : (deep ? fastCapsOf< FastTier<2> >(tab_nrows,tab_nsup) : fastCapsOf< FastTier<6> >(tab_nrows,tab_nsup));
-		ftier0 = fastCapsOf< FastTier<0> >(tab_nrows,tab_nsup);
-		ftier7 = fastCapsOf< FastTier<7> >(tab_nrows,tab_nsup);
-		ftierL = fastCapsOf< FastTier<5> >(tab_nrows,tab_nsup);
-		ftierD = deep ? fastCapsOf< FastTier<11> >(tab_nrows,tab_nsup) : fastCapsOf< FastTier<10> >(tab_nrows,tab_nsup);      // (deep batches: tier 11)
-		ftier[2] = wide ? fastCapsOf< FastTier<9> >(tab_nrows,tab_nsup) : fastCapsOf< FastTier<3> >(tab_nrows,tab_nsup);
+		for ( uint32_t i = 0; i < TIER_NSTAGES; ++i ) stageCaps(i) = tierCaps(stageTier(TIER_CHAIN[i],deep,wide),tab_nrows,tab_nsup);
 		return DACC_OK;
 	}
 };

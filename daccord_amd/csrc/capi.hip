@@ -366,7 +366,7 @@ struct dacc_ctx
 	dacc_params par;
 	int device;
 	hipStream_t stream; hipStream_t stream2; hipEvent_t evFirstTier, evEarlyGeneric, evPrescan;   // stream2: generic engine for the windows no LDS tier can run, concurrent with tiers 2 and 3
-	hipEvent_t ev[6]; hipEvent_t evtier[3]; hipEvent_t evT0; bool tier0_ran;
+	hipEvent_t ev[6]; hipEvent_t evslot[TIER_NSLOTS];      // evslot[t]: slot t of the tier chain is done
 	std::string err;
 	bool haveprofile, havedb, havebatch;
 	double est_cor;
@@ -381,11 +381,15 @@ struct dacc_ctx
 	DevBuf<uint8_t> d_wrec; DevBuf<WindowOut> d_wout; DevBuf<uint8_t> d_arena;
 	DevBuf<uint8_t> d_has, d_oc, d_outsym, d_pilebad; DevBuf<uint16_t> d_ld0; DevBuf<uint32_t> d_ocs, d_nfrag, d_err;
 	DevBuf<VoteFragment> d_frags; DevBuf<uint64_t> d_fragbase; DevBuf<uint64_t> d_prof;
-	DevBuf<uint64_t> d_vst; DevBuf<uint32_t> d_tab32; DevBuf<uint8_t> d_gslab; DevBuf<uint32_t> d_retry[3], d_work, d_gearly, d_pregen, d_pregen2, d_pregenlist; DevBuf<uint8_t> d_arena2; DevBuf<uint64_t> d_trslab; DevBuf<uint32_t> d_small, d_big, d_mid; DevBuf<uint64_t> d_hand; DevBuf<uint32_t> d_handctr; uint32_t handcap, handwords; uint64_t handwant, nruns; bool nohand, oom; bool tier0_ok; uint32_t tier0_grid; uint64_t gstride0; bool tier7_ok, tier7_ran, tier7_adapt_off; int env_t7adapt; int env_trdyn; int env_widetier; bool widetier; int env_dense; bool tier10_ok, tier10_ran; uint32_t tier10_grid, tier10_out; uint64_t gstride10; DevBuf<uint32_t> d_dense; hipEvent_t evT10; uint32_t tier7_grid; uint64_t gstride7; hipEvent_t evT7;
+	DevBuf<uint64_t> d_vst; DevBuf<uint32_t> d_tab32; DevBuf<uint8_t> d_gslab; DevBuf<uint32_t> d_retry[TIER_NSLOTS], d_work, d_gearly, d_pregen, d_pregen2, d_pregenlist; DevBuf<uint8_t> d_arena2; DevBuf<uint64_t> d_trslab; DevBuf<uint32_t> d_small; DevBuf<uint64_t> d_hand; DevBuf<uint32_t> d_handctr; uint32_t handcap; uint64_t handwant, nruns; bool nohand, oom; bool tier7_adapt_off; int env_t7adapt; int env_trdyn;
+	// the LDS tiers (tier_pipeline.hpp): their switches, the resolved chain of the current batch (capacities: BP.stageCaps), by TierId and the launch state of its stages.
+	// A main tier hands on through d_retry[slot] and is done at evslot[slot]; `handon` and `done` are those of the front tiers.
+	TierSwitches sw; TierPipeline TP;
+	struct Stage { bool ran; uint32_t grid; DevBuf<uint32_t> handon; hipEvent_t done; } st[TIER_NSTAGES];
 	uint32_t nlong[2];      // windows on the two lists of the second stream in the current pass (pre-scan, first tier's generic-only windows)
-	uint32_t tier_grid[3], retry_grid, early_grid; uint64_t gstride[3]; int tier_ok[3]; int tierL_ok; int usefast; int sched; uint32_t tier_out[3];
+	uint32_t retry_grid, early_grid; int sched;
 	uint32_t tr_grid, tr_lds, tr_words, tr_lanes, trace_bytes, win_grid;
-	int env_nofast, env_sched, env_tiers, env_dbgretry; uint32_t env_lds_t1, env_lds_t0, env_t0inst, env_t7inst; int env_long128;     // debugging knobs, read once in dacc_create
+	int env_sched, env_dbgretry;     // debugging knobs, read once in dacc_create
 	std::vector<uint32_t> retry_flags;                      // DACC_DEBUG_RETRY: (window, flags) of what the last LDS tier handed on
 	std::vector<dacc_fragment> frags; std::string bases;
 	std::vector<int32_t> pile_status; std::vector<std::string> pile_errors; std::string pile_errors_joined;
@@ -439,34 +443,25 @@ int dacc_create(dacc_ctx ** out, dacc_params const * p)
 	if ( hipSetDevice(p->device) != hipSuccess ) return DACC_ENODEV;
 	dacc_ctx * c = new (std::nothrow) dacc_ctx;
 	if ( !c ) return DACC_ENOMEM;
-	c->par = *p; c->device = p->device; c->haveprofile = c->havedb = c->havebatch = false; c->est_cor = 0; c->nlong[0] = c->nlong[1] = 0; c->handcap = 0; c->handwords = 0; c->handwant = 0; c->nruns = 0; c->nohand = false; c->oom = false;
+	c->par = *p; c->device = p->device; c->haveprofile = c->havedb = c->havebatch = false; c->est_cor = 0; c->nlong[0] = c->nlong[1] = 0; c->handcap = 0; c->handwant = 0; c->nruns = 0; c->nohand = false; c->oom = false;
 	std::memset(&c->timing,0,sizeof(c->timing));
 	// launch geometry of the LDS tiers: set by every batch that uses them; a generic-only batch (DACC_NOFAST, w >= 64, a model table no
 	// tier holds) reads retry_grid in its scratch retry and must not find an indeterminate value there
-	c->retry_grid = c->early_grid = c->win_grid = 0; c->tier0_grid = 0; c->tier0_ok = false; c->tier0_ran = false; c->tier7_grid = 0; c->tier7_ok = false; c->tier7_ran = false; c->gstride7 = 0; c->tier7_adapt_off = false; c->tierL_ok = 0; c->usefast = 0; c->sched = 0;
-	for ( int i = 0; i < 3; ++i ) { c->tier_grid[i] = 0; c->tier_ok[i] = 0; c->tier_out[i] = 0; c->gstride[i] = 0; }
-	c->gstride0 = 0; c->tr_grid = c->tr_lds = c->tr_words = c->tr_lanes = c->trace_bytes = 0;
+	c->retry_grid = c->early_grid = c->win_grid = 0; c->tier7_adapt_off = false; c->sched = 0;
+	c->tr_grid = c->tr_lds = c->tr_words = c->tr_lanes = c->trace_bytes = 0;
 	{
-		char const * e = getenv("DACC_NOFAST"); c->env_nofast = (e && e[0] == '1');
+		c->sw = readTierSwitches();      // DACC_NOFAST, DACC_TIERS, DACC_WIDE_TIER, DACC_DENSE_TIER, DACC_LONG128, DACC_HAND, DACC_T0INST, DACC_T7INST, DACC_LDS_T1, DACC_LDS_T0
 		char const * sc = getenv("DACC_SCHED"); c->env_sched = sc ? atoi(sc) : 1;      // bit 0: LDS tiers pull work from a counter, bit 1: generic engine too
-		char const * tm = getenv("DACC_TIERS"); c->env_tiers = tm ? atoi(tm) : 31;      // bit t enables LDS tier t+1, bit 3 tier 0 (size classes), bit 4 tier 7 (the middle class; needs tier 0)
-		char const * l8 = getenv("DACC_LONG128"); c->env_long128 = !(l8 && l8[0] == '0');      // 0: windows with a string of 65 ... 128 bases run in tier 5 on the second stream (rounds 3-5)
-		{ char const * wt = getenv("DACC_WIDE_TIER"); c->env_widetier = !(wt && wt[0] == '0'); c->widetier = false; }
-		{ char const * dt = getenv("DACC_DENSE_TIER"); c->env_dense = !(dt && dt[0] == '0'); c->tier10_ok = false; c->tier10_ran = false; c->tier10_grid = 0; c->tier10_out = 0; c->gstride10 = 0; }      // 0: tier 6 hands on to tier 3 directly (before round 6's dense tier)
 		{ char const * td = getenv("DACC_TRACE_DYN"); c->env_trdyn = !(td && td[0] == '0'); }      // 0: k_trace walks its blocks with a fixed stride (rounds 1-5)
 		char const * ta = getenv("DACC_T7_ADAPT"); c->env_t7adapt = !(ta && ta[0] == '0');      // 0: tier 7 stays on whatever it hands on
-		char const * t7 = getenv("DACC_T7INST"); c->env_t7inst = t7 ? static_cast<uint32_t>(atoi(t7)) : static_cast<uint32_t>(T7INST_DEFAULT);      // size-class threshold of tier 7
-		char const * l1 = getenv("DACC_LDS_T1"); c->env_lds_t1 = l1 ? static_cast<uint32_t>(atoi(l1)) : 0u;      // measurement only: LDS bytes requested for the first tier (more than it needs = fewer wavefronts per CU)
-		char const * l0 = getenv("DACC_LDS_T0"); c->env_lds_t0 = l0 ? static_cast<uint32_t>(atoi(l0)) : 0u;      // the same for tier 0 (size classes)
-		char const * t0 = getenv("DACC_T0INST"); c->env_t0inst = t0 ? static_cast<uint32_t>(atoi(t0)) : static_cast<uint32_t>(T0INST_DEFAULT);      // size-class threshold (k-mer instances) of tier 0
 		char const * dr = getenv("DACC_DEBUG_RETRY"); c->env_dbgretry = (dr && dr[0] == '1');
 	}
 	if ( hipStreamCreate(&c->stream) != hipSuccess ) { delete c; return DACC_EHIP; }
 	{ int lo = 0, hi = 0; hipDeviceGetStreamPriorityRange(&lo,&hi); if ( hipStreamCreateWithPriority(&c->stream2,hipStreamNonBlocking,hi) != hipSuccess ) { delete c; return DACC_EHIP; } }
 	hipEventCreateWithFlags(&c->evFirstTier,hipEventDisableTiming); hipEventCreateWithFlags(&c->evEarlyGeneric,hipEventDisableTiming); hipEventCreateWithFlags(&c->evPrescan,hipEventDisableTiming);
 	for ( int i = 0; i < 6; ++i ) hipEventCreate(&c->ev[i]);
-	for ( int i = 0; i < 3; ++i ) hipEventCreate(&c->evtier[i]);
-	hipEventCreate(&c->evT0); c->tier0_ran = false; hipEventCreate(&c->evT7); hipEventCreate(&c->evT10);
+	for ( int i = 0; i < TIER_NSLOTS; ++i ) hipEventCreate(&c->evslot[i]);
+	for ( int i = 0; i < TIER_NSTAGES; ++i ) { hipEventCreate(&c->st[i].done); c->st[i].ran = false; c->st[i].grid = 0; }
 	*out = c;
 	return DACC_OK;
 }
@@ -480,10 +475,10 @@ void dacc_destroy(dacc_ctx * c)
 	c->d_bps.release(); c->d_boff.release(); c->d_rlen.release();
 	c->d_piles.release(); c->d_ovl.release(); c->d_ovl_pile.release(); c->d_trace.release(); c->d_blk_ovl.release(); c->d_blk_b0.release(); c->d_wt_b.release(); c->d_wt_e.release();
 	c->d_wrec.release(); c->d_wout.release(); c->d_arena.release();
-	c->h_outsym.release(); c->d_pilebad.release(); c->d_has.release(); c->d_oc.release(); c->d_outsym.release(); c->d_ld0.release(); c->d_ocs.release(); c->d_nfrag.release(); c->d_err.release(); c->d_frags.release(); c->d_fragbase.release(); c->d_prof.release(); c->d_vst.release(); c->d_tab32.release(); c->d_gslab.release(); for ( int i = 0; i < 3; ++i ) c->d_retry[i].release(); c->d_work.release(); c->d_gearly.release(); c->d_pregen.release(); c->d_pregen2.release(); c->d_pregenlist.release(); c->d_arena2.release(); c->d_trslab.release(); c->d_small.release(); c->d_big.release(); c->d_mid.release(); c->d_hand.release(); c->d_handctr.release();
+	c->h_outsym.release(); c->d_pilebad.release(); c->d_has.release(); c->d_oc.release(); c->d_outsym.release(); c->d_ld0.release(); c->d_ocs.release(); c->d_nfrag.release(); c->d_err.release(); c->d_frags.release(); c->d_fragbase.release(); c->d_prof.release(); c->d_vst.release(); c->d_tab32.release(); c->d_gslab.release(); for ( int i = 0; i < 3; ++i ) c->d_retry[i].release(); c->d_work.release(); c->d_gearly.release(); c->d_pregen.release(); c->d_pregen2.release(); c->d_pregenlist.release(); c->d_arena2.release(); c->d_trslab.release(); c->d_hand.release(); c->d_handctr.release();
 	for ( int i = 0; i < 6; ++i ) hipEventDestroy(c->ev[i]);
-	hipStreamDestroy(c->stream); hipStreamDestroy(c->stream2); hipEventDestroy(c->evFirstTier); hipEventDestroy(c->evEarlyGeneric); hipEventDestroy(c->evPrescan); for ( int i = 0; i < 3; ++i ) hipEventDestroy(c->evtier[i]);
-	hipEventDestroy(c->evT0); hipEventDestroy(c->evT7); hipEventDestroy(c->evT10); c->d_dense.release();
+	hipStreamDestroy(c->stream); hipStreamDestroy(c->stream2); hipEventDestroy(c->evFirstTier); hipEventDestroy(c->evEarlyGeneric); hipEventDestroy(c->evPrescan); for ( int i = 0; i < TIER_NSLOTS; ++i ) hipEventDestroy(c->evslot[i]);
+	c->d_small.release(); for ( int i = 0; i < TIER_NSTAGES; ++i ) { hipEventDestroy(c->st[i].done); c->st[i].handon.release(); }
 	delete c;
 }
 
@@ -551,7 +546,7 @@ static int dacc_load_db_body(dacc_ctx * c, uint8_t const * bps, uint64_t bps_byt
 
 static int runDevice(dacc_ctx * c)
 {
-	BatchPlan & BP = c->BP;
+	BatchPlan & BP = c->BP; TierPipeline & TP = c->TP;
 	hipStream_t const s = c->stream;
 	// DACC_DEBUG_SYNC=1: wait for every kernel of the generic-only path and say so on stderr (a device fault then names its kernel)
 	static bool const dbgsync = getenv("DACC_DEBUG_SYNC") && getenv("DACC_DEBUG_SYNC")[0] == '1';
@@ -563,8 +558,8 @@ static int runDevice(dacc_ctx * c)
 		uint64_t cap = c->handwant;
 		//  never more than half of what the device has free right now: the buffer is an optimisation and must not be what
 		// makes a later, larger batch of this context (or of another worker on the same device) fail its mandatory buffers
-		{ size_t fr = 0, tot = 0; if ( hipMemGetInfo(&fr,&tot) == hipSuccess ) { uint64_t const lim = (static_cast<uint64_t>(fr)/2) / (static_cast<uint64_t>(c->handwords)*8ull); if ( cap > lim ) cap = lim; } else (void)hipGetLastError(); }
-		while ( cap && c->d_hand.ensure(static_cast<size_t>(cap)*c->handwords) != hipSuccess ) { (void)hipGetLastError(); cap = cap > 65536 ? cap/2 : 0; }
+		{ size_t fr = 0, tot = 0; if ( hipMemGetInfo(&fr,&tot) == hipSuccess ) { uint64_t const lim = (static_cast<uint64_t>(fr)/2) / (static_cast<uint64_t>(c->TP.handwords)*8ull); if ( cap > lim ) cap = lim; } else (void)hipGetLastError(); }
+		while ( cap && c->d_hand.ensure(static_cast<size_t>(cap)*c->TP.handwords) != hipSuccess ) { (void)hipGetLastError(); cap = cap > 65536 ? cap/2 : 0; }
 		c->handcap = static_cast<uint32_t>(cap); c->handwant = cap;
 	}
 	++c->nruns;
@@ -582,7 +577,7 @@ static int runDevice(dacc_ctx * c)
 		TB.piles = c->d_piles.p; TB.ovl = c->d_ovl.p; TB.ovl_pile = c->d_ovl_pile.p; TB.trace = c->d_trace.p;
 		TB.blk_ovl = c->d_blk_ovl.p; TB.blk_b0 = c->d_blk_b0.p; TB.nblocks = BP.nblocks; TB.wt_b = c->d_wt_b.p; TB.wt_e = c->d_wt_e.p;
 		TB.maxcols = BP.maxcols; TB.trace_bytes = c->trace_bytes; TB.errflag = c->d_err.p + 2; TB.slab = c->d_trslab.p;
-		TB.work = (c->env_trdyn && BP.nblocks < 0xFFFFFF00ull) ? c->d_work.p + 60 : static_cast<uint32_t *>(0);
+		TB.work = (c->env_trdyn && BP.nblocks < 0xFFFFFF00ull) ? c->d_work.p + WORK_TRACE : static_cast<uint32_t *>(0);
 		if ( TB.work ) HIPCHK(hipMemsetAsync(TB.work,0,sizeof(uint32_t),s));
 		if ( c->tr_words == 2 ) hipLaunchKernelGGL(k_trace,dim3(c->tr_grid),dim3(64),c->tr_lds,s,TB);
 		else if ( c->tr_words == 4 ) hipLaunchKernelGGL(k_trace_wide<4>,dim3(c->tr_grid),dim3(64),c->tr_lds,s,TB,c->tr_lanes);
@@ -597,33 +592,31 @@ static int runDevice(dacc_ctx * c)
 		WB.piles = c->d_piles.p; WB.npiles = BP.piles.size(); WB.ovl = c->d_ovl.p; WB.wt_b = c->d_wt_b.p; WB.wt_e = c->d_wt_e.p;
 		WB.nwindows = BP.nwindows; WB.wrec = c->d_wrec.p; WB.wout = c->d_wout.p; WB.arena = c->d_arena.p; WB.prof = c->d_prof.p;
 		WB.pregen = 0;
+		for ( uint32_t i = 0; i < TIER_NSTAGES; ++i ) c->st[i].ran = false;
 		// no LDS tier usable (DACC_TIERS=0 or a model table no tier's overlay holds): everything runs in the generic engine on
 		// the main stream; the pre-scan / second stream would hand the same windows to two kernels
-		bool const anytier = c->tier_ok[0] || c->tier_ok[1] || c->tier_ok[2];
-		c->tier0_ran = false; c->tier7_ran = false; c->tier10_ran = false;
-		if ( c->usefast && anytier )
+		if ( TP.usefast && TP.anytier() )
 		{
 			// windows only the generic engine can run (a string longer than 64 bases): found by a scan of the window tables and
 			// started on the second stream now, concurrently with all LDS tiers
 			HIPCHK(hipMemsetAsync(c->d_pregen.p,0,((BP.nwindows+31)/32+1)*sizeof(uint32_t),s));
 			HIPCHK(hipMemsetAsync(c->d_pregen2.p,0,((BP.nwindows+31)/32+1)*sizeof(uint32_t),s));
 			HIPCHK(hipMemsetAsync(c->d_pregenlist.p,0,sizeof(uint32_t),s));
-			for ( int i = 0; i < 3; ++i ) HIPCHK(hipMemsetAsync(c->d_retry[i].p,0,sizeof(uint32_t),s));
+			for ( int i = 0; i < TIER_NSLOTS; ++i ) HIPCHK(hipMemsetAsync(c->d_retry[i].p,0,sizeof(uint32_t),s));
 			if ( BP.ovl.size() )
 			{
-				hipLaunchKernelGGL(k_prescan,dim3((BP.ovl.size()+3)/4),dim3(256),0,s,c->d_ovl.p,static_cast<uint64_t>(BP.ovl.size()),c->d_ovl_pile.p,c->d_piles.p,c->d_wt_b.p,c->d_wt_e.p,c->d_pregen.p,c->d_pregen2.p,c->widetier ? 128u : 64u);
+				hipLaunchKernelGGL(k_prescan,dim3((BP.ovl.size()+3)/4),dim3(256),0,s,c->d_ovl.p,static_cast<uint64_t>(BP.ovl.size()),c->d_ovl_pile.p,c->d_piles.p,c->d_wt_b.p,c->d_wt_e.p,c->d_pregen.p,c->d_pregen2.p,TP.widetier ? 128u : 64u);
 				// windows with a string of 65 ... 128 bases join the first slot's hand-overs when the second slot's tier holds such strings (tiers 6 / 3;
 				// a deep batch's tier 2 does not: it hands them on to tier 3 at its length check) and the first slot runs at all
-				bool const slot1 = c->tier_ok[0] && (c->tier_ok[1] || c->tier_ok[2]) && c->env_long128;
 				hipLaunchKernelGGL(k_prescan_lists,dim3(((BP.nwindows+31)/32+255)/256),dim3(256),0,s,c->d_pregen.p,c->d_pregen2.p,static_cast<uint64_t>(BP.nwindows),c->d_pregenlist.p,
-					slot1 ? c->d_retry[0].p : static_cast<uint32_t *>(0),c->d_wout.p);
+					TP.slot1_long ? c->d_retry[0].p : static_cast<uint32_t *>(0),c->d_wout.p);
 			}
 			HIPCHK(hipEventRecord(c->evPrescan,s));
 			FastBatch FL; FL.W = WB; FL.W.arena = c->d_arena2.p; FL.W.prof = 0; FL.W.pregen = 0; FL.F = BP.ftierL; FL.dpsq_vst = c->d_vst.p; FL.retry = 0; FL.gearly = 0; FL.gslab = 0; FL.gstride = 0; FL.tab32 = c->d_tab32.p; FL.hand = 0; FL.handctr = 0; FL.handcap = 0; FL.handwords = 0;
 #if defined(DACC_LEDGER)
 			FL.ledger = 0;
 #endif
-			if ( !c->tierL_ok ) FL.F.ldsbytes = 0;
+			if ( !TP.ok[ID_LONG] ) FL.F.ldsbytes = 0;
 			// a launch the device refuses (the LDS of a whole CU) falls back to the generic engine alone, for good
 			// (round 5) The length of a list is fetched before its launch and the grid follows it: an empty list -- the rule at the default
 			// window -- is not launched at all, a list of three windows asks for three CUs' worth of LDS instead of 256.  Rounds 1-4 queued
@@ -645,7 +638,7 @@ static int runDevice(dacc_ctx * c)
 				hipLaunchKernelGGL(k_window_long,dim3(grid),dim3(64),FL.F.ldsbytes,c->stream2,FL,c->d_err.p,lst);
 				if ( FL.F.ldsbytes && hipGetLastError() != hipSuccess )
 				{
-					c->tierL_ok = 0; FL.F.ldsbytes = 0;
+					TP.ok[ID_LONG] = false; FL.F.ldsbytes = 0;
 					hipLaunchKernelGGL(k_window_long,dim3(grid),dim3(64),0,c->stream2,FL,c->d_err.p,lst);
 				}
 				return DACC_OK;
@@ -655,20 +648,22 @@ static int runDevice(dacc_ctx * c)
 			HIPCHK(hipMemsetAsync(c->d_gearly.p,0,sizeof(uint32_t),s));
 			HIPCHK(hipMemsetAsync(c->d_handctr.p,0,sizeof(uint32_t),s));
 			bool early = false;
-			HIPCHK(hipMemsetAsync(c->d_work.p,0,64*sizeof(uint32_t),s));
-			// capacity tiers: every tier takes the windows the previous one handed over (list = 0: all windows)
+			HIPCHK(hipMemsetAsync(c->d_work.p,0,WORK_WORDS*sizeof(uint32_t),s));
+			// the chain (tier_pipeline.hpp): every slot takes the windows the previous one handed over (list = 0: all windows)
+			auto const work = [&](uint32_t const off) { return (c->sched&1) ? c->d_work.p+off : static_cast<uint32_t *>(0); };
 			uint32_t const * list = 0;
-			for ( int t = 0; t < 3; ++t )
+			for ( uint32_t slot = 0; slot < TIER_NSLOTS; ++slot )
 			{
-				if ( c->tier_ok[t] )
+				if ( TP.slotok(slot) )
 				{
-					FastBatch FB; FB.W = WB; FB.F = BP.ftier[t]; FB.dpsq_vst = c->d_vst.p; FB.retry = c->d_retry[t].p;
+					int const m = TIER_MAIN[slot];
+					FastBatch FB; FB.W = WB; FB.F = BP.stageCaps(m); FB.dpsq_vst = c->d_vst.p; FB.retry = c->d_retry[slot].p;
 					// the first slot's tiers skip every window with a string of more than 64 bases; the later ones only those the second stream has
 					// (without the 128-base route: all of them, as in rounds 3-5)
-					if ( t > 0 && c->tier_ok[0] && c->env_long128 ) FB.W.pregen = c->d_pregen2.p;
-					if ( c->widetier ) { FB.W.pregen = c->d_pregen2.p; FB.hand = 0; }      // (its hand-overs go to the generic engine, which sorts for itself)
-					FB.gslab = c->d_gslab.p; FB.gstride = c->gstride[t]; FB.tab32 = c->d_tab32.p;
-					FB.hand = c->handcap ? c->d_hand.p : static_cast<uint64_t *>(0); FB.handctr = c->d_handctr.p; FB.handcap = c->handcap; FB.handwords = c->handwords;
+					if ( (slot > 0 && TP.late_long) || TP.widetier ) FB.W.pregen = c->d_pregen2.p;
+					FB.gslab = c->d_gslab.p; FB.gstride = FB.F.gbytes; FB.tab32 = c->d_tab32.p;
+					// (a wide batch has handcap == 0, dacc_submit_piles: its hand-overs go to the generic engine, which sorts for itself)
+					FB.hand = c->handcap ? c->d_hand.p : static_cast<uint64_t *>(0); FB.handctr = c->d_handctr.p; FB.handcap = c->handcap; FB.handwords = TP.handwords;
 #if defined(DACC_LEDGER)
 					{ char const * lm = getenv("DACC_LEDGER_MASK"); FB.ledger = lm ? static_cast<uint32_t>(strtoul(lm,0,0)) : 0u; }      // (scripts/ledger.py)
 #endif
@@ -676,51 +671,36 @@ static int runDevice(dacc_ctx * c)
 					// window that reaches a later tier first (mao beyond the earlier tier) and turns out to be generic-only takes
 					// the ordinary hand-over chain to the generic kernel at the end
 					FB.gearly = early ? static_cast<uint32_t *>(0) : c->d_gearly.p;
-					uint32_t * const work = (c->sched&1) ? c->d_work.p+8*t : static_cast<uint32_t *>(0);
-					if ( t == 0 && BP.deep ) hipLaunchKernelGGL(k_window_fast<4>,dim3(c->tier_grid[t]),dim3(64),FB.F.ldsbytes,s,FB,list,work);
-					else if ( t == 0 && c->tier0_ok )
+					// the front tiers of the slot that run in this pass, each handing on to the next stage of the slot
+					// (tier 7 switches itself off for the rest of a context's batches when it hands on more than a fifth of what it runs: on the
+					// ONT mix at k = 10 / 12 a third / a quarter of its windows overflow it late, on their stretches and pools, and the class costs
+					// 2.6 / 1.4 % instead of gaining the 3 % it gains at k = 14 and 16 and on config 2, profiles/r06j; results do not depend on it)
+					int fr[TIER_NSTAGES]; uint32_t nfr = 0;
+					for ( int i = 0; i < m; ++i ) if ( TIER_CHAIN[i].slot == slot && TP.ok[i] && !((TIER_CHAIN[i].flags & STAGE_ADAPTIVE) && c->tier7_adapt_off) ) fr[nfr++] = i;
+					bool const classed = nfr && (TIER_CHAIN[fr[0]].flags & STAGE_PREPASS);
+					if ( classed ) HIPCHK(hipMemsetAsync(c->d_small.p,0,sizeof(uint32_t),s));
+					for ( uint32_t k = 0; k < nfr; ++k ) HIPCHK(hipMemsetAsync(c->st[fr[k]].handon.p,0,sizeof(uint32_t),s));
+					uint32_t const * in = list;
+					if ( classed )
 					{
 						// size classes: the small windows run in tier 0 (8 wavefronts per CU), the middle class and tier 0's hand-overs in tier 7
-						// (7 per CU), tier 7's hand-overs and all other windows in tier 1 (6 per CU)
-						HIPCHK(hipMemsetAsync(c->d_small.p,0,sizeof(uint32_t),s)); HIPCHK(hipMemsetAsync(c->d_big.p,0,sizeof(uint32_t),s));
-						// (tier 7 switches itself off for the rest of a context's batches when it hands on more than a fifth of what it runs: on the
-						// ONT mix at k = 10 / 12 a third / a quarter of its windows overflow it late, on their stretches and pools, and the class costs
-						// 2.6 / 1.4 % instead of gaining the 3 % it gains at k = 14 and 16 and on config 2, profiles/r06j; results do not depend on it)
-						bool const use7 = c->tier7_ok && !c->tier7_adapt_off;
-						if ( use7 ) HIPCHK(hipMemsetAsync(c->d_mid.p,0,sizeof(uint32_t),s));
-						uint32_t * const midlist = use7 ? c->d_mid.p : c->d_big.p;
-						hipLaunchKernelGGL(k_classify,dim3((BP.nwindows+255)/256),dim3(256),0,s,WB,c->d_small.p,midlist,c->d_big.p,c->env_t0inst,use7 ? c->env_t7inst : 0u);
+						// (7 per CU), tier 7's hand-overs and all other windows in tier 1 (6 per CU); without tier 7 the middle class counts as big
+						uint32_t * const mid = c->st[fr[0]].handon.p, * const big = c->st[fr[nfr-1]].handon.p;
+						hipLaunchKernelGGL(k_classify,dim3((BP.nwindows+255)/256),dim3(256),0,s,WB,c->d_small.p,mid,big,c->sw.t0inst,nfr > 1 ? c->sw.t7inst : 0u);
 						// (what the pre-pass itself put on the middle and the big list, before the tiers' hand-overs join them: for the counters of dacc_timing)
-						if ( use7 ) { HIPCHK(hipMemcpyAsync(c->d_work.p+56,c->d_mid.p,sizeof(uint32_t),hipMemcpyDeviceToDevice,s)); HIPCHK(hipMemcpyAsync(c->d_work.p+57,c->d_big.p,sizeof(uint32_t),hipMemcpyDeviceToDevice,s)); }
-						FastBatch F0 = FB; F0.F = BP.ftier0; F0.retry = midlist; F0.gstride = c->gstride0;
-						hipLaunchKernelGGL(k_window_fast<0>,dim3(c->tier0_grid),dim3(64),F0.F.ldsbytes,s,F0,static_cast<uint32_t const *>(c->d_small.p),(c->sched&1) ? c->d_work.p+40 : static_cast<uint32_t *>(0));
-						HIPCHK(hipEventRecord(c->evT0,s)); c->tier0_ran = true;
-						if ( use7 )
-						{
-							FastBatch F7 = FB; F7.F = BP.ftier7; F7.retry = c->d_big.p; F7.gstride = c->gstride7;
-							hipLaunchKernelGGL(k_window_fast<7>,dim3(c->tier7_grid),dim3(64),F7.F.ldsbytes,s,F7,static_cast<uint32_t const *>(c->d_mid.p),(c->sched&1) ? c->d_work.p+48 : static_cast<uint32_t *>(0));
-							HIPCHK(hipEventRecord(c->evT7,s)); c->tier7_ran = true;
-						}
-						hipLaunchKernelGGL(k_window_fast<1>,dim3(c->tier_grid[t]),dim3(64),FB.F.ldsbytes,s,FB,static_cast<uint32_t const *>(c->d_big.p),work);
+						if ( nfr > 1 ) { HIPCHK(hipMemcpyAsync(c->d_work.p+WORK_PRE_MID,mid,sizeof(uint32_t),hipMemcpyDeviceToDevice,s)); HIPCHK(hipMemcpyAsync(c->d_work.p+WORK_PRE_BIG,big,sizeof(uint32_t),hipMemcpyDeviceToDevice,s)); }
+						in = c->d_small.p;
 					}
-					else if ( t == 0 ) hipLaunchKernelGGL(k_window_fast<1>,dim3(c->tier_grid[t]),dim3(64),FB.F.ldsbytes,s,FB,list,work);
-					else if ( t == 1 && c->widetier ) hipLaunchKernelGGL(k_window_fast<8>,dim3(c->tier_grid[t]),dim3(64),FB.F.ldsbytes,s,FB,list,work);
-					else if ( t == 1 && BP.deep ) hipLaunchKernelGGL(k_window_fast<2>,dim3(c->tier_grid[t]),dim3(64),FB.F.ldsbytes,s,FB,list,work);
-					else if ( t == 1 ) hipLaunchKernelGGL(k_window_fast<6>,dim3(c->tier_grid[t]),dim3(64),FB.F.ldsbytes,s,FB,list,work);
-					else if ( c->widetier ) hipLaunchKernelGGL(k_window_fast<9>,dim3(c->tier_grid[t]),dim3(64),FB.F.ldsbytes,s,FB,list,work);
-					else if ( c->tier10_ok && list )
+					for ( uint32_t k = 0; k < nfr; ++k )
 					{
-						// (round 6) the dense-graph tier in front of tier 3: two wavefronts per CU with 16 bit path ids take what the second slot
-						// handed on; tier 3 (one per CU) gets what overflows them
-						HIPCHK(hipMemsetAsync(c->d_dense.p,0,sizeof(uint32_t),s));
-						FastBatch FD = FB; FD.F = BP.ftierD; FD.retry = c->d_dense.p; FD.gstride = c->gstride10;
-						if ( BP.deep ) hipLaunchKernelGGL(k_window_fast<11>,dim3(c->tier10_grid),dim3(64),FD.F.ldsbytes,s,FD,list,(c->sched&1) ? c->d_work.p+24 : static_cast<uint32_t *>(0));      // (deep batches: tier 11)
-						else hipLaunchKernelGGL(k_window_fast<10>,dim3(c->tier10_grid),dim3(64),FD.F.ldsbytes,s,FD,list,(c->sched&1) ? c->d_work.p+24 : static_cast<uint32_t *>(0));
-						HIPCHK(hipEventRecord(c->evT10,s)); c->tier10_ran = true;
-						hipLaunchKernelGGL(k_window_fast<3>,dim3(c->tier_grid[t]),dim3(64),FB.F.ldsbytes,s,FB,static_cast<uint32_t const *>(c->d_dense.p),work);
+						dacc_ctx::Stage & S = c->st[fr[k]];
+						FastBatch FF = FB; FF.F = BP.stageCaps(fr[k]); FF.retry = S.handon.p; FF.gstride = FF.F.gbytes;
+						hipLaunchKernelGGL(fastKernel(TP.tier[fr[k]]),dim3(S.grid),dim3(64),FF.F.ldsbytes,s,FF,in,work(TIER_CHAIN[fr[k]].work));
+						HIPCHK(hipEventRecord(S.done,s)); S.ran = true;
+						in = S.handon.p;
 					}
-					else hipLaunchKernelGGL(k_window_fast<3>,dim3(c->tier_grid[t]),dim3(64),FB.F.ldsbytes,s,FB,list,work);
-					list = c->d_retry[t].p;
+					hipLaunchKernelGGL(fastKernel(TP.tier[m]),dim3(c->st[m].grid),dim3(64),FB.F.ldsbytes,s,FB,in,work(TIER_CHAIN[m].work));
+					list = c->d_retry[slot].p;
 					if ( !early )
 					{
 						// the first tier has seen every window: what only the generic engine can run starts now, on its own
@@ -729,7 +709,7 @@ static int runDevice(dacc_ctx * c)
 						HIPCHK(hipEventRecord(c->evFirstTier,s));
 					}
 				}
-				hipEventRecord(c->evtier[t],s);
+				hipEventRecord(c->evslot[slot],s);
 			}
 			if ( c->env_dbgretry && list )
 			{
@@ -741,7 +721,7 @@ static int runDevice(dacc_ctx * c)
 				for ( uint32_t i = 0; i < n; ++i ) { WindowOut o; HIPCHK(hipMemcpy(&o,c->d_wout.p+idx[i],sizeof(WindowOut),hipMemcpyDeviceToHost)); c->retry_flags.push_back(idx[i]); c->retry_flags.push_back(o.flags); c->retry_flags.push_back(o.mao); c->retry_flags.push_back(static_cast<uint32_t>(o.filterfreq)); }
 			}
 			// what is left (rare shapes) goes through the generic engine
-			hipLaunchKernelGGL(k_window,dim3(c->retry_grid),dim3(64),0,s,WB,c->d_err.p,list,(c->sched&2) ? c->d_work.p+32 : static_cast<uint32_t *>(0));
+			hipLaunchKernelGGL(k_window,dim3(c->retry_grid),dim3(64),0,s,WB,c->d_err.p,list,(c->sched&2) ? c->d_work.p+WORK_GENERIC : static_cast<uint32_t *>(0));
 			// the second stream: the pre-scan's list (a string of more than 64 bases) as soon as the pre-scan is done, the first tier's
 			// generic-only windows behind the first tier; the main stream's queue is full by now
 			{ int const rc = launchLong(static_cast<uint32_t const *>(c->d_pregenlist.p),c->nlong[0],c->evPrescan); if ( rc ) return rc; }
@@ -751,7 +731,7 @@ static int runDevice(dacc_ctx * c)
 			HIPCHK(hipStreamWaitEvent(s,c->evEarlyGeneric,0));
 		}
 		else
-			{ HIPCHK(hipMemsetAsync(c->d_work.p,0,64*sizeof(uint32_t),s)); hipLaunchKernelGGL(k_window,dim3(c->win_grid),dim3(64),0,s,WB,c->d_err.p,static_cast<uint32_t const *>(0),(c->sched&2) ? c->d_work.p+32 : static_cast<uint32_t *>(0)); mark("k_window (all windows)"); }
+			{ HIPCHK(hipMemsetAsync(c->d_work.p,0,WORK_WORDS*sizeof(uint32_t),s)); hipLaunchKernelGGL(k_window,dim3(c->win_grid),dim3(64),0,s,WB,c->d_err.p,static_cast<uint32_t const *>(0),(c->sched&2) ? c->d_work.p+WORK_GENERIC : static_cast<uint32_t *>(0)); mark("k_window (all windows)"); }
 	}
 	HIPCHK(hipEventRecord(c->ev[2],s));
 	uint32_t herr[4] = {0,0,0,0};
@@ -785,26 +765,28 @@ static int runDevice(dacc_ctx * c)
 		return DACC_OK;
 	};
 	{ int const rc = voteAndFetch(); if ( rc ) return rc; }
-	for ( int i = 0; i < 3; ++i ) c->tier_out[i] = 0;
-	if ( c->usefast && BP.nwindows ) for ( int i = 0; i < 3; ++i ) if ( c->tier_ok[i] ) HIPCHK(hipMemcpy(&c->tier_out[i],c->d_retry[i].p,sizeof(uint32_t),hipMemcpyDeviceToHost));
-	c->tier10_out = 0;
-	if ( c->tier10_ran ) HIPCHK(hipMemcpy(&c->tier10_out,c->d_dense.p,sizeof(uint32_t),hipMemcpyDeviceToHost));
+	// dacc_timing's names for the front tiers: tier 0 and tier 7 are the first slot's (size classes), tier 10 the last slot's (dense graphs; tier 11 in deep batches)
+	auto const ranOf = [&](TierId const id) { return c->st[id].ran ? &c->st[id] : static_cast<dacc_ctx::Stage *>(0); };
+	dacc_ctx::Stage * const f0 = ranOf(ID_T0), * const f7 = ranOf(ID_T7), * const fD = ranOf(ID_DENSE);
+	for ( int i = 0; i < 3; ++i ) c->timing.tier_out[i] = 0;
+	if ( TP.usefast && BP.nwindows ) for ( int i = 0; i < 3; ++i ) if ( TP.slotok(i) ) HIPCHK(hipMemcpy(&c->timing.tier_out[i],c->d_retry[i].p,sizeof(uint32_t),hipMemcpyDeviceToHost));
+	c->timing.tier10_out = 0;
+	if ( fD ) HIPCHK(hipMemcpy(&c->timing.tier10_out,fD->handon.p,sizeof(uint32_t),hipMemcpyDeviceToHost));
 	c->timing.tier0_in = 0; c->timing.tier0_out = 0; c->timing.tier7_in = 0; c->timing.tier7_out = 0;
-	if ( c->usefast && BP.nwindows && (c->tier_ok[0] || c->tier_ok[1] || c->tier_ok[2]) )
+	if ( TP.usefast && BP.nwindows && TP.anytier() )
 	{
 		// length of the two lists of the second stream (pre-scan, first tier's generic-only windows), fetched before their launches
 		uint32_t const n1 = c->nlong[0], n2 = c->nlong[1];
 		c->timing.long_windows = n1 + n2; c->timing.long_first_tier = n2;
-		c->timing.tier7_in = 0; c->timing.tier7_out = 0;
-		if ( c->tier0_ran )
+		if ( f0 )
 		{
 			// size classes: the pre-pass sent nsmall windows to tier 0, nmid0 to the middle list and nwindows - nsmall - nmid0 - n1 to the big
 			// list; tier 0's hand-overs have joined the middle list since (the big list without tier 7), tier 7's the big list
 			uint32_t nsmall = 0, nbig = 0, nmid = 0;
-			HIPCHK(hipMemcpy(&nsmall,c->d_small.p,sizeof(uint32_t),hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&nbig,c->d_big.p,sizeof(uint32_t),hipMemcpyDeviceToHost));
-			if ( c->tier7_ran ) HIPCHK(hipMemcpy(&nmid,c->d_mid.p,sizeof(uint32_t),hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(&nsmall,c->d_small.p,sizeof(uint32_t),hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&nbig,(f7 ? f7 : f0)->handon.p,sizeof(uint32_t),hipMemcpyDeviceToHost));
+			if ( f7 ) HIPCHK(hipMemcpy(&nmid,f0->handon.p,sizeof(uint32_t),hipMemcpyDeviceToHost));
 			c->timing.tier0_in = nsmall;
-			if ( !c->tier7_ran )
+			if ( !f7 )
 			{
 				uint64_t const big0 = BP.nwindows - std::min<uint64_t>(BP.nwindows,static_cast<uint64_t>(nsmall) + n1);
 				c->timing.tier0_out = nbig > big0 ? static_cast<uint32_t>(nbig - big0) : 0u;
@@ -813,7 +795,7 @@ static int runDevice(dacc_ctx * c)
 			{
 				// nmid = what the pre-pass put on the middle list + tier 0's hand-overs, nbig = the pre-pass's big windows + tier 7's hand-overs
 				uint32_t pre[2] = {0,0};
-				HIPCHK(hipMemcpy(pre,c->d_work.p+56,2*sizeof(uint32_t),hipMemcpyDeviceToHost));
+				HIPCHK(hipMemcpy(pre,c->d_work.p+WORK_PRE_MID,2*sizeof(uint32_t),hipMemcpyDeviceToHost));
 				uint32_t const t7out = nbig > pre[1] ? nbig - pre[1] : 0u;
 				c->timing.tier0_out = nmid > pre[0] ? nmid - pre[0] : 0u;
 				c->timing.tier7_in = nmid; c->timing.tier7_out = t7out;
@@ -830,7 +812,7 @@ static int runDevice(dacc_ctx * c)
 		uint32_t const g = boundByArena(c->retry_grid < 64 ? c->retry_grid : 64,BP.caps.bytes,4);
 		c->retry_grid = g; c->win_grid = g; if ( c->early_grid > g ) c->early_grid = g;     // later launches of this batch use the grown arenas
 		HIPCHK(c->d_arena.ensure(static_cast<size_t>(g)*BP.caps.bytes));
-		if ( c->usefast ) HIPCHK(c->d_arena2.ensure(static_cast<size_t>(c->early_grid)*BP.caps.bytes));
+		if ( TP.usefast ) HIPCHK(c->d_arena2.ensure(static_cast<size_t>(c->early_grid)*BP.caps.bytes));
 		HIPCHK(c->d_gearly.ensure(BP.nwindows+2)); HIPCHK(c->d_pregenlist.ensure(BP.nwindows+2)); HIPCHK(c->d_pregen.ensure((BP.nwindows+31)/32+2)); HIPCHK(c->d_pregen2.ensure((BP.nwindows+31)/32+2));
 		HIPCHK(hipMemsetAsync(c->d_err.p,0,4*sizeof(uint32_t),s));
 		HIPCHK(hipMemsetAsync(c->d_gearly.p,0,sizeof(uint32_t),s));
@@ -877,18 +859,16 @@ static int runDevice(dacc_ctx * c)
 	float ms = 0;
 	hipEventElapsedTime(&ms,c->ev[0],c->ev[1]); c->timing.trace_ms = ms;
 	hipEventElapsedTime(&ms,c->ev[1],c->ev[2]); c->timing.window_ms = ms;
-	for ( int i = 0; i < 3; ++i ) { c->timing.tier_ms[i] = 0; c->timing.tier_out[i] = c->tier_out[i]; }
-	if ( c->usefast && BP.nwindows ) for ( int i = 0; i < 3; ++i ) { hipEventElapsedTime(&ms,i ? c->evtier[i-1] : c->ev[1],c->evtier[i]); c->timing.tier_ms[i] = ms; }
-	c->timing.tier0_ms = 0;
-	if ( c->tier0_ran ) { hipEventElapsedTime(&ms,c->ev[1],c->evT0); c->timing.tier0_ms = ms; }
-	c->timing.tier7_ms = 0; c->timing.pad_ = 0;
-	if ( c->tier7_ran ) { hipEventElapsedTime(&ms,c->evT0,c->evT7); c->timing.tier7_ms = ms; }
-	c->timing.tier10_ms = 0; c->timing.tier10_out = c->tier10_out; c->timing.tier10_ran = c->tier10_ran ? 1u : 0u;
-	if ( c->tier10_ran ) { hipEventElapsedTime(&ms,c->evtier[1],c->evT10); c->timing.tier10_ms = ms; }
+	for ( int i = 0; i < 3; ++i ) c->timing.tier_ms[i] = 0;
+	if ( TP.usefast && BP.nwindows ) for ( int i = 0; i < 3; ++i ) { hipEventElapsedTime(&ms,i ? c->evslot[i-1] : c->ev[1],c->evslot[i]); c->timing.tier_ms[i] = ms; }
+	c->timing.tier0_ms = 0; c->timing.tier7_ms = 0; c->timing.pad_ = 0; c->timing.tier10_ms = 0; c->timing.tier10_ran = fD ? 1u : 0u;
+	if ( f0 ) { hipEventElapsedTime(&ms,c->ev[1],f0->done); c->timing.tier0_ms = ms; }
+	if ( f7 ) { hipEventElapsedTime(&ms,f0->done,f7->done); c->timing.tier7_ms = ms; }
+	if ( fD ) { hipEventElapsedTime(&ms,c->evslot[1],fD->done); c->timing.tier10_ms = ms; }
 	hipEventElapsedTime(&ms,c->ev[2],c->ev[3]); c->timing.vote_ms = ms;
 	hipEventElapsedTime(&ms,c->ev[3],c->ev[4]); c->timing.d2h_ms = ms;
 	hipEventElapsedTime(&ms,c->ev[0],c->ev[3]); c->timing.total_ms = ms;
-	c->timing.first_tier = (c->usefast && BP.deep) ? 4u : 1u;
+	c->timing.first_tier = (TP.usefast && BP.deep) ? 4u : 1u;
 	c->timing.nwindows = BP.nwindows; c->timing.nblocks = BP.nblocks; c->timing.algo_bytes = BP.algo_bytes + nbases;
 	return DACC_OK;
 }
@@ -964,73 +944,26 @@ static int dacc_submit_piles_body(dacc_ctx * c, dacc_pile const * piles, uint64_
 	uint64_t const maxwg = 256*8;
 	if ( wg > maxwg ) wg = maxwg;
 	if ( wg < 8 ) wg = 8;
+	c->sched = c->env_sched;
+	bool fits32 = true;
+	for ( size_t i = 0; i < c->H.dpsq_vst.size(); ++i ) if ( c->H.dpsq_vst[i] >> 32 ) fits32 = false; // table must fit 32 bits
+	// which LDS tiers this batch runs (tier_pipeline.hpp); none: the generic engine alone
+	c->TP = resolveTiers(c->sw,!c->sw.nofast && fits32,BP.deep,BP.wide,c->H.nrows,c->H.nsup,c->par.w,[&](uint32_t const id) -> FastCaps & { return BP.stageCaps(id); });
+	TierPipeline const & TP = c->TP;
+	if ( TP.usefast )
 	{
-		c->usefast = !c->env_nofast;
-		c->sched = c->env_sched;
-		for ( size_t i = 0; i < c->H.dpsq_vst.size(); ++i ) if ( c->H.dpsq_vst[i] >> 32 ) c->usefast = 0; // table must fit 32 bits
-		// (round 6) wide windows, w = 64 ... 127 (model table of up to 128 rows): tier 8 in the second slot and tier 9 in the third in front of the generic engine
-		// (DACC_WIDE_TIER=0: the generic engine only, as in rounds 4-5; w = 128 always)
-		c->widetier = BP.wide && c->env_widetier && c->H.nrows <= 128 && c->H.nsup <= FSUPCAPW;
-		if ( !c->widetier && (c->H.nrows > 64 || c->H.nsup > FSUPCAP || c->par.w > 63) ) c->usefast = 0;
-	}
-	if ( c->usefast )
-	{
-		// LDS tiers: floor(160 KiB / ldsbytes) wavefronts per CU; a tier whose table overlay cannot hold the model table is skipped
-		if ( c->env_lds_t1 > BP.ftier[0].ldsbytes && c->env_lds_t1 <= 160*1024 ) BP.ftier[0].ldsbytes = c->env_lds_t1;
-		for ( int t = 0; t < 3; ++t )
+		for ( int t = 0; t < TIER_NSLOTS; ++t ) HIPCHK(c->d_retry[t].ensure(BP.nwindows+2));
+		// the stages of the chain: launch geometry, hand-on lists of the front tiers (and the pre-pass's list of small windows), global slab
+		// of the gw tiers (weights, spill): one per workgroup, the tiers run one after the other and share the buffer
+		for ( uint32_t i = 0; i < TIER_NSTAGES; ++i )
 		{
-			FastCaps const & F = BP.ftier[t];
-			c->tier_ok[t] = (static_cast<uint64_t>(c->H.nrows+1)*(c->H.nsup+1) <= F.tabcap) && F.ldsbytes <= 160*1024;
-			if ( !((c->env_tiers>>t)&1) ) c->tier_ok[t] = 0;
-			if ( c->widetier && t == 0 ) c->tier_ok[t] = 0;
-			uint64_t percu = (160*1024) / (F.ldsbytes ? F.ldsbytes : 1);
-			if ( percu > 8 ) percu = 8;
-			if ( percu < 1 ) percu = 1;
-			uint64_t fg = ((BP.nwindows+7)/8)*8;
-			if ( fg > 256*percu ) fg = 256*percu;
-			if ( fg < 8 ) fg = 8;
-			c->tier_grid[t] = fg;
-			HIPCHK(c->d_retry[t].ensure(BP.nwindows+2));
-			// gw tiers: one global slab per workgroup (weights, spill); the tiers run one after the other and share the buffer
-			c->gstride[t] = F.gbytes;
-			if ( F.gbytes ) HIPCHK(c->d_gslab.ensure(static_cast<size_t>(fg)*F.gbytes + 256));
-		}
-		{
-			// tier 0 (size classes) in front of tier 1 of a shallow batch: DACC_TIERS bit 3 switches it off
-			if ( c->env_lds_t0 > BP.ftier0.ldsbytes && c->env_lds_t0 <= 160*1024 ) BP.ftier0.ldsbytes = c->env_lds_t0;
-			FastCaps const & F0 = BP.ftier0;
-			c->tier0_ok = !BP.deep && c->tier_ok[0] && ((c->env_tiers>>3)&1) && F0.ldsbytes <= 160*1024;
-			uint64_t percu0 = (160*1024) / (F0.ldsbytes ? F0.ldsbytes : 1); if ( percu0 > 8 ) percu0 = 8; if ( percu0 < 1 ) percu0 = 1;
-			uint64_t fg0 = ((BP.nwindows+7)/8)*8; if ( fg0 > 256*percu0 ) fg0 = 256*percu0; if ( fg0 < 8 ) fg0 = 8;
-			c->tier0_grid = static_cast<uint32_t>(fg0); c->gstride0 = F0.gbytes;
-			if ( c->tier0_ok )
-			{
-				HIPCHK(c->d_small.ensure(BP.nwindows+2)); HIPCHK(c->d_big.ensure(BP.nwindows+2));
-				HIPCHK(c->d_gslab.ensure(static_cast<size_t>(fg0)*F0.gbytes + 256));
-			}
-			// tier 7 (the middle size class, 7 wavefronts per CU) between them: DACC_TIERS bit 4 switches it off
-			FastCaps const & F7 = BP.ftier7;
-			c->tier7_ok = c->tier0_ok && ((c->env_tiers>>4)&1) && F7.ldsbytes <= 160*1024 && c->env_t7inst > c->env_t0inst;
-			uint64_t percu7 = (160*1024) / (F7.ldsbytes ? F7.ldsbytes : 1); if ( percu7 > 8 ) percu7 = 8; if ( percu7 < 1 ) percu7 = 1;
-			uint64_t fg7 = ((BP.nwindows+7)/8)*8; if ( fg7 > 256*percu7 ) fg7 = 256*percu7; if ( fg7 < 8 ) fg7 = 8;
-			c->tier7_grid = static_cast<uint32_t>(fg7); c->gstride7 = F7.gbytes;
-			if ( c->tier7_ok )
-			{
-				HIPCHK(c->d_mid.ensure(BP.nwindows+2));
-				HIPCHK(c->d_gslab.ensure(static_cast<size_t>(fg7)*F7.gbytes + 256));
-			}
-			// tier 10 (the dense-graph tier, two wavefronts per CU) between the second slot's tier 6 and tier 3 of a shallow batch: DACC_DENSE_TIER=0 switches it off
-			FastCaps const & FD = BP.ftierD;
-			c->tier10_ok = !c->widetier && c->env_dense && c->tier_ok[1] && c->tier_ok[2] && FD.ldsbytes <= 160*1024 && (static_cast<uint64_t>(c->H.nrows+1)*(c->H.nsup+1) <= FD.tabcap);
-			uint64_t percuD = (160*1024) / (FD.ldsbytes ? FD.ldsbytes : 1); if ( percuD > 8 ) percuD = 8; if ( percuD < 1 ) percuD = 1;
-			uint64_t fgD = ((BP.nwindows+7)/8)*8; if ( fgD > 256*percuD ) fgD = 256*percuD; if ( fgD < 8 ) fgD = 8;
-			c->tier10_grid = static_cast<uint32_t>(fgD); c->gstride10 = FD.gbytes;
-			if ( c->tier10_ok )
-			{
-				HIPCHK(c->d_dense.ensure(BP.nwindows+2));
-				HIPCHK(c->d_gslab.ensure(static_cast<size_t>(fgD)*FD.gbytes + 256));
-				if ( FD.ldsbytes > 64*1024 ) HIPCHK(hipFuncSetAttribute(BP.deep ? reinterpret_cast<const void *>(k_window_fast<11>) : reinterpret_cast<const void *>(k_window_fast<10>),hipFuncAttributeMaxDynamicSharedMemorySize,FD.ldsbytes));
-			}
+			FastCaps const & F = BP.stageCaps(i);
+			c->st[i].grid = tierGrid(F.ldsbytes,BP.nwindows);
+			if ( !TP.ok[i] || TIER_CHAIN[i].role == ROLE_LONG ) continue;
+			if ( TIER_CHAIN[i].role == ROLE_FRONT ) HIPCHK(c->st[i].handon.ensure(BP.nwindows+2));
+			if ( TIER_CHAIN[i].flags & STAGE_PREPASS ) HIPCHK(c->d_small.ensure(BP.nwindows+2));
+			if ( F.gbytes ) HIPCHK(c->d_gslab.ensure(static_cast<size_t>(c->st[i].grid)*F.gbytes + 256));
+			if ( F.ldsbytes > 64*1024 ) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(fastKernel(TP.tier[i])),hipFuncAttributeMaxDynamicSharedMemorySize,F.ldsbytes));
 		}
 		{
 			// hand-over slots (sorted instances of a window that overflowed a tier's node table, picked up by the next tier): header +
@@ -1039,24 +972,17 @@ static int dacc_submit_piles_body(dacc_ctx * c, dacc_pile const * piles, uint64_
 			// The buffer is an optimisation for contexts that live: the driver clears device memory it hands out (16 GB = half a
 			// second on some boxes), which a single pass does not earn back, so the FIRST pass of a context runs without it and the
 			// buffer is allocated when the context is used again (runDevice).
-			char const * he = getenv("DACC_HAND");
-			c->handwords = (BP.deep ? 2048u + 128u : 1024u + 64u) + 4u;
-			uint64_t cap = BP.nwindows/3 + 4096; uint64_t const maxcap = (16ull<<30) / (static_cast<uint64_t>(c->handwords)*8ull);
+			uint64_t cap = BP.nwindows/3 + 4096; uint64_t const maxcap = (16ull<<30) / (static_cast<uint64_t>(TP.handwords)*8ull);
 			if ( cap > maxcap ) cap = maxcap;
-			if ( he && he[0] == '0' ) cap = 0;
 			if ( c->par.klow != c->par.khigh ) cap = 0;
 			if ( c->nohand ) cap = 0;      // a retry after an allocation failure: no optional buffer (dacc_drop_hand)
-			if ( c->widetier ) cap = 0;    // a wide batch has one LDS tier: nothing to hand the sorted instances to
+			if ( !TP.handover ) cap = 0;   // DACC_HAND=0, or a wide batch: nothing to hand the sorted instances to
 			c->handwant = cap;
 			HIPCHK(c->d_handctr.ensure(4));
-			if ( c->d_hand.cap < static_cast<size_t>(cap)*c->handwords ) c->handcap = static_cast<uint32_t>(c->d_hand.cap / c->handwords);     // what an earlier batch left
+			if ( c->d_hand.cap < static_cast<size_t>(cap)*TP.handwords ) c->handcap = static_cast<uint32_t>(c->d_hand.cap / TP.handwords);     // what an earlier batch left
 			else c->handcap = static_cast<uint32_t>(cap);
 		}
-		if ( BP.ftier[0].ldsbytes > 64*1024 ) HIPCHK(hipFuncSetAttribute(BP.deep ? reinterpret_cast<const void *>(k_window_fast<4>) : reinterpret_cast<const void *>(k_window_fast<1>),hipFuncAttributeMaxDynamicSharedMemorySize,BP.ftier[0].ldsbytes));
-		c->tierL_ok = (static_cast<uint64_t>(c->H.nrows+1)*(c->H.nsup+1) <= BP.ftierL.tabcap) && BP.ftierL.ldsbytes <= 160*1024 && ((c->env_tiers>>2)&1);
-		if ( c->tierL_ok && BP.ftierL.ldsbytes > 64*1024 ) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_window_long),hipFuncAttributeMaxDynamicSharedMemorySize,BP.ftierL.ldsbytes));
-		if ( BP.ftier[1].ldsbytes > 64*1024 ) HIPCHK(hipFuncSetAttribute(c->widetier ? reinterpret_cast<const void *>(k_window_fast<8>) : (BP.deep ? reinterpret_cast<const void *>(k_window_fast<2>) : reinterpret_cast<const void *>(k_window_fast<6>)),hipFuncAttributeMaxDynamicSharedMemorySize,BP.ftier[1].ldsbytes));
-		if ( BP.ftier[2].ldsbytes > 64*1024 ) HIPCHK(hipFuncSetAttribute(c->widetier ? reinterpret_cast<const void *>(k_window_fast<9>) : reinterpret_cast<const void *>(k_window_fast<3>),hipFuncAttributeMaxDynamicSharedMemorySize,BP.ftier[2].ldsbytes));
+		if ( TP.ok[ID_LONG] && BP.ftierL.ldsbytes > 64*1024 ) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_window_long),hipFuncAttributeMaxDynamicSharedMemorySize,BP.ftierL.ldsbytes));
 		c->retry_grid = boundByArena(wg < 512 ? wg : 512,BP.caps.bytes,8);
 		c->win_grid = c->retry_grid;
 		// generic engine on the second stream (windows with a string of more than 64 bases): a wavefront per window as far
@@ -1066,16 +992,14 @@ static int dacc_submit_piles_body(dacc_ctx * c, dacc_pile const * piles, uint64_
 		while ( c->early_grid > 16 && static_cast<uint64_t>(c->early_grid)*BP.caps.bytes > (8ull<<30) ) c->early_grid >>= 1;
 		HIPCHK(c->d_gearly.ensure(BP.nwindows+2)); HIPCHK(c->d_pregenlist.ensure(BP.nwindows+2)); HIPCHK(c->d_pregen.ensure((BP.nwindows+31)/32+2)); HIPCHK(c->d_pregen2.ensure((BP.nwindows+31)/32+2));
 		HIPCHK(c->d_arena2.ensure(static_cast<size_t>(c->early_grid)*BP.caps.bytes));
-		HIPCHK(c->d_work.ensure(64));
+		HIPCHK(c->d_work.ensure(WORK_WORDS));
 		HIPCHK(c->d_arena.ensure(static_cast<size_t>(c->retry_grid)*BP.caps.bytes));
 	}
 	else
 	{
 		c->win_grid = boundByArena(wg,BP.caps.bytes,8);
 		c->retry_grid = c->win_grid; c->early_grid = 0;
-		for ( int t = 0; t < 3; ++t ) c->tier_ok[t] = 0;
-		c->tier0_ok = false; c->tier7_ok = false; c->tierL_ok = 0;
-		HIPCHK(c->d_work.ensure(64));
+		HIPCHK(c->d_work.ensure(WORK_WORDS));
 		HIPCHK(c->d_arena.ensure(static_cast<size_t>(c->win_grid)*BP.caps.bytes));
 	}
 	HIPCHK(c->d_wrec.ensure((BP.nwindows+1)*static_cast<size_t>(DACC_WREC_OF(c->par.w)))); HIPCHK(c->d_wout.ensure(BP.nwindows+1));

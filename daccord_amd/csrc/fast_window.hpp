@@ -30,14 +30,30 @@
  *  - stretches are looked up by first / last node through small index arrays, the weights of a feasible (stretch,
  *    position) entry carry the weights of its end nodes, candidates are kept as stretch sequences and decoded once.
  *
- * The same code is instantiated for five capacity tiers (FastTier<1..3>: 3, 2 and 1 wavefronts per CU; <4>: deep piles,
- * 3 per CU; <5>: strings of up to 128 bases, 1 per CU; the layout
- * FastLds<CT> is a compile time constant, so every LDS access has an immediate offset).  processWindowFast returns
+ * The same code is instantiated for twelve capacity tiers (FastTier<N> below; the layout FastLds<CT> is a compile time constant,
+ * so every LDS access has an immediate offset).  Which of them a batch runs, in which order and behind which switches, is
+ * written down once, in tier_pipeline.hpp.
+ *
+ *   tier  role                                                        layout  path/stretch ids  wavefronts per CU
+ *      0  front of slot 0, shallow: the small size class              gw       8 /  8 bit       8
+ *      7  front of slot 0, shallow: the middle size class             gw       8 /  8 bit       7
+ *      1  slot 0 of shallow batches                                   gw       8 /  8 bit       6
+ *      4  slot 0 of deep batches (many strings, small graph)          gw       8 /  8 bit       5
+ *      6  slot 1 of shallow batches (strings of up to 128 bases)      gw       8 /  8 bit       4
+ *      2  slot 1 of deep batches                                      gw       8 /  8 bit       3
+ *     10  front of slot 2, shallow: dense graphs                      gw      16 /  8 bit       2
+ *     11  front of slot 2, deep: many instances                       gw      16 /  8 bit       2
+ *      3  slot 2 of shallow and deep batches                          gw      16 / 16 bit       1
+ *      8  slot 1 of wide batches (w = 64 ... 127)                     gw      16 /  8 bit       2
+ *      9  slot 2 of wide batches                                      gw      16 / 16 bit       1
+ *      5  second stream (k_window_long): strings of up to 128 bases   legacy  16 /  8 bit       1
+ *
+ * processWindowFast returns
  * FW_NEXT when a window overflows a tier (flags say what overflowed: 1 instances, 2 nodes, 8 candidates, 16 walk,
  * 32 stretches, 64 links, 128 weights, 512 pools (0x4000 reverse cache, 0x8000 path ids, 0x10000 forward pool,
  * 0x20000 popped paths, 0x40000 score intervals), 1024 introsort depth, 2048 base length, 4096 candidate length /
- * sequence, 8192 gap filling) and FW_GENERIC for shapes the tier does not support (w > 63, a string longer than its
- * string stride: 64 bases in tiers 1-4, 128 in tier 5); those go to tier 5 / the generic engine (dbg_window.hpp).
+ * sequence, 8192 gap filling) and FW_GENERIC for shapes the tier does not support (a window wider than it holds, a string
+ * longer than its string stride lstr: 64 or 128 bases); those go to tier 5 / the generic engine (dbg_window.hpp).
  */
 #ifndef DACC_FAST_WINDOW_HPP
 #define DACC_FAST_WINDOW_HPP
@@ -45,28 +61,19 @@
 #include "dev_types.hpp"
 #include "arena.hpp"
 #include "window_main.hpp"
+#include "tier_pipeline.hpp"
 
 namespace dacc {
 
 enum { WS_RETRY = 4 };
 enum { FNOPAR = 0xFF };
-enum { FSUPCAP = 128, FSUPCAPW = 192 };      // (W: the wide tier -- the table of w = 127 covers 165 read offsets)
-enum { FSEQCAP = 48 };      // max stretches of one candidate path     // max width (read offsets) of the model table copy in LDS
-
-// run time description of a capacity tier (host planning, launch parameters)
-struct FastCaps
-{
-	uint32_t maxs, precap, ncap, scap, lcap, wcap, rccap, fcap, siqcap, blcap;
-	uint32_t tabcap;             // 32-bit words the table overlay of this tier can hold
-	uint32_t nrows, nsup;        // dimensions of the fixed-point table copy held in LDS
-	uint32_t ldsbytes;
-	uint32_t gbytes;             // gw tiers: bytes of global scratch per workgroup (0: none)
-};
+enum { FSEQCAP = 48 };      // max stretches of one candidate path
+// (FastCaps, the run time description of a tier, and FSUPCAP / FSUPCAPW: tier_pipeline.hpp)
 
 struct FSI { uint64_t w; uint16_t left, right, current, path; };   // ScoreInterval (left/right/current: sorted reverse entries, path: forward pop index)
 struct FCC { uint64_t w; uint32_t o, l; };                                       // ConsensusCandidate
 
-// compile time capacities of the two tiers: every LDS offset below is an instruction immediate
+// compile time capacities of the tiers: every LDS offset below is an instruction immediate
 template<int TIER> struct FastTier;
 // gw: the weights of the feasible (stretch, position) pairs and the model table live in global memory (a scratch slab per
 // workgroup / the padded 32 bit table), the build-phase arrays are overlaid by the enumeration pools (spilled to the slab
@@ -87,8 +94,7 @@ template<> struct FastTier<0> { typedef uint8_t id_t; typedef uint8_t sid_t; enu
 // used to run have at most 28 strings, 704 k-mer instances, 640 nodes and 800 links (emulation, 16 piles of config 2: 4244 of 5295); the
 // pre-pass sends them here, what overflows joins tier 1's list like tier 0's hand-overs join this one.
 template<> struct FastTier<7> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 896, rch = DACC_RCH01, fch = 4, fnw = 2, fnc = 32, idmax = 250, rpstcap = 256, lstr = 64, maxs = 28, precap = 704, ncap = 640, scap = 104, lcap = 800, wcap = 896, rccap = 112, fcap = 148, siqcap = 56, blcap = 96, seqcap = 32, psiq = 8, consrow = 64, lscrids = 2048, wide = 0 }; };
-enum : uint32_t { T0INST_DEFAULT = 576, T7INST_DEFAULT = 704 };      // a window with more k-mer instances (upper bound of the pre-pass) starts in tier 1; run-time
-                                               // argument of the pre-pass (DACC_T0INST overrides it for sweeps)
+// (the size-class thresholds of the pre-pass, T0INST_DEFAULT / T7INST_DEFAULT = the instance capacities of tiers 0 and 7: tier_pipeline.hpp)
 // tier 2: gw layout as well since round 3 (43 KB: 3 wavefronts per CU; the legacy layout was 80.5 KB: 2 per CU)
 // (round 4: 76 KB = 2 wavefronts per CU instead of 46.5 KB = 3, with tier 3's node capacity: at 54x more than half of what the deep tier
 // hands on has more than 1024 nodes at filter frequency 1 and used to go through this tier only to be handed on again to tier 3, which

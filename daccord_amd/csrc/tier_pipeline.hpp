@@ -1,0 +1,176 @@
+/*
+ * The pipeline of LDS capacity tiers of the window stage, once and as data (host only, plain C++17: the planner, the launches
+ * of capi.hip and the CPU emulation of the tests all read it from here).
+ *
+ * Every window runs through a chain of tiers (FastTier<N>, fast_window.hpp); which tiers, in which order, depends on the batch:
+ *
+ *   shallow batches   slot 0: 0 -> 7 -> 1     slot 1: 6     slot 2: 10 -> 3
+ *   deep batches      slot 0: 4               slot 1: 2     slot 2: 11 -> 3
+ *   wide batches                              slot 1: 8     slot 2: 9
+ *   every batch       tier 5 on the second stream (k_window_long), in front of the generic engine there
+ *
+ * (TIER_CHAIN below: one row per stage, one column per batch shape.)
+ *
+ * A slot is one entry of dacc_timing.tier_ms[3] / tier_out[3].  Its MAIN tier takes what the slot in front handed on (slot 0: all
+ * windows) and hands on to the next slot, the last one to the generic engine.  FRONT tiers run before the main tier of their slot
+ * with more wavefronts per CU: each hands on to the next stage of its slot.  Tiers 0 and 7 are fed by the size-class pre-pass
+ * (k_classify), tiers 10 / 11 by the list of the slot in front.
+ */
+#ifndef DACC_TIER_PIPELINE_HPP
+#define DACC_TIER_PIPELINE_HPP
+#include <cstdint>
+#include <cstdlib>
+#include <algorithm>
+
+namespace dacc {
+
+// run time description of a capacity tier (host planning, launch parameters)
+struct FastCaps
+{
+	uint32_t maxs, precap, ncap, scap, lcap, wcap, rccap, fcap, siqcap, blcap;
+	uint32_t tabcap;             // 32-bit words the table overlay of this tier can hold
+	uint32_t nrows, nsup;        // dimensions of the fixed-point table copy held in LDS
+	uint32_t ldsbytes;
+	uint32_t gbytes;             // gw tiers: bytes of global scratch per workgroup (0: none)
+};
+enum { FSUPCAP = 128, FSUPCAPW = 192 };      // max width (read offsets) of the model table copy in LDS (W: the wide tiers -- the table of w = 127 covers 165 read offsets)
+enum : uint32_t { T0INST_DEFAULT = 576, T7INST_DEFAULT = 704 };      // a window with more k-mer instances (upper bound of the pre-pass) starts in tier 7 / tier 1; run-time
+                                               // arguments of the pre-pass (DACC_T0INST / DACC_T7INST override them for sweeps)
+
+// The tiers.  KERNEL: those with a kernel of their own (k_window_fast<N>, window_kernels.hpp); tier 5 runs inside k_window_long.
+#define DACC_KERNEL_TIERS(X) X(0) X(1) X(2) X(3) X(4) X(6) X(7) X(8) X(9) X(10) X(11)
+#define DACC_ALL_TIERS(X) DACC_KERNEL_TIERS(X) X(5)
+
+// From a run-time tier number to its compile-time capacities: f is called with a TierTag<N>, whose `type` is FastTier<N>
+template<int TIER> struct FastTier;
+template<int TIER> struct TierTag { typedef FastTier<TIER> type; };
+template<typename F> static inline auto withTier(uint32_t const tier, F && f) -> decltype(f(TierTag<0>()))
+{
+#define DACC_TIER_CASE(N) case N: return f(TierTag<N>());
+	switch ( tier ) { DACC_ALL_TIERS(DACC_TIER_CASE) }
+#undef DACC_TIER_CASE
+	std::abort();
+}
+
+enum TierRole { ROLE_FRONT, ROLE_MAIN, ROLE_LONG };      // front tier of a slot, the slot's main tier, tier 5 on the second stream
+// What switches a stage off, beside its bit of DACC_TIERS, its LDS size (at most the 160 KiB of a CU) and a batch shape it has no tier
+// for (TIER_NONE: "not in a wide batch", "not in a deep batch").  A front tier also needs the main tier of its slot.
+enum : uint32_t
+{
+	GATE_TABFIT = 1,      // the tier's table overlay must hold the model table: (nrows+1)*(nsup+1) <= tabcap
+	GATE_PREV_FRONT = 2,  // needs the front tier before it (tier 7 needs tier 0)
+	GATE_T7_ABOVE_T0 = 4, // only with DACC_T7INST > DACC_T0INST (else the middle size class is empty)
+	GATE_DENSE = 8,       // DACC_DENSE_TIER=0 switches it off
+	GATE_PREV_SLOT = 16,  // needs the main tier of the slot in front as well (the dense tiers need slots 1 and 2)
+	STAGE_PREPASS = 32,   // (no gate) fed by the size-class pre-pass instead of the list in front of it
+	STAGE_ADAPTIVE = 64   // (no gate) switches itself off for the rest of a context when it hands on too much (DACC_T7_ADAPT)
+};
+// counters of d_work (32 bit words): eight per-XCD work counters for every kernel that pulls its windows (window_kernels.hpp: next_window)
+enum : uint32_t { WORK_SLOT0 = 0, WORK_SLOT1 = 8, WORK_SLOT2 = 16, WORK_DENSE = 24, WORK_GENERIC = 32, WORK_T0 = 40, WORK_T7 = 48,
+	WORK_PRE_MID = 56, WORK_PRE_BIG = 57,      // what the pre-pass itself put on the middle and the big list (for dacc_timing)
+	WORK_TRACE = 60, WORK_WORDS = 64 };
+
+// The stages, in the order they run; their place in this table is their place in BatchPlan::stageCaps, TierPipeline and dacc_ctx::st.
+enum TierId { ID_T0, ID_T7, ID_SLOT0, ID_SLOT1, ID_DENSE, ID_SLOT2, ID_LONG, TIER_NSTAGES };
+enum { TIER_NSLOTS = 3, TIER_NONE = 255, TIER_SHALLOW_FIRST = 1 };      // (the first slot's main tier of shallow batches: a batch whose windows mostly overflow its strings / instances is deep)
+struct TierStage { uint8_t tier[3] /* in a shallow, deep, wide batch */, slot, role; int8_t tiersbit /* bit of DACC_TIERS */; uint32_t flags, work; };
+static TierStage const TIER_CHAIN[TIER_NSTAGES] = {
+	{ { 0, TIER_NONE, TIER_NONE }, 0, ROLE_FRONT, 3, STAGE_PREPASS, WORK_T0 },
+	{ { 7, TIER_NONE, TIER_NONE }, 0, ROLE_FRONT, 4, STAGE_PREPASS|STAGE_ADAPTIVE|GATE_PREV_FRONT|GATE_T7_ABOVE_T0, WORK_T7 },
+	{ { 1, 4, TIER_NONE }, 0, ROLE_MAIN, 0, GATE_TABFIT, WORK_SLOT0 },
+	{ { 6, 2, 8 }, 1, ROLE_MAIN, 1, GATE_TABFIT, WORK_SLOT1 },
+	{ { 10, 11, TIER_NONE }, 2, ROLE_FRONT, -1, GATE_TABFIT|GATE_DENSE|GATE_PREV_SLOT, WORK_DENSE },
+	{ { 3, 3, 9 }, 2, ROLE_MAIN, 2, GATE_TABFIT, WORK_SLOT2 },
+	{ { 5, 5, 5 }, 0, ROLE_LONG, 2, GATE_TABFIT, 0 } };
+static TierId const TIER_MAIN[TIER_NSLOTS] = { ID_SLOT0, ID_SLOT1, ID_SLOT2 };
+// does the stage run in a batch of this shape, and the tier whose capacities the plan holds for it (a stage that does not run keeps
+// those of the nearest shape: the first slot of a wide batch has tier 1's or tier 4's)
+static inline bool stageRuns(TierStage const & st, bool const deep, bool const wide) { return st.tier[wide ? 2 : deep] != TIER_NONE; }
+static inline uint32_t stageTier(TierStage const & st, bool const deep, bool const wide)
+{
+	return (wide && st.tier[2] != TIER_NONE) ? st.tier[2] : (st.tier[deep] != TIER_NONE ? st.tier[deep] : st.tier[0]);
+}
+
+// the environment switches of the chain, read once per context
+struct TierSwitches
+{
+	bool nofast;              // DACC_NOFAST=1: generic engine only
+	uint32_t tiers;           // DACC_TIERS: bit t enables the main tier of slot t (bit 2: tier 5 as well), bit 3 tier 0 (size classes), bit 4 tier 7 (the middle class)
+	bool widetier;            // DACC_WIDE_TIER=0: wide batches run in the generic engine only, as in rounds 4-5
+	bool dense;               // DACC_DENSE_TIER=0: the second slot hands on to tier 3 directly (before round 6's dense tiers)
+	bool long128;             // DACC_LONG128=0: windows with a string of 65 ... 128 bases run in tier 5 on the second stream (rounds 3-5)
+	bool hand;                // DACC_HAND=0: no hand-over buffer, every hand-over restarts from the strings
+	uint32_t t0inst, t7inst;  // DACC_T0INST / DACC_T7INST: size-class thresholds (k-mer instances) of tiers 0 and 7
+	uint32_t lds_t1, lds_t0;  // DACC_LDS_T1 / DACC_LDS_T0, measurement only: LDS bytes requested for the first slot's main tier / for tier 0 (more than it needs = fewer wavefronts per CU)
+};
+static inline TierSwitches readTierSwitches()
+{
+	auto const off = [](char const * const name) { char const * const e = getenv(name); return e && e[0] == '0'; };
+	auto const num = [](char const * const name, uint32_t const dflt) { char const * const e = getenv(name); return e ? static_cast<uint32_t>(atoi(e)) : dflt; };
+	TierSwitches S;
+	{ char const * const e = getenv("DACC_NOFAST"); S.nofast = e && e[0] == '1'; }
+	S.tiers = num("DACC_TIERS",31);
+	S.widetier = !off("DACC_WIDE_TIER"); S.dense = !off("DACC_DENSE_TIER"); S.long128 = !off("DACC_LONG128"); S.hand = !off("DACC_HAND");
+	S.t0inst = num("DACC_T0INST",T0INST_DEFAULT); S.t7inst = num("DACC_T7INST",T7INST_DEFAULT);
+	S.lds_t1 = num("DACC_LDS_T1",0); S.lds_t0 = num("DACC_LDS_T0",0);
+	return S;
+}
+
+enum : uint32_t { TIER_LDS_CU = 160*1024 };
+// launch geometry of a tier: floor(160 KiB / ldsbytes) wavefronts per CU, 1 ... 8, and a workgroup per window up to 256 CUs' worth
+static inline uint32_t tierGrid(uint32_t const ldsbytes, uint64_t const nwindows)
+{
+	uint64_t const percu = std::min<uint64_t>(8,std::max<uint64_t>(1,TIER_LDS_CU / (ldsbytes ? ldsbytes : 1)));
+	return static_cast<uint32_t>(std::min<uint64_t>(256*percu,std::max<uint64_t>(8,((nwindows+7)/8)*8)));
+}
+
+// The chain of one batch with every gate resolved, by TierId.
+struct TierPipeline
+{
+	bool usefast = false;                 // the LDS tiers may run at all
+	bool widetier = false;                // wide windows (w = 64 ... 127) in tiers 8 and 9
+	bool ok[TIER_NSTAGES] = {};
+	uint32_t tier[TIER_NSTAGES] = {};     // the tier of the stage in this batch
+	bool late_long = false;               // slots 1 and 2 skip only the windows the second stream has (a string of more than 128 bases), not all with more than 64
+	bool slot1_long = false;              // the pre-scan puts the windows with a string of 65 ... 128 bases on the first slot's hand-over list
+	bool handover = false;                // hand-over slots pay: a wide batch has nothing to hand the sorted instances to
+	uint32_t handwords = 0;               // 64 bit words of a hand-over slot: header + the instance capacity of the tiers that hand on + their last k-mer lists
+	bool slotok(uint32_t const s) const { return ok[TIER_MAIN[s]]; }
+	bool anytier() const { return slotok(0) || slotok(1) || slotok(2); }
+};
+
+// fastpath: the caller's own conditions (not switched off, a model table that fits 32 bit fixed point).  capsOf(id): the plan's capacities
+// of a stage (BatchPlan::stageCaps); the measurement switches DACC_LDS_T1 / DACC_LDS_T0 raise the LDS sizes in them.
+template<typename C>
+static inline TierPipeline resolveTiers(TierSwitches const & S, bool const fastpath, bool const deep, bool const wide, uint32_t const nrows, uint32_t const nsup, uint32_t const w, C && capsOf)
+{
+	TierPipeline R;
+	// wide windows, w = 64 ... 127 (model table of up to 128 rows): DACC_WIDE_TIER=0 leaves them to the generic engine, w = 128 always
+	R.widetier = wide && S.widetier && nrows <= 128 && nsup <= FSUPCAPW;
+	R.usefast = fastpath && (R.widetier || (nrows <= 64 && nsup <= FSUPCAP && w <= 63));
+	R.handover = S.hand && !R.widetier;
+	R.handwords = (deep ? 2048u + 128u : 1024u + 64u) + 4u;
+	auto const gated = [&](uint32_t const i) -> bool
+	{
+		TierStage const & st = TIER_CHAIN[i]; FastCaps const & F = capsOf(i);
+		return R.usefast && stageRuns(st,deep,wide) && F.ldsbytes <= TIER_LDS_CU && (st.tiersbit < 0 || ((S.tiers >> st.tiersbit) & 1))
+			&& (!(st.flags & GATE_TABFIT) || static_cast<uint64_t>(nrows+1)*(nsup+1) <= F.tabcap)
+			&& (!(st.flags & GATE_T7_ABOVE_T0) || S.t7inst > S.t0inst) && (!(st.flags & GATE_DENSE) || S.dense);
+	};
+	{ FastCaps & F = capsOf(ID_SLOT0); if ( S.lds_t1 > F.ldsbytes && S.lds_t1 <= TIER_LDS_CU ) F.ldsbytes = S.lds_t1; }
+	{ FastCaps & F = capsOf(ID_T0); if ( S.lds_t0 > F.ldsbytes && S.lds_t0 <= TIER_LDS_CU ) F.ldsbytes = S.lds_t0; }
+	for ( uint32_t i = 0; i < TIER_NSTAGES; ++i ) { R.tier[i] = stageTier(TIER_CHAIN[i],deep,wide); if ( TIER_CHAIN[i].role != ROLE_FRONT ) R.ok[i] = gated(i); }
+	// the front tiers, in chain order (a front tier stands before the main tier of its slot)
+	for ( uint32_t i = 0; i < TIER_NSTAGES; ++i )
+	{
+		TierStage const & st = TIER_CHAIN[i];
+		if ( st.role == ROLE_FRONT )
+			R.ok[i] = gated(i) && R.slotok(st.slot) && (!(st.flags & GATE_PREV_FRONT) || R.ok[i-1]) && (!(st.flags & GATE_PREV_SLOT) || R.slotok(st.slot-1));
+	}
+	R.late_long = R.slotok(0) && S.long128;
+	R.slot1_long = R.late_long && (R.slotok(1) || R.slotok(2));
+	return R;
+}
+
+}
+#endif

@@ -1,7 +1,8 @@
 /*
- * The window kernels of libdaccord_hip.so, one translation unit each (k_fast_<tier>.hip, k_generic.hip): the seven of them are 150-260 KB
- * of gfx950 code apiece and took 25 minutes to compile one after the other inside capi.hip; as separate objects they compile side by side
- * (daccord_amd/build.py).  This header holds what the units share: the work distribution, the kernel template of the LDS tiers (defined
+ * The window kernels of libdaccord_hip.so, one translation unit each (k_fast_<tier>.hip for the eleven tiers of DACC_KERNEL_TIERS,
+ * tier_pipeline.hpp -- the table of the tiers is at the head of fast_window.hpp --, and k_generic.hip, which also holds tier 5): they are
+ * 150-260 KB of gfx950 code apiece and took 25 minutes to compile one after the other inside capi.hip; as separate objects they compile
+ * side by side (daccord_amd/build.py).  This header holds what the units share: the work distribution, the kernel template of the LDS tiers (defined
  * here, instantiated explicitly in k_fast_<tier>.hip, declared `extern template` for capi.hip's launches) and the prototypes of the two
  * kernels of the generic engine (defined in k_generic.hip).  Same device code as before the split: build.kernel_isa_hashes() is unchanged.
  */
@@ -90,16 +91,17 @@ __global__ void __launch_bounds__(64) DACC_WPE(TIER) k_window_fast(FastBatch FB,
 
 #if !defined(DACC_INSTANTIATE_TIER)
 // every unit but k_fast_<tier>.hip: the tiers' kernels are instantiated elsewhere
-extern template __global__ void k_window_fast<0>(FastBatch, uint32_t const *, uint32_t *);
-extern template __global__ void k_window_fast<1>(FastBatch, uint32_t const *, uint32_t *);
-extern template __global__ void k_window_fast<2>(FastBatch, uint32_t const *, uint32_t *);
-extern template __global__ void k_window_fast<3>(FastBatch, uint32_t const *, uint32_t *);
-extern template __global__ void k_window_fast<4>(FastBatch, uint32_t const *, uint32_t *);
-extern template __global__ void k_window_fast<6>(FastBatch, uint32_t const *, uint32_t *);
-extern template __global__ void k_window_fast<7>(FastBatch, uint32_t const *, uint32_t *);
-extern template __global__ void k_window_fast<8>(FastBatch, uint32_t const *, uint32_t *);
-extern template __global__ void k_window_fast<9>(FastBatch, uint32_t const *, uint32_t *);
-extern template __global__ void k_window_fast<10>(FastBatch, uint32_t const *, uint32_t *);
-extern template __global__ void k_window_fast<11>(FastBatch, uint32_t const *, uint32_t *);
+#define DACC_EXTERN_TIER(N) extern template __global__ void k_window_fast<N>(FastBatch, uint32_t const *, uint32_t *);
+DACC_KERNEL_TIERS(DACC_EXTERN_TIER)
+#undef DACC_EXTERN_TIER
+// the kernel of a run-time tier number (launches and hipFuncSetAttribute of capi.hip)
+typedef void (*FastKernel)(FastBatch, uint32_t const *, uint32_t *);
+static inline FastKernel fastKernel(uint32_t const tier)
+{
+#define DACC_KERNEL_CASE(N) case N: return k_window_fast<N>;
+	switch ( tier ) { DACC_KERNEL_TIERS(DACC_KERNEL_CASE) }
+#undef DACC_KERNEL_CASE
+	return 0;
+}
 #endif
 #endif

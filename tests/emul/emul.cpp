@@ -218,26 +218,23 @@ int emul_run(void * v, dacc_pile const * piles, uint64_t npiles, dacc_overlap co
 		WB.P = P; WB.T = T; WB.C = caps; WB.bps = c->bps.data(); WB.boff = c->boff.data(); WB.rlen = c->rlen.data();
 		WB.piles = BP.piles.data(); WB.npiles = BP.piles.size(); WB.ovl = BP.ovl.data(); WB.wt_b = wt_b.data(); WB.wt_e = wt_e.data();
 		WB.nwindows = BP.nwindows; WB.wrec = wrec.data(); WB.wout = wout.data(); WB.arena = arena.data(); WB.prof = 0; WB.pregen = 0;
-		FastBatch FB[3]; FastBatch FB0, FB7;
-		// hand-over slots as in the library (DACC_HAND=0: off)
-		uint32_t const handwords = (BP.wide ? 4096u + 128u : (BP.deep ? 2048u + 128u : 1024u + 64u)) + 4u;
-		bool const handon = !(getenv("DACC_HAND") && getenv("DACC_HAND")[0] == '0') && c->par.klow == c->par.khigh;
-		std::vector<uint64_t> hand(handon ? static_cast<size_t>(BP.nwindows+1)*handwords : 1); uint32_t handctr = 0;
+		// the chain of LDS tiers as the library resolves it (tier_pipeline.hpp: the same switches, gates and stages as capi.hip)
+		TierSwitches const sw = readTierSwitches();
+		bool big = false; for ( size_t i = 0; i < c->H.dpsq_vst.size(); ++i ) if ( c->H.dpsq_vst[i] >> 32 ) big = true;
+		TierPipeline const TP = resolveTiers(sw,c->usefast && !sw.nofast && !big,BP.deep,BP.wide,c->H.nrows,c->H.nsup,c->par.w,[&](uint32_t const id) -> FastCaps & { return BP.stageCaps(id); });
+		// hand-over slots as in the library, one per window here
+		bool const usehand = TP.handover && c->par.klow == c->par.khigh;
+		std::vector<uint64_t> hand(usehand ? static_cast<size_t>(BP.nwindows+1)*TP.handwords : 1); uint32_t handctr = 0;
 		// (pattern in the slots that can be used first; the whole buffer is 8 KB per window of the batch and stays untouched pages otherwise)
 		std::fill(hand.begin(),hand.begin()+std::min<size_t>(hand.size(),(64u<<20)/8u),0x0101010101010101ull*arenafill);
-		std::vector<uint8_t> lds[3]; std::vector<uint8_t> gslab[3]; std::vector<uint8_t> lds0, gslab0, lds7, gslab7;
-		bool big = false; for ( size_t i = 0; i < c->H.dpsq_vst.size(); ++i ) if ( c->H.dpsq_vst[i] >> 32 ) big = true;
-		// (round 6) wide windows (w 64 ... 127: nrows = w+1 <= 128) run in tier 8, the second slot, alone; DACC_WIDE_TIER=0: generic engine only (rounds 4-5)
-		bool const widetier = BP.wide && !(getenv("DACC_WIDE_TIER") && getenv("DACC_WIDE_TIER")[0] == '0');
-		bool const usefast = c->usefast && !big && (widetier ? (c->H.nrows <= 128 && c->H.nsup <= FSUPCAPW) : (c->H.nrows <= 64 && c->H.nsup <= FSUPCAP && c->par.w <= 63));
-		bool tierok[3];
 		// the library's pre-scan (k_prescan + k_prescan_lists): windows with an active B string of more than 64 bases are flagged (the first
 		// slot's tiers skip them); those with a string of more than 128 bases (second bit map: every tier skips them) are listed for the launch
 		// on the second stream, the others join the list the second slot's tier reads (round 6: tiers 6 and 3 hold strings of up to 128 bases;
 		// DACC_LONG128=0: all of them go to the second stream as in rounds 3-5)
-		std::vector<uint32_t> pregen((BP.nwindows+31)/32+1,0), pregen2((BP.nwindows+31)/32+1,0); std::vector<uint64_t> pregenlist, slot1list;
-		bool const long128 = !(getenv("DACC_LONG128") && getenv("DACC_LONG128")[0] == '0');
-		if ( usefast )
+		std::vector<uint32_t> pregen((BP.nwindows+31)/32+1,0), pregen2((BP.nwindows+31)/32+1,0); std::vector<uint64_t> pregenlist;
+		std::vector<uint64_t> retry[TIER_NSLOTS];      // what every slot hands on
+		auto const bit = [](uint32_t const * const map, uint64_t const w) { return map && ((map[w>>5] >> (w&31)) & 1); };
+		if ( TP.usefast && TP.anytier() )      // (no LDS tier usable: everything runs in the generic engine, no pre-scan, no second stream)
 		{
 			for ( size_t o = 0; o < BP.ovl.size(); ++o )
 			{
@@ -246,217 +243,114 @@ int emul_run(void * v, dacc_pile const * piles, uint64_t npiles, dacc_overlap co
 				{
 					uint32_t const len = wt_e[ov.wtoff+r] - wt_b[ov.wtoff+r];
 					uint64_t const w = winbase + ov.y0 + r;
-					if ( len > (widetier ? 128u : 64u) ) pregen[w>>5] |= 1u << (w&31);
+					if ( len > (TP.widetier ? 128u : 64u) ) pregen[w>>5] |= 1u << (w&31);
 					if ( len > 128u ) pregen2[w>>5] |= 1u << (w&31);
 				}
 			}
 			WB.pregen = pregen.data();
-		}
-		for ( int t = 0; t < 3; ++t )
-		{
-			FB[t].W = WB; FB[t].F = BP.ftier[t]; FB[t].dpsq_vst = c->H.dpsq_vst.data(); FB[t].retry = 0; FB[t].gearly = 0;
-			gslab[t].assign(BP.ftier[t].gbytes+64,arenafill); FB[t].gslab = gslab[t].data(); FB[t].gstride = 0; FB[t].tab32 = c->H.tab32.data();
-			FB[t].hand = handon ? hand.data() : 0; FB[t].handctr = &handctr; FB[t].handcap = handon ? static_cast<uint32_t>(BP.nwindows) : 0u; FB[t].handwords = handwords;
-#if defined(DACC_LEDGER)
-			{ char const * lm = getenv("DACC_LEDGER_MASK"); FB[t].ledger = lm ? static_cast<uint32_t>(strtoul(lm,0,0)) : 0u; }      // (ledger build: phases run twice, results must not move)
-#endif
-			lds[t].assign(BP.ftier[t].ldsbytes+64,arenafill);
-			tierok[t] = usefast && static_cast<uint64_t>(c->H.nrows+1)*(c->H.nsup+1) <= BP.ftier[t].tabcap;
-			if ( widetier && t == 0 ) tierok[t] = false;
-			c->ntier[t] = 0; for ( int i = 0; i < 64; ++i ) c->reasonsT[t][i] = 0; for ( int i = 0; i < 24; ++i ) c->flagbitsT[t][i] = 0;
-		}
-		c->nretry = 0; c->glist.clear();
-		{
-			bool const slot1 = usefast && tierok[0] && (tierok[1] || tierok[2]) && long128;
-			for ( uint64_t w = 0; usefast && w < BP.nwindows; ++w )
-				if ( (pregen[w>>5] >> (w&31)) & 1 )
+			for ( uint64_t w = 0; w < BP.nwindows; ++w )
+				if ( bit(pregen.data(),w) )
 				{
 					wout[w].status = WS_INSUFFICIENT;
-					if ( ((pregen2[w>>5] >> (w&31)) & 1) || !slot1 ) pregenlist.push_back(w); else slot1list.push_back(w);
+					if ( bit(pregen2.data(),w) || !TP.slot1_long ) pregenlist.push_back(w); else retry[0].push_back(w);      // (k_prescan_lists puts them on the first slot's list before its tiers run)
 				}
-			if ( usefast && tierok[0] && long128 ) for ( int t = 1; t < 3; ++t ) FB[t].W.pregen = pregen2.data();
-			if ( usefast && widetier ) { FB[1].W.pregen = pregen2.data(); FB[2].W.pregen = pregen2.data(); }
 		}
-		// tier 0 (size classes) in front of tier 1 of a shallow batch, as in the library (DACC_TIERS bit 3 switches it off)
-		bool const tier0ok = !BP.deep && tierok[0] && !(getenv("DACC_TIERS") && !((atoi(getenv("DACC_TIERS"))>>3)&1));
-		c->ntier0 = 0; c->ntier7 = 0; c->ntier10 = 0;
-		// tier 7 (the middle size class) as in the library: DACC_TIERS bit 4 switches it off, DACC_T7INST is its threshold
-		uint32_t const t0inst = getenv("DACC_T0INST") ? static_cast<uint32_t>(atoi(getenv("DACC_T0INST"))) : static_cast<uint32_t>(T0INST_DEFAULT);
-		uint32_t const t7inst = getenv("DACC_T7INST") ? static_cast<uint32_t>(atoi(getenv("DACC_T7INST"))) : static_cast<uint32_t>(T7INST_DEFAULT);
-		bool const tier7ok = tier0ok && !(getenv("DACC_TIERS") && !((atoi(getenv("DACC_TIERS"))>>4)&1)) && t7inst > t0inst;
-		if ( tier7ok )
+		c->nretry = 0; c->glist.clear();
+		for ( int t = 0; t < 3; ++t ) { for ( int i = 0; i < 64; ++i ) c->reasonsT[t][i] = 0; for ( int i = 0; i < 24; ++i ) c->flagbitsT[t][i] = 0; }
+		// the stages that run: batch record, LDS, global slab, model table
+		FastBatch FB[TIER_NSTAGES]; std::vector<uint8_t> lds[TIER_NSTAGES], gslab[TIER_NSTAGES]; uint64_t ndone[TIER_NSTAGES] = { 0 };
+		auto const loadTables = [&](uint32_t const i) { wave_run([&]() { withTier(TP.tier[i],[&](auto ct) { FastLds<typename decltype(ct)::type> L; L.base = lds[i].data(); fast_load_tables(L,FB[i].F.nrows,FB[i].F.nsup,T,c->H.dpsq_vst.data()); }); }); };
+		for ( uint32_t i = 0; i < TIER_NSTAGES; ++i )
 		{
-			FB7.W = WB; FB7.F = BP.ftier7; FB7.dpsq_vst = c->H.dpsq_vst.data(); FB7.retry = 0; FB7.gearly = 0;
-			gslab7.assign(BP.ftier7.gbytes+64,arenafill); FB7.gslab = gslab7.data(); FB7.gstride = 0; FB7.tab32 = c->H.tab32.data();
-			FB7.hand = handon ? hand.data() : 0; FB7.handctr = &handctr; FB7.handcap = handon ? static_cast<uint32_t>(BP.nwindows) : 0u; FB7.handwords = handwords;
+			if ( !TP.ok[i] ) continue;
+			TierStage const & st = TIER_CHAIN[i]; FastBatch & F = FB[i];
+			bool const second = st.role == ROLE_LONG;      // the second stream's tier: every window of its list, no slab, no hand-over slots
+			F.W = WB; F.F = BP.stageCaps(i); F.dpsq_vst = c->H.dpsq_vst.data(); F.retry = 0; F.gearly = 0; F.gstride = 0; F.tab32 = c->H.tab32.data();
+			if ( second || (st.slot > 0 && TP.late_long) || TP.widetier ) F.W.pregen = second ? 0 : pregen2.data();
+			gslab[i].assign(second ? 0 : F.F.gbytes+64,arenafill); F.gslab = second ? 0 : gslab[i].data();
+			F.hand = (usehand && !second) ? hand.data() : 0; F.handctr = second ? 0 : &handctr; F.handcap = F.hand ? static_cast<uint32_t>(BP.nwindows) : 0u; F.handwords = second ? 0u : TP.handwords;
 #if defined(DACC_LEDGER)
-			{ char const * lm = getenv("DACC_LEDGER_MASK"); FB7.ledger = lm ? static_cast<uint32_t>(strtoul(lm,0,0)) : 0u; }
+			{ char const * lm = getenv("DACC_LEDGER_MASK"); F.ledger = (lm && !second) ? static_cast<uint32_t>(strtoul(lm,0,0)) : 0u; }      // (ledger build: phases run twice, results must not move)
 #endif
-			lds7.assign(BP.ftier7.ldsbytes+64,arenafill);
-			wave_run([&]() { FastLds< FastTier<7> > L; L.base = lds7.data(); fast_load_tables(L,BP.ftier7.nrows,BP.ftier7.nsup,T,c->H.dpsq_vst.data()); });
+			lds[i].assign(F.F.ldsbytes+64,arenafill);
+			loadTables(i);
 		}
-		if ( tier0ok )
+		auto const runWindow = [&](uint32_t const i, uint64_t const wdx, bool const resume) -> int
 		{
-			FB0.W = WB; FB0.F = BP.ftier0; FB0.dpsq_vst = c->H.dpsq_vst.data(); FB0.retry = 0; FB0.gearly = 0;
-			gslab0.assign(BP.ftier0.gbytes+64,arenafill); FB0.gslab = gslab0.data(); FB0.gstride = 0; FB0.tab32 = c->H.tab32.data();
-			FB0.hand = handon ? hand.data() : 0; FB0.handctr = &handctr; FB0.handcap = handon ? static_cast<uint32_t>(BP.nwindows) : 0u; FB0.handwords = handwords;
-#if defined(DACC_LEDGER)
-			{ char const * lm = getenv("DACC_LEDGER_MASK"); FB0.ledger = lm ? static_cast<uint32_t>(strtoul(lm,0,0)) : 0u; }
-#endif
-			lds0.assign(BP.ftier0.ldsbytes+64,arenafill);
-			wave_run([&]() { FastLds< FastTier<0> > L; L.base = lds0.data(); fast_load_tables(L,BP.ftier0.nrows,BP.ftier0.nsup,T,c->H.dpsq_vst.data()); });
-		}
-		// tier 10 (the dense-graph tier) between the second slot's tier 6 and tier 3 of a shallow batch, as in the library (DACC_DENSE_TIER=0 switches it off)
-		FastBatch FBD; std::vector<uint8_t> ldsD, gslabD;
-		bool const tier10ok = usefast && !widetier && tierok[1] && tierok[2] && !(getenv("DACC_DENSE_TIER") && getenv("DACC_DENSE_TIER")[0] == '0')
-			&& static_cast<uint64_t>(c->H.nrows+1)*(c->H.nsup+1) <= BP.ftierD.tabcap;
-		if ( tier10ok )
-		{
-			FBD = FB[2]; FBD.F = BP.ftierD;
-			gslabD.assign(BP.ftierD.gbytes+64,arenafill); FBD.gslab = gslabD.data();
-			ldsD.assign(BP.ftierD.ldsbytes+64,arenafill);
-			wave_run([&]() { if ( BP.deep ) { FastLds< FastTier<11> > L; L.base = ldsD.data(); fast_load_tables(L,BP.ftierD.nrows,BP.ftierD.nsup,T,c->H.dpsq_vst.data()); } else { FastLds< FastTier<10> > L; L.base = ldsD.data(); fast_load_tables(L,BP.ftierD.nrows,BP.ftierD.nsup,T,c->H.dpsq_vst.data()); } });
-		}
-		auto loadTables = [&](int const t)
-		{
-			wave_run([&]() {
-				if ( t == 0 && BP.deep ) { FastLds< FastTier<4> > L; L.base = lds[0].data(); fast_load_tables(L,BP.ftier[0].nrows,BP.ftier[0].nsup,T,c->H.dpsq_vst.data()); }
-				else if ( t == 0 ) { FastLds< FastTier<1> > L; L.base = lds[0].data(); fast_load_tables(L,BP.ftier[0].nrows,BP.ftier[0].nsup,T,c->H.dpsq_vst.data()); }
-				else if ( t == 1 && BP.wide ) { FastLds< FastTier<8> > L; L.base = lds[1].data(); fast_load_tables(L,BP.ftier[1].nrows,BP.ftier[1].nsup,T,c->H.dpsq_vst.data()); }
-				else if ( t == 1 && BP.deep ) { FastLds< FastTier<2> > L; L.base = lds[1].data(); fast_load_tables(L,BP.ftier[1].nrows,BP.ftier[1].nsup,T,c->H.dpsq_vst.data()); }
-				else if ( t == 1 ) { FastLds< FastTier<6> > L; L.base = lds[1].data(); fast_load_tables(L,BP.ftier[1].nrows,BP.ftier[1].nsup,T,c->H.dpsq_vst.data()); }
-				else if ( BP.wide ) { FastLds< FastTier<9> > L; L.base = lds[2].data(); fast_load_tables(L,BP.ftier[2].nrows,BP.ftier[2].nsup,T,c->H.dpsq_vst.data()); }
-				else { FastLds< FastTier<3> > L; L.base = lds[2].data(); fast_load_tables(L,BP.ftier[2].nrows,BP.ftier[2].nsup,T,c->H.dpsq_vst.data()); }
-			});
-		};
-		for ( int t = 0; t < 3; ++t ) loadTables(t);
-		// Same orchestration as the library (capi.hip): every tier is one "kernel" over the list the previous tier
-		// handed over; windows only the generic engine can run go to an early list that is read ONCE, right after the
-		// first tier (later tiers hand such windows on through their ordinary list); the generic engine runs the early
-		// list and, at the end, what the last tier handed over.
-		auto runTier = [&](int const t, uint64_t const wdx, bool const resume) -> int
-		{
-			dacc_emul_curwin = wdx; dacc_emul_curtier = t;
+			dacc_emul_curwin = wdx; dacc_emul_curtier = TP.tier[i];
 			if ( getenv("DACC_EMUL_POISON") )
 			{
 				// debugging aid: no window may depend on what an earlier window (or kernel) left in LDS
-				std::memset(lds[t].data(),atoi(getenv("DACC_EMUL_POISON")),lds[t].size());
-				std::memset(gslab[t].data(),atoi(getenv("DACC_EMUL_POISON")),gslab[t].size());
-				loadTables(t);
+				std::memset(lds[i].data(),atoi(getenv("DACC_EMUL_POISON")),lds[i].size());
+				if ( gslab[i].size() ) std::memset(gslab[i].data(),atoi(getenv("DACC_EMUL_POISON")),gslab[i].size());
+				loadTables(i);
 			}
 			int rc = -1;
-			wave_run([&]() {
-				int r;
-				if ( t == 0 && BP.deep ) r = processWindowFast< FastTier<4> >(FB[0],wdx,lds[0].data(),resume);
-				else if ( t == 0 ) r = processWindowFast< FastTier<1> >(FB[0],wdx,lds[0].data(),resume);
-				else if ( t == 1 && BP.wide ) r = processWindowFast< FastTier<8> >(FB[1],wdx,lds[1].data(),resume);
-				else if ( t == 1 && BP.deep ) r = processWindowFast< FastTier<2> >(FB[1],wdx,lds[1].data(),resume);
-				else if ( t == 1 ) r = processWindowFast< FastTier<6> >(FB[1],wdx,lds[1].data(),resume);
-				else if ( BP.wide ) r = processWindowFast< FastTier<9> >(FB[2],wdx,lds[2].data(),resume);
-				else r = processWindowFast< FastTier<3> >(FB[2],wdx,lds[2].data(),resume);
-				if ( wv_lane() == 0 ) rc = r;
-			});
+			wave_run([&]() { int const r = withTier(TP.tier[i],[&](auto ct) { return processWindowFast<typename decltype(ct)::type>(FB[i],wdx,lds[i].data(),resume); }); if ( wv_lane() == 0 ) rc = r; });
 			return rc;
 		};
-		std::vector<uint64_t> cur, next, gearly, earlysnap;
-		bool haveList = false, early = false;
-		for ( int t = 0; t < 3; ++t )
+		// The library's orchestration (capi.hip: runDevice): every stage is one "kernel" over the list the stage in front handed on
+		// (0: all windows); windows only the generic engine can run go to an early list that is read ONCE, right after the first slot
+		// (later slots hand such windows on through their ordinary list); the generic engine runs the early list and, at the end,
+		// what the last slot handed on.  acct: the slot whose reasons / flag counters take the stage's hand-overs (-1: none).
+		std::vector<uint64_t> gearly, earlysnap; bool early = false;
+		auto const runStage = [&](uint32_t const i, std::vector<uint64_t> const * const in, std::vector<uint64_t> & out, int const acct)
 		{
-			if ( !tierok[t] ) continue;
-			next.clear();
-			if ( t == 0 && tier0ok )
+			uint64_t const n = in ? in->size() : BP.nwindows;
+			for ( uint64_t q = 0; q < n; ++q )
 			{
-				// k_classify + k_window_fast<0> + k_window_fast<7>: the small windows first, then the middle list followed by tier 0's hand-overs;
-				// tier 1 then runs the big list followed by tier 7's hand-overs (without tier 7: by tier 0's)
-				std::vector<uint64_t> small, mid, big;
+				uint64_t const wdx = in ? (*in)[q] : q;
+				if ( bit(FB[i].W.pregen,wdx) ) continue;      // the kernels return at once for these: not counted as run by the tier
+				int const rc = runWindow(i,wdx,in != 0);
+				if ( rc == FW_DONE ) { ++ndone[i]; continue; }
+				if ( acct >= 0 ) { uint32_t const f = wout[wdx].flags; c->reasonsT[acct][(f>>24)&63]++; for ( int b = 0; b < 24; ++b ) if ( (f>>b)&1 ) c->flagbitsT[acct][b]++; }
+				if ( rc == FW_GENERIC && !early ) gearly.push_back(wdx); else out.push_back(wdx);
+			}
+		};
+		std::vector<uint64_t> small, handon[TIER_NSTAGES];      // the pre-pass's small windows, what every front tier hands on
+		std::vector<uint64_t> const * list = 0;
+		for ( uint32_t slot = 0; slot < TIER_NSLOTS; ++slot )
+		{
+			if ( !TP.slotok(slot) ) continue;
+			int const m = TIER_MAIN[slot];
+			int fr[TIER_NSTAGES]; uint32_t nfr = 0;
+			for ( int i = 0; i < m; ++i ) if ( TIER_CHAIN[i].slot == slot && TP.ok[i] ) fr[nfr++] = i;
+			std::vector<uint64_t> const * in = list;
+			if ( nfr && (TIER_CHAIN[fr[0]].flags & STAGE_PREPASS) )
+			{
+				// k_classify: the small windows, the middle list in front of the first front tier's hand-overs, the big list in front of the last one's
+				std::vector<uint64_t> & mid = handon[fr[0]], & bigl = handon[fr[nfr-1]];
 				for ( uint64_t wdx = 0; wdx < BP.nwindows; ++wdx )
 				{
-					if ( WB.pregen && ((WB.pregen[wdx>>5] >> (wdx&31)) & 1) ) continue;
-					uint32_t cls = 0; wave_run([&]() { uint32_t const r = classifyWindow(WB,wdx,t0inst,tier7ok ? t7inst : 0u); if ( wv_lane() == 0 ) cls = r; });
+					if ( bit(WB.pregen,wdx) ) continue;
+					uint32_t cls = 0; wave_run([&]() { uint32_t const r = classifyWindow(WB,wdx,sw.t0inst,nfr > 1 ? sw.t7inst : 0u); if ( wv_lane() == 0 ) cls = r; });
 					wout[wdx].status = WS_INSUFFICIENT;
-					(cls == 0 ? small : (cls == 2 ? mid : big)).push_back(wdx);
+					(cls == 0 ? small : (cls == 2 ? mid : bigl)).push_back(wdx);
 				}
-				for ( size_t i = 0; i < small.size(); ++i )
-				{
-					uint64_t const wdx = small[i];
-					if ( getenv("DACC_EMUL_POISON") ) { std::memset(lds0.data(),atoi(getenv("DACC_EMUL_POISON")),lds0.size()); std::memset(gslab0.data(),atoi(getenv("DACC_EMUL_POISON")),gslab0.size()); wave_run([&]() { FastLds< FastTier<0> > L; L.base = lds0.data(); fast_load_tables(L,BP.ftier0.nrows,BP.ftier0.nsup,T,c->H.dpsq_vst.data()); }); }
-					int rc = -1;
-					dacc_emul_curwin = wdx; dacc_emul_curtier = 100;
-					wave_run([&]() { int const r = processWindowFast< FastTier<0> >(FB0,wdx,lds0.data(),true); if ( wv_lane() == 0 ) rc = r; });
-					if ( rc == FW_DONE ) { ++c->ntier0; continue; }
-					if ( rc == FW_GENERIC ) gearly.push_back(wdx); else (tier7ok ? mid : big).push_back(wdx);
-				}
-				for ( size_t i = 0; i < mid.size(); ++i )
-				{
-					uint64_t const wdx = mid[i];
-					if ( getenv("DACC_EMUL_POISON") ) { std::memset(lds7.data(),atoi(getenv("DACC_EMUL_POISON")),lds7.size()); std::memset(gslab7.data(),atoi(getenv("DACC_EMUL_POISON")),gslab7.size()); wave_run([&]() { FastLds< FastTier<7> > L; L.base = lds7.data(); fast_load_tables(L,BP.ftier7.nrows,BP.ftier7.nsup,T,c->H.dpsq_vst.data()); }); }
-					int rc = -1;
-					dacc_emul_curwin = wdx; dacc_emul_curtier = 107;
-					wave_run([&]() { int const r = processWindowFast< FastTier<7> >(FB7,wdx,lds7.data(),true); if ( wv_lane() == 0 ) rc = r; });
-					if ( rc == FW_DONE ) { ++c->ntier7; continue; }
-					if ( rc == FW_GENERIC ) gearly.push_back(wdx); else big.push_back(wdx);
-				}
-				cur.swap(big); haveList = true;
+				in = &small;
 			}
-			if ( t == 2 && tier10ok && haveList )
-			{
-				// k_window_fast<10> over the second slot's hand-overs; tier 3 then runs what it hands on
-				std::vector<uint64_t> cur10;
-				for ( size_t i = 0; i < cur.size(); ++i )
-				{
-					uint64_t const wdx = cur[i];
-					if ( FBD.W.pregen && ((FBD.W.pregen[wdx>>5] >> (wdx&31)) & 1) ) { cur10.push_back(wdx); continue; }      // (skipped by tier 3 as well)
-					if ( getenv("DACC_EMUL_POISON") ) { std::memset(ldsD.data(),atoi(getenv("DACC_EMUL_POISON")),ldsD.size()); std::memset(gslabD.data(),atoi(getenv("DACC_EMUL_POISON")),gslabD.size()); wave_run([&]() { if ( BP.deep ) { FastLds< FastTier<11> > L; L.base = ldsD.data(); fast_load_tables(L,BP.ftierD.nrows,BP.ftierD.nsup,T,c->H.dpsq_vst.data()); } else { FastLds< FastTier<10> > L; L.base = ldsD.data(); fast_load_tables(L,BP.ftierD.nrows,BP.ftierD.nsup,T,c->H.dpsq_vst.data()); } }); }
-					int rc = -1;
-					dacc_emul_curwin = wdx; dacc_emul_curtier = 110;
-					wave_run([&]() { int const r = BP.deep ? processWindowFast< FastTier<11> >(FBD,wdx,ldsD.data(),true) : processWindowFast< FastTier<10> >(FBD,wdx,ldsD.data(),true); if ( wv_lane() == 0 ) rc = r; });
-					if ( rc == FW_DONE ) { ++c->ntier10; continue; }
-					cur10.push_back(wdx);
-				}
-				cur.swap(cur10);
-			}
-			uint64_t const n = haveList ? cur.size() : BP.nwindows;
-			for ( uint64_t i = 0; i < n; ++i )
-			{
-				uint64_t const wdx = haveList ? cur[i] : i;
-				if ( FB[t].W.pregen && ((FB[t].W.pregen[wdx>>5] >> (wdx&31)) & 1) ) continue;      // the kernels return at once for these: not counted as run by the tier
-				int const rc = runTier(t,wdx,haveList);
-				if ( rc == FW_DONE ) { ++c->ntier[t]; continue; }
-				uint32_t const f = wout[wdx].flags; c->reasonsT[t][(f>>24)&63]++; for ( int b = 0; b < 24; ++b ) if ( (f>>b)&1 ) c->flagbitsT[t][b]++;
-				if ( rc == FW_GENERIC && !early ) gearly.push_back(wdx); else next.push_back(wdx);
-			}
-			if ( t == 0 && !slot1list.empty() ) { next.insert(next.begin(),slot1list.begin(),slot1list.end()); slot1list.clear(); }      // (k_prescan_lists appended them before the tier ran)
-			cur.swap(next); haveList = true;
+			for ( uint32_t k = 0; k < nfr; ++k ) { runStage(fr[k],in,handon[fr[k]],-1); in = &handon[fr[k]]; }
+			runStage(m,in,retry[slot],slot);
+			list = &retry[slot];
 			if ( !early ) { early = true; earlysnap = gearly; }       // the early generic kernel reads its list here
 		}
+		for ( uint32_t slot = 0; slot < TIER_NSLOTS; ++slot ) c->ntier[slot] = ndone[TIER_MAIN[slot]];
+		c->ntier0 = ndone[ID_T0]; c->ntier7 = ndone[ID_T7]; c->ntier10 = ndone[ID_DENSE];
 		// the library's launch on the second stream (k_window_long): tier 5 (strings of up to 128 bases) first, the generic
 		// engine for what it cannot hold
-		FastBatch FBL; FBL.W = WB; FBL.W.pregen = 0; FBL.F = BP.ftierL; FBL.dpsq_vst = c->H.dpsq_vst.data(); FBL.retry = 0; FBL.gearly = 0; FBL.gslab = 0; FBL.gstride = 0; FBL.tab32 = c->H.tab32.data(); FBL.hand = 0; FBL.handctr = 0; FBL.handcap = 0; FBL.handwords = 0;
-#if defined(DACC_LEDGER)
-		FBL.ledger = 0;
-#endif
-		std::vector<uint8_t> ldsL(BP.ftierL.ldsbytes+64,arenafill);
-		bool const longok = usefast && static_cast<uint64_t>(c->H.nrows+1)*(c->H.nsup+1) <= BP.ftierL.tabcap;
-		auto loadTablesL = [&]() { wave_run([&]() { FastLds< FastTier<5> > L; L.base = ldsL.data(); fast_load_tables(L,BP.ftierL.nrows,BP.ftierL.nsup,T,c->H.dpsq_vst.data()); }); };
-		if ( longok ) loadTablesL();
 		c->nlong = 0;
 		earlysnap.insert(earlysnap.begin(),pregenlist.begin(),pregenlist.end());      // launch order: pre-scan list, then the first tier's list
 		for ( size_t i = 0; i < earlysnap.size(); ++i )
 		{
-			int rc = FW_NEXT;
-			if ( longok )
-			{
-				if ( getenv("DACC_EMUL_POISON") ) { std::memset(ldsL.data(),atoi(getenv("DACC_EMUL_POISON")),ldsL.size()); loadTablesL(); }
-				wave_run([&]() { int const r = processWindowFast< FastTier<5> >(FBL,earlysnap[i],ldsL.data(),false); if ( wv_lane() == 0 ) rc = r; });
-			}
+			int const rc = TP.ok[ID_LONG] ? runWindow(ID_LONG,earlysnap[i],false) : static_cast<int>(FW_NEXT);
 			if ( rc == FW_DONE ) { ++c->nlong; continue; }
 			++c->nretry; c->glist.push_back(earlysnap[i]); c->glist.push_back(wout[earlysnap[i]].flags); GENERIC_WINDOW(earlysnap[i]) checkGuards(earlysnap[i]);
 		}
 		{
-			uint64_t const n = haveList ? cur.size() : BP.nwindows;
+			uint64_t const n = list ? list->size() : BP.nwindows;
 			for ( uint64_t i = 0; i < n; ++i )
 			{
-				uint64_t const wdx = haveList ? cur[i] : i;
+				uint64_t const wdx = list ? (*list)[i] : i;
 				++c->nretry; c->glist.push_back(wdx); c->glist.push_back(wout[wdx].flags); GENERIC_WINDOW(wdx) checkGuards(wdx);
 			}
 		}
