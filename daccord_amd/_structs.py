@@ -36,7 +36,12 @@ class DaccTiming(C.Structure):
                 ("algo_bytes", C.c_uint64), ("tier_ms", C.c_float * 3), ("tier_out", C.c_uint32 * 3),
                 ("first_tier", C.c_uint32), ("long_windows", C.c_uint32), ("tier0_ms", C.c_float), ("tier0_in", C.c_uint32),
                 ("tier0_out", C.c_uint32), ("tier7_ms", C.c_float), ("tier7_in", C.c_uint32), ("tier7_out", C.c_uint32), ("pad_", C.c_uint32),
-                ("long_first_tier", C.c_uint32), ("tier10_ms", C.c_float), ("tier10_out", C.c_uint32), ("tier10_ran", C.c_uint32), ("pad2_", C.c_uint32)]
+                ("long_first_tier", C.c_uint32), ("tier10_ms", C.c_float), ("tier10_out", C.c_uint32), ("tier10_ran", C.c_uint32), ("pad2_", C.c_uint32),
+                # (everything above: DACC_TIMING_SIZE_V1 bytes, what dacc_last_timing fills; the deep-window tier: dacc_last_timing2)
+                ("deep_ms", C.c_float), ("deep_windows", C.c_uint32), ("deep_out", C.c_uint32), ("pad3_", C.c_uint32)]
+
+
+TIMING_SIZE_V1 = 128
 
 
 class DaccWindowResult(C.Structure):

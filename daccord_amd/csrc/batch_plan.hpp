@@ -64,8 +64,9 @@ struct BatchPlan
 	FastCaps ftier[TIER_NSLOTS];   // main tier of every slot
 	FastCaps ftier0, ftier7;  // front tiers of the first slot (size classes of shallow batches)
 	FastCaps ftierD;          // front tier of the last slot (dense graphs: tier 10, deep batches 11)
+	FastCaps ftierX;          // second front tier of the last slot (deep windows, 97 ... 250 strings: tier 12)
 	FastCaps ftierL;          // tier 5: windows with a string of 65..128 bases (second stream, before the generic engine)
-	FastCaps & stageCaps(uint32_t const id) { FastCaps * const F[TIER_NSTAGES] = { &ftier0,&ftier7,&ftier[0],&ftier[1],&ftierD,&ftier[2],&ftierL }; return *F[id]; }
+	FastCaps & stageCaps(uint32_t const id) { FastCaps * const F[TIER_NSTAGES] = { &ftier0,&ftier7,&ftier[0],&ftier[1],&ftierD,&ftierX,&ftier[2],&ftierL }; return *F[id]; }
 	uint64_t ndeepwin;        // windows with more strings / k-mer instances than the first tier of shallow batches holds
 	bool deep;                // most windows are deep: the chain of deep batches (many strings, small graph in the first slot)
 	bool wide;                // window size 64 ... 127: the chain of wide batches (round 6)

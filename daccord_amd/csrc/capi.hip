@@ -152,6 +152,17 @@ __global__ void k_check_done(WindowOut const * wout, uint64_t n, uint32_t * errf
 	}
 }
 
+// dacc_timing's counters of the deep-window tier: the windows with more than `mins` strings on the list the tier read (out[0]) and on the
+// list it handed on (out[1]); the tier passes every other window of its list on untouched.  Reads the final window records.
+__global__ void k_count_deeper(uint32_t const * in, uint32_t const * handon, WindowOut const * wout, uint32_t const mins, uint32_t * out)
+{
+	uint32_t const nin = in[0], nout = handon[0];
+	uint32_t a = 0, b = 0;
+	for ( uint32_t i = blockIdx.x*blockDim.x + threadIdx.x; i < nin; i += gridDim.x*blockDim.x ) a += static_cast<uint32_t>(wout[in[1+i]].mao) > mins;
+	for ( uint32_t i = blockIdx.x*blockDim.x + threadIdx.x; i < nout; i += gridDim.x*blockDim.x ) b += static_cast<uint32_t>(wout[handon[1+i]].mao) > mins;
+	if ( a ) atomicAdd(out,a);
+	if ( b ) atomicAdd(out+1,b);
+}
 // windows the generic engine left as WS_OVERFLOW -> list (count in list[0])
 __global__ void k_collect_overflow(WindowOut const * wout, uint64_t n, uint32_t * list)
 {
@@ -385,7 +396,7 @@ struct dacc_ctx
 	// the LDS tiers (tier_pipeline.hpp): their switches, the resolved chain of the current batch (capacities: BP.stageCaps), by TierId and the launch state of its stages.
 	// A main tier hands on through d_retry[slot] and is done at evslot[slot]; `handon` and `done` are those of the front tiers.
 	TierSwitches sw; TierPipeline TP;
-	struct Stage { bool ran; uint32_t grid; DevBuf<uint32_t> handon; hipEvent_t done; } st[TIER_NSTAGES];
+	struct Stage { bool ran; uint32_t grid; DevBuf<uint32_t> handon; hipEvent_t done; uint32_t const * in; /* the list it read in the last pass */ } st[TIER_NSTAGES];
 	uint32_t nlong[2];      // windows on the two lists of the second stream in the current pass (pre-scan, first tier's generic-only windows)
 	uint32_t retry_grid, early_grid; int sched;
 	uint32_t tr_grid, tr_lds, tr_words, tr_lanes, trace_bytes, win_grid;
@@ -461,7 +472,7 @@ int dacc_create(dacc_ctx ** out, dacc_params const * p)
 	hipEventCreateWithFlags(&c->evFirstTier,hipEventDisableTiming); hipEventCreateWithFlags(&c->evEarlyGeneric,hipEventDisableTiming); hipEventCreateWithFlags(&c->evPrescan,hipEventDisableTiming);
 	for ( int i = 0; i < 6; ++i ) hipEventCreate(&c->ev[i]);
 	for ( int i = 0; i < TIER_NSLOTS; ++i ) hipEventCreate(&c->evslot[i]);
-	for ( int i = 0; i < TIER_NSTAGES; ++i ) { hipEventCreate(&c->st[i].done); c->st[i].ran = false; c->st[i].grid = 0; }
+	for ( int i = 0; i < TIER_NSTAGES; ++i ) { hipEventCreate(&c->st[i].done); c->st[i].ran = false; c->st[i].grid = 0; c->st[i].in = 0; }
 	*out = c;
 	return DACC_OK;
 }
@@ -696,7 +707,7 @@ static int runDevice(dacc_ctx * c)
 						dacc_ctx::Stage & S = c->st[fr[k]];
 						FastBatch FF = FB; FF.F = BP.stageCaps(fr[k]); FF.retry = S.handon.p; FF.gstride = FF.F.gbytes;
 						hipLaunchKernelGGL(fastKernel(TP.tier[fr[k]]),dim3(S.grid),dim3(64),FF.F.ldsbytes,s,FF,in,work(TIER_CHAIN[fr[k]].work));
-						HIPCHK(hipEventRecord(S.done,s)); S.ran = true;
+						HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = in;
 						in = S.handon.p;
 					}
 					hipLaunchKernelGGL(fastKernel(TP.tier[m]),dim3(c->st[m].grid),dim3(64),FB.F.ldsbytes,s,FB,in,work(TIER_CHAIN[m].work));
@@ -767,7 +778,7 @@ static int runDevice(dacc_ctx * c)
 	{ int const rc = voteAndFetch(); if ( rc ) return rc; }
 	// dacc_timing's names for the front tiers: tier 0 and tier 7 are the first slot's (size classes), tier 10 the last slot's (dense graphs; tier 11 in deep batches)
 	auto const ranOf = [&](TierId const id) { return c->st[id].ran ? &c->st[id] : static_cast<dacc_ctx::Stage *>(0); };
-	dacc_ctx::Stage * const f0 = ranOf(ID_T0), * const f7 = ranOf(ID_T7), * const fD = ranOf(ID_DENSE);
+	dacc_ctx::Stage * const f0 = ranOf(ID_T0), * const f7 = ranOf(ID_T7), * const fD = ranOf(ID_DENSE), * const fX = ranOf(ID_DEEP);
 	for ( int i = 0; i < 3; ++i ) c->timing.tier_out[i] = 0;
 	if ( TP.usefast && BP.nwindows ) for ( int i = 0; i < 3; ++i ) if ( TP.slotok(i) ) HIPCHK(hipMemcpy(&c->timing.tier_out[i],c->d_retry[i].p,sizeof(uint32_t),hipMemcpyDeviceToHost));
 	c->timing.tier10_out = 0;
@@ -827,6 +838,18 @@ static int runDevice(dacc_ctx * c)
 		mark("k_window (scratch retry)");
 		int const rc = voteAndFetch(); if ( rc ) return rc;
 	}
+	// the deep-window tier passes the windows of at most FastTier<12>::mins strings on untouched: its own share are the windows with more strings
+	// on the list it read (deep_windows + deep_out) and on the list it handed on (deep_out), counted from the final window records (behind the scratch retries of the generic engine)
+	c->timing.deep_windows = 0; c->timing.deep_out = 0; c->timing.pad3_ = 0;
+	if ( fX && fX->in )
+	{
+		HIPCHK(hipMemsetAsync(c->d_work.p+WORK_DEEP_COUNT,0,2*sizeof(uint32_t),s));
+		hipLaunchKernelGGL(k_count_deeper,dim3(64),dim3(256),0,s,fX->in,static_cast<uint32_t const *>(fX->handon.p),c->d_wout.p,static_cast<uint32_t>(FastTier<12>::mins),c->d_work.p+WORK_DEEP_COUNT);
+		uint32_t cnt[2] = {0,0};
+		HIPCHK(hipMemcpyAsync(cnt,c->d_work.p+WORK_DEEP_COUNT,sizeof(cnt),hipMemcpyDeviceToHost,s));
+		HIPCHK(hipStreamSynchronize(s));
+		c->timing.deep_out = cnt[1]; c->timing.deep_windows = cnt[0] > cnt[1] ? cnt[0] - cnt[1] : 0u;
+	}
 	c->pile_status = BP.pile_status; c->pile_errors = BP.pile_errors;
 	if ( herr[0] && BP.piles.size() )
 	{
@@ -865,6 +888,8 @@ static int runDevice(dacc_ctx * c)
 	if ( f0 ) { hipEventElapsedTime(&ms,c->ev[1],f0->done); c->timing.tier0_ms = ms; }
 	if ( f7 ) { hipEventElapsedTime(&ms,f0->done,f7->done); c->timing.tier7_ms = ms; }
 	if ( fD ) { hipEventElapsedTime(&ms,c->evslot[1],fD->done); c->timing.tier10_ms = ms; }
+	c->timing.deep_ms = 0;
+	if ( fX ) { hipEventElapsedTime(&ms,fD ? fD->done : c->evslot[1],fX->done); c->timing.deep_ms = ms; }
 	hipEventElapsedTime(&ms,c->ev[2],c->ev[3]); c->timing.vote_ms = ms;
 	hipEventElapsedTime(&ms,c->ev[3],c->ev[4]); c->timing.d2h_ms = ms;
 	hipEventElapsedTime(&ms,c->ev[0],c->ev[3]); c->timing.total_ms = ms;
@@ -1032,10 +1057,19 @@ int dacc_collect(dacc_ctx * c, dacc_fragment const ** frags, uint64_t * nfrags, 
 
 void dacc_release(dacc_ctx * c) { if ( c ) { c->frags.clear(); c->bases.clear(); } }
 
+// dacc_last_timing: the record as it was when the call got its signature (everything in front of deep_ms), so that a caller compiled against
+// that header is not overrun; dacc_last_timing2 copies as much of today's record as the caller says it has room for
+static_assert(offsetof(dacc_timing,deep_ms) == DACC_TIMING_SIZE_V1,"dacc_last_timing fills the record in front of deep_ms");
 int dacc_last_timing(dacc_ctx * c, dacc_timing * t)
 {
 	if ( !c || !t ) return DACC_EINVAL;
-	*t = c->timing;
+	std::memcpy(static_cast<void *>(t),&c->timing,DACC_TIMING_SIZE_V1);
+	return DACC_OK;
+}
+int dacc_last_timing2(dacc_ctx * c, dacc_timing * t, size_t size)
+{
+	if ( !c || !t ) return DACC_EINVAL;
+	std::memcpy(static_cast<void *>(t),&c->timing,size < sizeof(dacc_timing) ? size : sizeof(dacc_timing));
 	return DACC_OK;
 }
 

@@ -549,6 +549,7 @@ int main(int argc, char ** argv)
 	});
 	std::string fatal; bool stopall = false;           // both under mu
 	double gpu_s = 0; uint64_t nbatches = 0;            // under mu
+	struct { uint64_t nwindows, tier_out[3], deep_windows, deep_out; double window_ms, tier_ms[3], deep_ms; } tstat = {};      // under mu: dacc_timing summed over the batches (-V)
 	// every batch (also an empty one, the end marker and a failed one) hands the writer an Out with its sequence number: the
 	// writer needs an unbroken sequence.  An output slot is always available within bounded time: at most one Out per worker is
 	// in flight besides those queued for the writer, and there are 2*nwork+1 slots.
@@ -587,7 +588,14 @@ int main(int argc, char ** argv)
 					{
 						O->fr.assign(fr,fr+nf); O->bases.assign(bases,nb);
 						dacc_release(ctx);
+						dacc_timing tm; std::memset(&tm,0,sizeof(tm));
+						bool const havetm = dacc_last_timing2(ctx,&tm,sizeof(tm)) == DACC_OK;
 						std::lock_guard<std::mutex> lk(mu); gpu_s += dt; ++nbatches; totalbases += nb;
+						if ( havetm )
+						{
+							tstat.nwindows += tm.nwindows; tstat.window_ms += tm.window_ms; tstat.deep_ms += tm.deep_ms; tstat.deep_windows += tm.deep_windows; tstat.deep_out += tm.deep_out;
+							for ( int i = 0; i < 3; ++i ) { tstat.tier_out[i] += tm.tier_out[i]; tstat.tier_ms[i] += tm.tier_ms[i]; }
+						}
 					}
 				}
 			}
@@ -618,6 +626,12 @@ int main(int argc, char ** argv)
 		std::fprintf(stderr,"[V] %llu corrected bases in %.2f s end to end (load + select + plan + GPU + FASTA) = %.3f Mbase/s; %llu batches, %.2f s in dacc_submit_piles%s\n",
 			static_cast<unsigned long long>(totalbases),el,el > 0 ? totalbases/el/1e6 : 0.0,static_cast<unsigned long long>(nbatches),gpu_s,
 			nwork > 1 ? (" (summed over " + std::to_string(nwork) + " device workers)").c_str() : "");
+		// the window stage by tier slot (dacc_timing): what every slot handed on (the last one to the generic engine) and the deep-window tier's share
+		std::fprintf(stderr,"[V] %llu windows, window kernels %.1f ms: tier slots %.1f / %.1f / %.1f ms handed on %llu / %llu / %llu windows (the last to the generic engine); "
+			"deep-window tier (97 ... 250 strings) %.1f ms, %llu windows finished, %llu handed on\n",
+			static_cast<unsigned long long>(tstat.nwindows),tstat.window_ms,tstat.tier_ms[0],tstat.tier_ms[1],tstat.tier_ms[2],
+			static_cast<unsigned long long>(tstat.tier_out[0]),static_cast<unsigned long long>(tstat.tier_out[1]),static_cast<unsigned long long>(tstat.tier_out[2]),
+			tstat.deep_ms,static_cast<unsigned long long>(tstat.deep_windows),static_cast<unsigned long long>(tstat.deep_out));
 	}
 	for ( int g = 0; g < nwork; ++g ) dacc_destroy(ctxs[g]);
 	dacc_las_close(las); dacc_db_close(A.h); if ( twodb ) dacc_db_close(B2.h);

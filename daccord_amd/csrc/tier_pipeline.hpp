@@ -4,17 +4,17 @@
  *
  * Every window runs through a chain of tiers (FastTier<N>, fast_window.hpp); which tiers, in which order, depends on the batch:
  *
- *   shallow batches   slot 0: 0 -> 7 -> 1     slot 1: 6     slot 2: 10 -> 3
- *   deep batches      slot 0: 4               slot 1: 2     slot 2: 11 -> 3
+ *   shallow batches   slot 0: 0 -> 7 -> 1     slot 1: 6     slot 2: 10 -> 12 -> 3
+ *   deep batches      slot 0: 4               slot 1: 2     slot 2: 11 -> 12 -> 3
  *   wide batches                              slot 1: 8     slot 2: 9
- *   every batch       tier 5 on the second stream (k_window_long), in front of the generic engine there
+ *   shallow and deep  tier 5 on the second stream (k_window_long), in front of the generic engine there
  *
  * (TIER_CHAIN below: one row per stage, one column per batch shape.)
  *
  * A slot is one entry of dacc_timing.tier_ms[3] / tier_out[3].  Its MAIN tier takes what the slot in front handed on (slot 0: all
  * windows) and hands on to the next slot, the last one to the generic engine.  FRONT tiers run before the main tier of their slot
  * with more wavefronts per CU: each hands on to the next stage of its slot.  Tiers 0 and 7 are fed by the size-class pre-pass
- * (k_classify), tiers 10 / 11 by the list of the slot in front.
+ * (k_classify), tiers 10 / 11 by the list of the slot in front, tier 12 (windows of 97 ... 250 strings; it passes the others on) by what they hand on.
  */
 #ifndef DACC_TIER_PIPELINE_HPP
 #define DACC_TIER_PIPELINE_HPP
@@ -38,7 +38,7 @@ enum : uint32_t { T0INST_DEFAULT = 576, T7INST_DEFAULT = 704 };      // a window
                                                // arguments of the pre-pass (DACC_T0INST / DACC_T7INST override them for sweeps)
 
 // The tiers.  KERNEL: those with a kernel of their own (k_window_fast<N>, window_kernels.hpp); tier 5 runs inside k_window_long.
-#define DACC_KERNEL_TIERS(X) X(0) X(1) X(2) X(3) X(4) X(6) X(7) X(8) X(9) X(10) X(11)
+#define DACC_KERNEL_TIERS(X) X(0) X(1) X(2) X(3) X(4) X(6) X(7) X(8) X(9) X(10) X(11) X(12)
 #define DACC_ALL_TIERS(X) DACC_KERNEL_TIERS(X) X(5)
 
 // From a run-time tier number to its compile-time capacities: f is called with a TierTag<N>, whose `type` is FastTier<N>
@@ -62,16 +62,19 @@ enum : uint32_t
 	GATE_T7_ABOVE_T0 = 4, // only with DACC_T7INST > DACC_T0INST (else the middle size class is empty)
 	GATE_DENSE = 8,       // DACC_DENSE_TIER=0 switches it off
 	GATE_PREV_SLOT = 16,  // needs the main tier of the slot in front as well (the dense tiers need slots 1 and 2)
+	GATE_DEEP = 128,      // DACC_DEEP_TIER=0 switches it off (windows of more than 96 strings run in the generic engine, as before the deep-window tier)
 	STAGE_PREPASS = 32,   // (no gate) fed by the size-class pre-pass instead of the list in front of it
 	STAGE_ADAPTIVE = 64   // (no gate) switches itself off for the rest of a context when it hands on too much (DACC_T7_ADAPT)
 };
 // counters of d_work (32 bit words): eight per-XCD work counters for every kernel that pulls its windows (window_kernels.hpp: next_window)
 enum : uint32_t { WORK_SLOT0 = 0, WORK_SLOT1 = 8, WORK_SLOT2 = 16, WORK_DENSE = 24, WORK_GENERIC = 32, WORK_T0 = 40, WORK_T7 = 48,
 	WORK_PRE_MID = 56, WORK_PRE_BIG = 57,      // what the pre-pass itself put on the middle and the big list (for dacc_timing)
-	WORK_TRACE = 60, WORK_WORDS = 64 };
+	WORK_TRACE = 60, WORK_DEEP = 64,
+	WORK_DEEP_COUNT = 72,      // two words: windows of more than FastTier<12>::mins strings the deep-window tier read / handed on (for dacc_timing)
+	WORK_WORDS = 80 };
 
 // The stages, in the order they run; their place in this table is their place in BatchPlan::stageCaps, TierPipeline and dacc_ctx::st.
-enum TierId { ID_T0, ID_T7, ID_SLOT0, ID_SLOT1, ID_DENSE, ID_SLOT2, ID_LONG, TIER_NSTAGES };
+enum TierId { ID_T0, ID_T7, ID_SLOT0, ID_SLOT1, ID_DENSE, ID_DEEP, ID_SLOT2, ID_LONG, TIER_NSTAGES };
 enum { TIER_NSLOTS = 3, TIER_NONE = 255, TIER_SHALLOW_FIRST = 1 };      // (the first slot's main tier of shallow batches: a batch whose windows mostly overflow its strings / instances is deep)
 struct TierStage { uint8_t tier[3] /* in a shallow, deep, wide batch */, slot, role; int8_t tiersbit /* bit of DACC_TIERS */; uint32_t flags, work; };
 static TierStage const TIER_CHAIN[TIER_NSTAGES] = {
@@ -80,8 +83,10 @@ static TierStage const TIER_CHAIN[TIER_NSTAGES] = {
 	{ { 1, 4, TIER_NONE }, 0, ROLE_MAIN, 0, GATE_TABFIT, WORK_SLOT0 },
 	{ { 6, 2, 8 }, 1, ROLE_MAIN, 1, GATE_TABFIT, WORK_SLOT1 },
 	{ { 10, 11, TIER_NONE }, 2, ROLE_FRONT, -1, GATE_TABFIT|GATE_DENSE|GATE_PREV_SLOT, WORK_DENSE },
+	{ { 12, 12, TIER_NONE }, 2, ROLE_FRONT, -1, GATE_TABFIT|GATE_DEEP|GATE_PREV_SLOT, WORK_DEEP },
 	{ { 3, 3, 9 }, 2, ROLE_MAIN, 2, GATE_TABFIT, WORK_SLOT2 },
-	{ { 5, 5, 5 }, 0, ROLE_LONG, 2, GATE_TABFIT, 0 } };
+	// (tier 5 holds no wide window: a wide batch's second stream is the generic engine alone, at its own occupancy instead of a CU's LDS per wavefront)
+	{ { 5, 5, TIER_NONE }, 0, ROLE_LONG, 2, GATE_TABFIT, 0 } };
 static TierId const TIER_MAIN[TIER_NSLOTS] = { ID_SLOT0, ID_SLOT1, ID_SLOT2 };
 // does the stage run in a batch of this shape, and the tier whose capacities the plan holds for it (a stage that does not run keeps
 // those of the nearest shape: the first slot of a wide batch has tier 1's or tier 4's)
@@ -98,6 +103,7 @@ struct TierSwitches
 	uint32_t tiers;           // DACC_TIERS: bit t enables the main tier of slot t (bit 2: tier 5 as well), bit 3 tier 0 (size classes), bit 4 tier 7 (the middle class)
 	bool widetier;            // DACC_WIDE_TIER=0: wide batches run in the generic engine only, as in rounds 4-5
 	bool dense;               // DACC_DENSE_TIER=0: the second slot hands on to tier 3 directly (before round 6's dense tiers)
+	bool deepwin;             // DACC_DEEP_TIER=0: no deep-window tier (tier 12) in front of tier 3
 	bool long128;             // DACC_LONG128=0: windows with a string of 65 ... 128 bases run in tier 5 on the second stream (rounds 3-5)
 	bool hand;                // DACC_HAND=0: no hand-over buffer, every hand-over restarts from the strings
 	uint32_t t0inst, t7inst;  // DACC_T0INST / DACC_T7INST: size-class thresholds (k-mer instances) of tiers 0 and 7
@@ -110,7 +116,7 @@ static inline TierSwitches readTierSwitches()
 	TierSwitches S;
 	{ char const * const e = getenv("DACC_NOFAST"); S.nofast = e && e[0] == '1'; }
 	S.tiers = num("DACC_TIERS",31);
-	S.widetier = !off("DACC_WIDE_TIER"); S.dense = !off("DACC_DENSE_TIER"); S.long128 = !off("DACC_LONG128"); S.hand = !off("DACC_HAND");
+	S.widetier = !off("DACC_WIDE_TIER"); S.dense = !off("DACC_DENSE_TIER"); S.deepwin = !off("DACC_DEEP_TIER"); S.long128 = !off("DACC_LONG128"); S.hand = !off("DACC_HAND");
 	S.t0inst = num("DACC_T0INST",T0INST_DEFAULT); S.t7inst = num("DACC_T7INST",T7INST_DEFAULT);
 	S.lds_t1 = num("DACC_LDS_T1",0); S.lds_t0 = num("DACC_LDS_T0",0);
 	return S;
@@ -155,7 +161,7 @@ static inline TierPipeline resolveTiers(TierSwitches const & S, bool const fastp
 		TierStage const & st = TIER_CHAIN[i]; FastCaps const & F = capsOf(i);
 		return R.usefast && stageRuns(st,deep,wide) && F.ldsbytes <= TIER_LDS_CU && (st.tiersbit < 0 || ((S.tiers >> st.tiersbit) & 1))
 			&& (!(st.flags & GATE_TABFIT) || static_cast<uint64_t>(nrows+1)*(nsup+1) <= F.tabcap)
-			&& (!(st.flags & GATE_T7_ABOVE_T0) || S.t7inst > S.t0inst) && (!(st.flags & GATE_DENSE) || S.dense);
+			&& (!(st.flags & GATE_T7_ABOVE_T0) || S.t7inst > S.t0inst) && (!(st.flags & GATE_DENSE) || S.dense) && (!(st.flags & GATE_DEEP) || S.deepwin);
 	};
 	{ FastCaps & F = capsOf(ID_SLOT0); if ( S.lds_t1 > F.ldsbytes && S.lds_t1 <= TIER_LDS_CU ) F.ldsbytes = S.lds_t1; }
 	{ FastCaps & F = capsOf(ID_T0); if ( S.lds_t0 > F.ldsbytes && S.lds_t0 <= TIER_LDS_CU ) F.ldsbytes = S.lds_t0; }

@@ -49,6 +49,8 @@ def lib():
         L.dacc_last_error.restype = C.c_char_p
         L.dacc_pile_select.argtypes = [vp, C.c_uint64, C.c_int, C.c_uint64, vp, vp]
         L.dacc_last_timing.argtypes = [vp, C.POINTER(DaccTiming)]
+        if hasattr(L, "dacc_last_timing2"):            # (variant libraries of earlier rounds, DACC_LIB, lack it)
+            L.dacc_last_timing2.argtypes = [vp, C.POINTER(DaccTiming), C.c_size_t]
         L.dacc_rerun_resident.argtypes = [vp]
         L.dacc_debug_windows.argtypes = [vp, vp, C.c_uint64, vp]
         L.dacc_debug_tables.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
@@ -143,8 +145,13 @@ class Engine:
         self._chk(self.L.dacc_rerun_resident(self.h))
 
     def timing(self):
+        """The timing record of the last run; the fields behind the first TIMING_SIZE_V1 bytes (deep_ms, deep_windows, deep_out) stay zero
+        with a library that has no dacc_last_timing2."""
         t = DaccTiming()
-        self._chk(self.L.dacc_last_timing(self.h, C.byref(t)))
+        if hasattr(self.L, "dacc_last_timing2"):
+            self._chk(self.L.dacc_last_timing2(self.h, C.byref(t), C.sizeof(DaccTiming)))
+        else:
+            self._chk(self.L.dacc_last_timing(self.h, C.byref(t)))
         return t
 
     def debug_windows(self):

@@ -26,6 +26,7 @@
 #define DACCORD_HIP_H
 
 #include <stdint.h>
+#include <stddef.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -190,8 +191,18 @@ typedef struct dacc_timing {
 	uint32_t tier10_out;     /* windows tier 10 handed on to tier 3 (it ran tier_out[1] windows) */
 	uint32_t tier10_ran;     /* 1: tier 10 ran in this pass (tier_out[1] went to it, not to tier 3) */
 	uint32_t pad2_;
+	/* ---- everything above: DACC_TIMING_SIZE_V1 bytes, what dacc_last_timing fills ---- */
+	float deep_ms;           /* the deep-window tier: k_window_fast<12> (1 wavefront per CU; windows of 97 ... 250 strings) in front of k_window_fast<3>, a part of tier_ms[2]; 0 if it did not run */
+	uint32_t deep_windows;   /* windows of more than 96 strings that finished in tier 12 */
+	uint32_t deep_out;       /* windows of more than 96 strings tier 12 handed on (more than 250 strings, a k-mer seen more than 255 times, a graph or pool beyond its capacities): they end in the generic engine */
+	uint32_t pad3_;
 } dacc_timing;
+#define DACC_TIMING_SIZE_V1 128
+/* dacc_last_timing fills the first DACC_TIMING_SIZE_V1 bytes only (the record as it was when the call was introduced: a caller built against
+ * an older header is never overrun).  dacc_last_timing2 copies min(size, sizeof(dacc_timing)) bytes: pass sizeof(dacc_timing) of the header
+ * the caller was compiled with; fields the library does not know stay as the caller set them. */
 int  dacc_last_timing(dacc_ctx *ctx, dacc_timing *t);
+int  dacc_last_timing2(dacc_ctx *ctx, dacc_timing *t, size_t size);
 
 /* Per-pile outcome of the last dacc_submit_piles, in submission order: DACC_OK, or the reason the pile was dropped
  * (DACC_EINVAL: malformed overlap / trace records; DACC_ENOTSUP: a window beyond every engine's capacity).  A dropped
