@@ -38,7 +38,9 @@ class DaccTiming(C.Structure):
                 ("tier0_out", C.c_uint32), ("tier7_ms", C.c_float), ("tier7_in", C.c_uint32), ("tier7_out", C.c_uint32), ("pad_", C.c_uint32),
                 ("long_first_tier", C.c_uint32), ("tier10_ms", C.c_float), ("tier10_out", C.c_uint32), ("tier10_ran", C.c_uint32), ("pad2_", C.c_uint32),
                 # (everything above: DACC_TIMING_SIZE_V1 bytes, what dacc_last_timing fills; the deep-window tier: dacc_last_timing2)
-                ("deep_ms", C.c_float), ("deep_windows", C.c_uint32), ("deep_out", C.c_uint32), ("pad3_", C.c_uint32)]
+                ("deep_ms", C.c_float), ("deep_windows", C.c_uint32), ("deep_out", C.c_uint32), ("pad3_", C.c_uint32),
+                # the last stage (tier 13 / 14, layout in device memory, in front of k_window)
+                ("last_ms", C.c_float), ("last_windows", C.c_uint32), ("last_out", C.c_uint32), ("pad4_", C.c_uint32)]
 
 
 TIMING_SIZE_V1 = 128

@@ -66,7 +66,8 @@ struct BatchPlan
 	FastCaps ftierD;          // front tier of the last slot (dense graphs: tier 10, deep batches 11)
 	FastCaps ftierX;          // second front tier of the last slot (deep windows, 97 ... 250 strings: tier 12)
 	FastCaps ftierL;          // tier 5: windows with a string of 65..128 bases (second stream, before the generic engine)
-	FastCaps & stageCaps(uint32_t const id) { FastCaps * const F[TIER_NSTAGES] = { &ftier0,&ftier7,&ftier[0],&ftier[1],&ftierD,&ftierX,&ftier[2],&ftierL }; return *F[id]; }
+	FastCaps ftierZ;          // the last stage, behind the slots and in front of the generic engine (layout in device memory: tier 13, wide batches 14)
+	FastCaps & stageCaps(uint32_t const id) { FastCaps * const F[TIER_NSTAGES] = { &ftier0,&ftier7,&ftier[0],&ftier[1],&ftierD,&ftierX,&ftier[2],&ftierZ,&ftierL }; return *F[id]; }
 	uint64_t ndeepwin;        // windows with more strings / k-mer instances than the first tier of shallow batches holds
 	bool deep;                // most windows are deep: the chain of deep batches (many strings, small graph in the first slot)
 	bool wide;                // window size 64 ... 127: the chain of wide batches (round 6)

@@ -392,7 +392,7 @@ struct dacc_ctx
 	DevBuf<uint8_t> d_wrec; DevBuf<WindowOut> d_wout; DevBuf<uint8_t> d_arena;
 	DevBuf<uint8_t> d_has, d_oc, d_outsym, d_pilebad; DevBuf<uint16_t> d_ld0; DevBuf<uint32_t> d_ocs, d_nfrag, d_err;
 	DevBuf<VoteFragment> d_frags; DevBuf<uint64_t> d_fragbase; DevBuf<uint64_t> d_prof;
-	DevBuf<uint64_t> d_vst; DevBuf<uint32_t> d_tab32; DevBuf<uint8_t> d_gslab; DevBuf<uint32_t> d_retry[TIER_NSLOTS], d_work, d_gearly, d_pregen, d_pregen2, d_pregenlist; DevBuf<uint8_t> d_arena2; DevBuf<uint64_t> d_trslab; DevBuf<uint32_t> d_small; DevBuf<uint64_t> d_hand; DevBuf<uint32_t> d_handctr; uint32_t handcap; uint64_t handwant, nruns; bool nohand, oom; bool tier7_adapt_off; int env_t7adapt; int env_trdyn;
+	DevBuf<uint64_t> d_vst; DevBuf<uint32_t> d_tab32; DevBuf<uint8_t> d_gslab, d_lastslab /* the last stage's own slab (layout included) */; DevBuf<uint32_t> d_retry[TIER_NSLOTS], d_work, d_gearly, d_pregen, d_pregen2, d_pregenlist; DevBuf<uint8_t> d_arena2; DevBuf<uint64_t> d_trslab; DevBuf<uint32_t> d_small; DevBuf<uint64_t> d_hand; DevBuf<uint32_t> d_handctr; uint32_t handcap; uint64_t handwant, nruns; bool nohand, oom; bool tier7_adapt_off; int env_t7adapt; int env_trdyn;
 	// the LDS tiers (tier_pipeline.hpp): their switches, the resolved chain of the current batch (capacities: BP.stageCaps), by TierId and the launch state of its stages.
 	// A main tier hands on through d_retry[slot] and is done at evslot[slot]; `handon` and `done` are those of the front tiers.
 	TierSwitches sw; TierPipeline TP;
@@ -461,7 +461,7 @@ int dacc_create(dacc_ctx ** out, dacc_params const * p)
 	c->retry_grid = c->early_grid = c->win_grid = 0; c->tier7_adapt_off = false; c->sched = 0;
 	c->tr_grid = c->tr_lds = c->tr_words = c->tr_lanes = c->trace_bytes = 0;
 	{
-		c->sw = readTierSwitches();      // DACC_NOFAST, DACC_TIERS, DACC_WIDE_TIER, DACC_DENSE_TIER, DACC_LONG128, DACC_HAND, DACC_T0INST, DACC_T7INST, DACC_LDS_T1, DACC_LDS_T0
+		c->sw = readTierSwitches();      // DACC_NOFAST, DACC_TIERS, DACC_WIDE_TIER, DACC_DENSE_TIER, DACC_DEEP_TIER, DACC_LAST_TIER, DACC_LAST_AS_SLOT2, DACC_LONG128, DACC_HAND, DACC_T0INST, DACC_T7INST, DACC_LDS_T1, DACC_LDS_T0
 		char const * sc = getenv("DACC_SCHED"); c->env_sched = sc ? atoi(sc) : 1;      // bit 0: LDS tiers pull work from a counter, bit 1: generic engine too
 		{ char const * td = getenv("DACC_TRACE_DYN"); c->env_trdyn = !(td && td[0] == '0'); }      // 0: k_trace walks its blocks with a fixed stride (rounds 1-5)
 		char const * ta = getenv("DACC_T7_ADAPT"); c->env_t7adapt = !(ta && ta[0] == '0');      // 0: tier 7 stays on whatever it hands on
@@ -486,7 +486,7 @@ void dacc_destroy(dacc_ctx * c)
 	c->d_bps.release(); c->d_boff.release(); c->d_rlen.release();
 	c->d_piles.release(); c->d_ovl.release(); c->d_ovl_pile.release(); c->d_trace.release(); c->d_blk_ovl.release(); c->d_blk_b0.release(); c->d_wt_b.release(); c->d_wt_e.release();
 	c->d_wrec.release(); c->d_wout.release(); c->d_arena.release();
-	c->h_outsym.release(); c->d_pilebad.release(); c->d_has.release(); c->d_oc.release(); c->d_outsym.release(); c->d_ld0.release(); c->d_ocs.release(); c->d_nfrag.release(); c->d_err.release(); c->d_frags.release(); c->d_fragbase.release(); c->d_prof.release(); c->d_vst.release(); c->d_tab32.release(); c->d_gslab.release(); for ( int i = 0; i < 3; ++i ) c->d_retry[i].release(); c->d_work.release(); c->d_gearly.release(); c->d_pregen.release(); c->d_pregen2.release(); c->d_pregenlist.release(); c->d_arena2.release(); c->d_trslab.release(); c->d_hand.release(); c->d_handctr.release();
+	c->h_outsym.release(); c->d_pilebad.release(); c->d_has.release(); c->d_oc.release(); c->d_outsym.release(); c->d_ld0.release(); c->d_ocs.release(); c->d_nfrag.release(); c->d_err.release(); c->d_frags.release(); c->d_fragbase.release(); c->d_prof.release(); c->d_vst.release(); c->d_tab32.release(); c->d_gslab.release(); c->d_lastslab.release(); for ( int i = 0; i < 3; ++i ) c->d_retry[i].release(); c->d_work.release(); c->d_gearly.release(); c->d_pregen.release(); c->d_pregen2.release(); c->d_pregenlist.release(); c->d_arena2.release(); c->d_trslab.release(); c->d_hand.release(); c->d_handctr.release();
 	for ( int i = 0; i < 6; ++i ) hipEventDestroy(c->ev[i]);
 	hipStreamDestroy(c->stream); hipStreamDestroy(c->stream2); hipEventDestroy(c->evFirstTier); hipEventDestroy(c->evEarlyGeneric); hipEventDestroy(c->evPrescan); for ( int i = 0; i < TIER_NSLOTS; ++i ) hipEventDestroy(c->evslot[i]);
 	c->d_small.release(); for ( int i = 0; i < TIER_NSTAGES; ++i ) { hipEventDestroy(c->st[i].done); c->st[i].handon.release(); }
@@ -662,7 +662,8 @@ static int runDevice(dacc_ctx * c)
 			HIPCHK(hipMemsetAsync(c->d_work.p,0,WORK_WORDS*sizeof(uint32_t),s));
 			// the chain (tier_pipeline.hpp): every slot takes the windows the previous one handed over (list = 0: all windows)
 			auto const work = [&](uint32_t const off) { return (c->sched&1) ? c->d_work.p+off : static_cast<uint32_t *>(0); };
-			uint32_t const * list = 0;
+			uint32_t const * list = 0; int lastslot = -1;
+			FastBatch FZ;      // the last stage's batch record: that of the last slot that ran, with its own capacities, list and slab
 			for ( uint32_t slot = 0; slot < TIER_NSLOTS; ++slot )
 			{
 				if ( TP.slotok(slot) )
@@ -706,12 +707,13 @@ static int runDevice(dacc_ctx * c)
 					{
 						dacc_ctx::Stage & S = c->st[fr[k]];
 						FastBatch FF = FB; FF.F = BP.stageCaps(fr[k]); FF.retry = S.handon.p; FF.gstride = FF.F.gbytes;
-						hipLaunchKernelGGL(fastKernel(TP.tier[fr[k]]),dim3(S.grid),dim3(64),FF.F.ldsbytes,s,FF,in,work(TIER_CHAIN[fr[k]].work));
+						hipLaunchKernelGGL(fastKernel(TP.tier[fr[k]]),dim3(S.grid),dim3(64),FF.F.gmem ? 0u : FF.F.ldsbytes,s,FF,in,work(TIER_CHAIN[fr[k]].work));
 						HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = in;
 						in = S.handon.p;
 					}
-					hipLaunchKernelGGL(fastKernel(TP.tier[m]),dim3(c->st[m].grid),dim3(64),FB.F.ldsbytes,s,FB,in,work(TIER_CHAIN[m].work));
-					list = c->d_retry[slot].p;
+					// (a device-memory tier in a slot, DACC_LAST_AS_SLOT2=1: no LDS)
+					hipLaunchKernelGGL(fastKernel(TP.tier[m]),dim3(c->st[m].grid),dim3(64),FB.F.gmem ? 0u : FB.F.ldsbytes,s,FB,in,work(TIER_CHAIN[m].work));
+					list = c->d_retry[slot].p; lastslot = static_cast<int>(slot);
 					if ( !early )
 					{
 						// the first tier has seen every window: what only the generic engine can run starts now, on its own
@@ -719,11 +721,26 @@ static int runDevice(dacc_ctx * c)
 						early = true;
 						HIPCHK(hipEventRecord(c->evFirstTier,s));
 					}
+					FZ = FB;
 				}
 				hipEventRecord(c->evslot[slot],s);
 			}
-			if ( c->env_dbgretry && list )
+			uint32_t const * const slotlist = list;      // what the last enabled slot handed on (dacc_debug_retry, tier_out)
+			if ( TP.ok[ID_LAST] && list && lastslot >= 0 )
 			{
+				// the last stage (tier 13, wide batches 14: layout in device memory) takes that list and hands on to the generic engine.  It skips the windows
+				// the second stream has, like every slot behind the first, and feeds no early list (the early kernel has read its list)
+				dacc_ctx::Stage & S = c->st[ID_LAST];
+				FZ.F = BP.stageCaps(ID_LAST); FZ.retry = S.handon.p; FZ.gearly = 0; FZ.gslab = c->d_lastslab.p; FZ.gstride = FZ.F.gbytes;
+				FZ.W.pregen = (TP.late_long || TP.widetier) ? c->d_pregen2.p : c->d_pregen.p;
+				HIPCHK(hipMemsetAsync(S.handon.p,0,sizeof(uint32_t),s));
+				hipLaunchKernelGGL(fastKernel(TP.tier[ID_LAST]),dim3(S.grid),dim3(64),0,s,FZ,list,work(TIER_CHAIN[ID_LAST].work));
+				HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = list;
+				list = S.handon.p;
+			}
+			if ( c->env_dbgretry && slotlist )
+			{
+				uint32_t const * const list = slotlist;
 				// debugging: which windows did the last LDS tier hand on, and why (flags of its FFAIL)
 				HIPCHK(hipStreamSynchronize(s));
 				uint32_t n = 0; HIPCHK(hipMemcpy(&n,list,sizeof(uint32_t),hipMemcpyDeviceToHost));
@@ -841,6 +858,14 @@ static int runDevice(dacc_ctx * c)
 	// the deep-window tier passes the windows of at most FastTier<12>::mins strings on untouched: its own share are the windows with more strings
 	// on the list it read (deep_windows + deep_out) and on the list it handed on (deep_out), counted from the final window records (behind the scratch retries of the generic engine)
 	c->timing.deep_windows = 0; c->timing.deep_out = 0; c->timing.pad3_ = 0;
+	// the last stage: what it read is what the last slot handed on, what it handed on is what k_window ran
+	c->timing.last_windows = 0; c->timing.last_out = 0; c->timing.pad4_ = 0;
+	if ( dacc_ctx::Stage const * const fZ = ranOf(ID_LAST) )
+	{
+		uint32_t nin = 0, nout = 0;
+		HIPCHK(hipMemcpy(&nin,fZ->in,sizeof(uint32_t),hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&nout,fZ->handon.p,sizeof(uint32_t),hipMemcpyDeviceToHost));
+		c->timing.last_out = nout; c->timing.last_windows = nin > nout ? nin - nout : 0u;
+	}
 	if ( fX && fX->in )
 	{
 		HIPCHK(hipMemsetAsync(c->d_work.p+WORK_DEEP_COUNT,0,2*sizeof(uint32_t),s));
@@ -888,7 +913,8 @@ static int runDevice(dacc_ctx * c)
 	if ( f0 ) { hipEventElapsedTime(&ms,c->ev[1],f0->done); c->timing.tier0_ms = ms; }
 	if ( f7 ) { hipEventElapsedTime(&ms,f0->done,f7->done); c->timing.tier7_ms = ms; }
 	if ( fD ) { hipEventElapsedTime(&ms,c->evslot[1],fD->done); c->timing.tier10_ms = ms; }
-	c->timing.deep_ms = 0;
+	c->timing.deep_ms = 0; c->timing.last_ms = 0;
+	if ( dacc_ctx::Stage const * const fZ = ranOf(ID_LAST) ) { hipEventElapsedTime(&ms,c->evslot[TIER_NSLOTS-1],fZ->done); c->timing.last_ms = ms; }
 	if ( fX ) { hipEventElapsedTime(&ms,fD ? fD->done : c->evslot[1],fX->done); c->timing.deep_ms = ms; }
 	hipEventElapsedTime(&ms,c->ev[2],c->ev[3]); c->timing.vote_ms = ms;
 	hipEventElapsedTime(&ms,c->ev[3],c->ev[4]); c->timing.d2h_ms = ms;
@@ -983,12 +1009,22 @@ static int dacc_submit_piles_body(dacc_ctx * c, dacc_pile const * piles, uint64_
 		for ( uint32_t i = 0; i < TIER_NSTAGES; ++i )
 		{
 			FastCaps const & F = BP.stageCaps(i);
-			c->st[i].grid = tierGrid(F.ldsbytes,BP.nwindows);
+			c->st[i].grid = F.gmem ? tierGridGmem(F.gbytes,BP.nwindows) : tierGrid(F.ldsbytes,BP.nwindows);
 			if ( !TP.ok[i] || TIER_CHAIN[i].role == ROLE_LONG ) continue;
+			if ( TIER_CHAIN[i].role == ROLE_LAST )
+			{
+				// the last stage: its own hand-on list (what k_window reads) and its own slab, grid x gbytes <= TIER_GMEM_SLAB.  Both are optional like the
+				// hand-over buffer: a device that cannot spare them runs the batch without the stage, on the route it had before
+				hipError_t e = c->st[i].handon.ensure(BP.nwindows+2);
+				if ( e == hipSuccess ) e = c->d_lastslab.ensure(static_cast<size_t>(c->st[i].grid)*F.gbytes + 256);
+				if ( e == hipErrorOutOfMemory ) { (void)hipGetLastError(); c->d_lastslab.release(); c->TP.ok[i] = false; }
+				else HIPCHK(e);
+				continue;
+			}
 			if ( TIER_CHAIN[i].role == ROLE_FRONT ) HIPCHK(c->st[i].handon.ensure(BP.nwindows+2));
 			if ( TIER_CHAIN[i].flags & STAGE_PREPASS ) HIPCHK(c->d_small.ensure(BP.nwindows+2));
 			if ( F.gbytes ) HIPCHK(c->d_gslab.ensure(static_cast<size_t>(c->st[i].grid)*F.gbytes + 256));
-			if ( F.ldsbytes > 64*1024 ) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(fastKernel(TP.tier[i])),hipFuncAttributeMaxDynamicSharedMemorySize,F.ldsbytes));
+			if ( !F.gmem && F.ldsbytes > 64*1024 ) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(fastKernel(TP.tier[i])),hipFuncAttributeMaxDynamicSharedMemorySize,F.ldsbytes));
 		}
 		{
 			// hand-over slots (sorted instances of a window that overflowed a tier's node table, picked up by the next tier): header +

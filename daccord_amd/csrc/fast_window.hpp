@@ -30,7 +30,7 @@
  *  - stretches are looked up by first / last node through small index arrays, the weights of a feasible (stretch,
  *    position) entry carry the weights of its end nodes, candidates are kept as stretch sequences and decoded once.
  *
- * The same code is instantiated for thirteen capacity tiers (FastTier<N> below; the layout FastLds<CT> is a compile time constant,
+ * The same code is instantiated for fifteen capacity tiers (FastTier<N> below; the layout FastLds<CT> is a compile time constant,
  * so every LDS access has an immediate offset).  Which of them a batch runs, in which order and behind which switches, is
  * written down once, in tier_pipeline.hpp.
  *
@@ -48,6 +48,8 @@
  *      8  slot 1 of wide batches (w = 64 ... 127)                     gw      16 /  8 bit       2
  *      9  slot 2 of wide batches                                      gw      16 / 16 bit       1
  *      5  second stream (k_window_long): strings of up to 128 bases   legacy  16 /  8 bit       1
+ *     13  last stage, shallow and deep (layout in device memory)      gw      16 / 16 bit       no LDS
+ *     14  last stage, wide batches (layout in device memory)          gw      16 / 16 bit       no LDS
  *
  * processWindowFast returns
  * FW_NEXT when a window overflows a tier (flags say what overflowed: 1 instances, 2 nodes, 8 candidates, 16 walk,
@@ -87,14 +89,14 @@ template<int TIER> struct FastTier;
 #if !defined(DACC_RCH01)
 #define DACC_RCH01 2
 #endif
-template<> struct FastTier<1> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 1024, rch = DACC_RCH01, fch = 4, fnw = 2, fnc = 40, idmax = 250, rpstcap = 256, lstr = 64, maxs = 32, precap = 1024, ncap = 776, scap = 112, lcap = 960, wcap = 1024, rccap = 144, fcap = 192, siqcap = 56, blcap = 96, seqcap = 32, psiq = 8, consrow = 64, lscrids = 2048, wide = 0, mins = 0 }; };
+template<> struct FastTier<1> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 1024, rch = DACC_RCH01, fch = 4, fnw = 2, fnc = 40, idmax = 250, rpstcap = 256, lstr = 64, maxs = 32, precap = 1024, ncap = 776, scap = 112, lcap = 960, wcap = 1024, rccap = 144, fcap = 192, siqcap = 56, blcap = 96, seqcap = 32, psiq = 8, consrow = 64, lscrids = 2048, wide = 0, mins = 0, gmem = 0 }; };
 // tier 0 (size classes): the windows a pre-pass (classifyWindow, k_classify) finds small -- few strings, at most T0INST k-mer
 // instances -- in 20 KB = 8 wavefronts per CU (two on every SIMD).  What overflows it joins the other windows in tier 1.
-template<> struct FastTier<0> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 768, rch = DACC_RCH01, fch = 4, fnw = 2, fnc = 32, idmax = 250, rpstcap = 256, lstr = 64, maxs = 28, precap = 576, ncap = 524, scap = 88, lcap = 640, wcap = 768, rccap = 96, fcap = 128, siqcap = 56, blcap = 96, seqcap = 32, psiq = 8, consrow = 64, lscrids = 2048, wide = 0, mins = 0 }; };
+template<> struct FastTier<0> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 768, rch = DACC_RCH01, fch = 4, fnw = 2, fnc = 32, idmax = 250, rpstcap = 256, lstr = 64, maxs = 28, precap = 576, ncap = 524, scap = 88, lcap = 640, wcap = 768, rccap = 96, fcap = 128, siqcap = 56, blcap = 96, seqcap = 32, psiq = 8, consrow = 64, lscrids = 2048, wide = 0, mins = 0, gmem = 0 }; };
 // tier 7 (round 6, the MIDDLE size class of shallow batches): 22.9 KB = 7 wavefronts per CU.  Four fifths of the windows tier 1 (6 per CU)
 // used to run have at most 28 strings, 704 k-mer instances, 640 nodes and 800 links (emulation, 16 piles of config 2: 4244 of 5295); the
 // pre-pass sends them here, what overflows joins tier 1's list like tier 0's hand-overs join this one.
-template<> struct FastTier<7> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 896, rch = DACC_RCH01, fch = 4, fnw = 2, fnc = 32, idmax = 250, rpstcap = 256, lstr = 64, maxs = 28, precap = 704, ncap = 640, scap = 104, lcap = 800, wcap = 896, rccap = 112, fcap = 148, siqcap = 56, blcap = 96, seqcap = 32, psiq = 8, consrow = 64, lscrids = 2048, wide = 0, mins = 0 }; };
+template<> struct FastTier<7> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 896, rch = DACC_RCH01, fch = 4, fnw = 2, fnc = 32, idmax = 250, rpstcap = 256, lstr = 64, maxs = 28, precap = 704, ncap = 640, scap = 104, lcap = 800, wcap = 896, rccap = 112, fcap = 148, siqcap = 56, blcap = 96, seqcap = 32, psiq = 8, consrow = 64, lscrids = 2048, wide = 0, mins = 0, gmem = 0 }; };
 // (the size-class thresholds of the pre-pass, T0INST_DEFAULT / T7INST_DEFAULT = the instance capacities of tiers 0 and 7: tier_pipeline.hpp)
 // tier 2: gw layout as well since round 3 (43 KB: 3 wavefronts per CU; the legacy layout was 80.5 KB: 2 per CU)
 // (round 4: 76 KB = 2 wavefronts per CU instead of 46.5 KB = 3, with tier 3's node capacity: at 54x more than half of what the deep tier
@@ -109,7 +111,7 @@ template<> struct FastTier<7> { typedef uint8_t id_t; typedef uint8_t sid_t; enu
 #if !defined(DACC_T2_LCAP)
 #define DACC_T2_LCAP 2032
 #endif
-template<> struct FastTier<2> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 3072, rch = 4, fch = 4, fnw = 4, fnc = 64, idmax = 250, rpstcap = 256, lstr = 64, maxs = 96, precap = 2048, ncap = DACC_T2_NCAP, scap = 232, lcap = DACC_T2_LCAP, wcap = 3072, rccap = 256, fcap = 192, siqcap = 96, blcap = 96, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0 }; };
+template<> struct FastTier<2> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 3072, rch = 4, fch = 4, fnw = 4, fnc = 64, idmax = 250, rpstcap = 256, lstr = 64, maxs = 96, precap = 2048, ncap = DACC_T2_NCAP, scap = 232, lcap = DACC_T2_LCAP, wcap = 3072, rccap = 256, fcap = 192, siqcap = 96, blcap = 96, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0, gmem = 0 }; };
 // tier 6 (second slot of SHALLOW batches since round 3, gw layout, 36 KB = 4 wavefronts per CU): what tier 1 hands on at 20x
 // are windows with more than its 608 nodes (82 % of the hand-overs) or fuller pools, not more strings or instances, so this
 // tier keeps tier 1's string / instance capacities and spends its LDS on nodes, stretches and pools.  Deep batches keep
@@ -117,47 +119,47 @@ template<> struct FastTier<2> { typedef uint8_t id_t; typedef uint8_t sid_t; enu
 // (round 6: the tier sat at 34 720 B, 6 KB below what four wavefronts per CU allow (40 960 B): the bytes went to what sends its windows on to
 // tier 3 -- ONE wavefront per CU -- on the ONT mix at small k (emulation, 6 piles of config 5 at k = 10 / 12: reverse pool 73 / 130, weights 53 / 1,
 // forward pool 45 / 7 of about 200 hand-overs): reverse pool 192 -> 256 paths in chunks of two, 248 stretches, 2048 weight records)
-template<> struct FastTier<6> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 2048, rch = 2, fch = 8, fnw = 3, fnc = 40, idmax = 250, rpstcap = 256, lstr = 128, maxs = 40, precap = 1024, ncap = 1024, scap = 248, lcap = 1280, wcap = 2048, rccap = 256, fcap = 256, siqcap = 96, blcap = 96, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0 }; };
+template<> struct FastTier<6> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 2048, rch = 2, fch = 8, fnw = 3, fnc = 40, idmax = 250, rpstcap = 256, lstr = 128, maxs = 40, precap = 1024, ncap = 1024, scap = 248, lcap = 1280, wcap = 2048, rccap = 256, fcap = 256, siqcap = 96, blcap = 96, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0, gmem = 0 }; };
 
 // tier 3 (one wavefront per CU): 16 bit path ids, so that an enumeration may hold more than 250 paths; sized for deep piles
 // too (BASELINE config 4, 54x: up to 96 strings with 4096 k-mer instances, 72 first / last k-mer candidates)
 // gw layout and 16 bit STRETCH ids since round 3: what the legacy tier 3 handed to the generic engine at 54x were windows with
 // more than 250 stretches (13 of 19 per 60 000 windows) or more than 2112 feasible weights (5 of 19), and each of them cost the
 // generic engine seconds (685 such windows were 92 % of a 2000-pile 54x batch, profiles/r03c_bench_54x_2000piles.log)
-template<> struct FastTier<3> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 1000, gw = 1, wcapg = 8192, rch = 8, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 96, precap = 4096, ncap = 2048, scap = 1024, lcap = 4096, wcap = 8192, rccap = 2048, fcap = 512, siqcap = 256, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0 }; };
+template<> struct FastTier<3> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 1000, gw = 1, wcapg = 8192, rch = 8, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 96, precap = 4096, ncap = 2048, scap = 1024, lcap = 4096, wcap = 8192, rccap = 2048, fcap = 512, siqcap = 256, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0, gmem = 0 }; };
 
 // tier 4 (three wavefronts per CU, takes the place of tier 1 in batches of deep piles): many strings and k-mer instances,
 // small graph.  At 54x (BASELINE config 4) 96 % of the windows find their consensus at filter frequency 2, where the graph
 // has about a hundred nodes, while the 55 strings of a window carry 1500 k-mer instances.
-template<> struct FastTier<4> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 608, rch = 4, fch = 4, fnw = 2, fnc = 40, idmax = 250, rpstcap = 256, lstr = 64, maxs = 96, precap = 2048, ncap = 256, scap = 48, lcap = 256, wcap = 608, rccap = 128, fcap = 96, siqcap = 56, blcap = 96, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0 }; };
+template<> struct FastTier<4> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 608, rch = 4, fch = 4, fnw = 2, fnc = 40, idmax = 250, rpstcap = 256, lstr = 64, maxs = 96, precap = 2048, ncap = 256, scap = 48, lcap = 256, wcap = 608, rccap = 128, fcap = 96, siqcap = 56, blcap = 96, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0, gmem = 0 }; };
 
 // tier 5 (one wavefront per CU, only for the windows the pre-scan found): B strings of up to 128 bases (string stride 128,
 // two words per pattern mask); everything else as tier 3 with 64 strings.  Window strings of more than 64 bases are rare
 // at the default window (a few per ten million windows of config 2) but each of them costs the generic engine seconds.
-template<> struct FastTier<5> { typedef uint16_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 0, wcapg = 0, rch = 8, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 64, precap = 4096, ncap = 1792, scap = 250, lcap = 2048, wcap = 2040, rccap = 512, fcap = 512, siqcap = 256, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0 }; };
+template<> struct FastTier<5> { typedef uint16_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 0, wcapg = 0, rch = 8, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 64, precap = 4096, ncap = 1792, scap = 250, lcap = 2048, wcap = 2040, rccap = 512, fcap = 512, siqcap = 256, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0, gmem = 0 }; };
 
 // tier 8 (round 6, two wavefronts per CU): WIDE windows, -w 64 ... 127 (the reference takes any -w, daccord.cpp:1282-1305; rounds 4-5 ran them in the generic
 // engine, two orders of magnitude slower per window).  What a wide window needs beyond tier 6's two-word pattern masks: feasible start positions
 // of a stretch up to nrows = w+1 <= 128 (two words per position mask: maskF / maskFh), candidates and a consensus of up to 128 symbols, the
 // two-word consensus -> A alignment and the wide window record (dev_types.hpp: WRECW).  A batch with w > 63 runs this tier alone in front of the
 // generic engine (BatchPlan::wide); sized for 20x piles at w = 64 ... 96 (20 strings of 83 k-mers at w = 96, k = 14).
-template<> struct FastTier<8> { typedef uint16_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 6144, rch = 4, fch = 8, fnw = 4, fnc = 64, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 40, precap = 3072, ncap = 2304, scap = 248, lcap = 3072, wcap = 6144, rccap = 640, fcap = 512, siqcap = 96, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 2560, wide = 1, mins = 0 }; };
+template<> struct FastTier<8> { typedef uint16_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 6144, rch = 4, fch = 8, fnw = 4, fnc = 64, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 40, precap = 3072, ncap = 2304, scap = 248, lcap = 3072, wcap = 6144, rccap = 640, fcap = 512, siqcap = 96, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 2560, wide = 1, mins = 0, gmem = 0 }; };
 
 // tier 9 (round 6, one wavefront per CU): what overflows tier 8 -- its reverse pool (512 paths), forward pool, score intervals -- before the generic
 // engine, which recomputes both enumerations for every (first, last) k-mer pair and takes seconds for such a window (30 of 37 000 windows at
 // w = 64 were 6.2 of a step's 6.7 s, profiles/r06v).  Tier 3's pools with the wide tier's masks, alignment and record.
-template<> struct FastTier<9> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 500, gw = 1, wcapg = 8192, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 64, precap = 4096, ncap = 3072, scap = 512, lcap = 4096, wcap = 8192, rccap = 2048, fcap = 1024, siqcap = 256, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 2560, wide = 1, mins = 0 }; };
+template<> struct FastTier<9> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 500, gw = 1, wcapg = 8192, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 64, precap = 4096, ncap = 3072, scap = 512, lcap = 4096, wcap = 8192, rccap = 2048, fcap = 1024, siqcap = 256, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 2560, wide = 1, mins = 0, gmem = 0 }; };
 
 // tier 10 (round 6, two wavefronts per CU): the DENSE-graph tier of shallow batches, between tier 6 (four per CU, 8 bit path ids: 256 reverse
 // paths) and tier 3 (ONE per CU).  On the ONT error mix at k = 10 tier 6 hands 1.4 % of the windows on -- reverse pools of more than 256 paths,
 // forward pools, more than 1024 k-mer instances -- and tier 3 needs 17 % of the step for them (profiles/r06k/bench_ont_k10.log; VERDICT r05 task 4:
 // "more than 1 % in tier 3: add a dense-graph tier").  Tier 8's pools and 16 bit ids without its wide parts.
-template<> struct FastTier<10> { typedef uint16_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 6144, rch = 4, fch = 8, fnw = 4, fnc = 64, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 64, precap = 2560, ncap = 2048, scap = 248, lcap = 3072, wcap = 6144, rccap = 896, fcap = 512, siqcap = 128, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0 }; };
+template<> struct FastTier<10> { typedef uint16_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 6144, rch = 4, fch = 8, fnw = 4, fnc = 64, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 64, precap = 2560, ncap = 2048, scap = 248, lcap = 3072, wcap = 6144, rccap = 896, fcap = 512, siqcap = 128, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0, gmem = 0 }; };
 
 // tier 11 (round 6, two wavefronts per CU): tier 10's place in batches of DEEP piles, between tier 2 (three per CU, 2048 k-mer instances) and tier 3 (one per CU).
 // At 54x what tier 2 hands on are windows of more than 2048 k-mer instances (75 strings and more: 186 of 208 hand-overs in 12 piles of config 4), a few node
 // tables and pools; tier 3 needs 6.8 % of the step for them (profiles/r06zz/bench_54x_2000piles.log).  Tier 3's string / instance capacities with tier 10's pools.
-template<> struct FastTier<11> { typedef uint16_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 4096, rch = 4, fch = 8, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 96, precap = 4096, ncap = 1536, scap = 248, lcap = 2048, wcap = 4096, rccap = 640, fcap = 384, siqcap = 128, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0 }; };
+template<> struct FastTier<11> { typedef uint16_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 4096, rch = 4, fch = 8, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 96, precap = 4096, ncap = 1536, scap = 248, lcap = 2048, wcap = 4096, rccap = 640, fcap = 384, siqcap = 128, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0, gmem = 0 }; };
 
 // tier 12 (one wavefront per CU): the DEEP-WINDOW tier, windows of 97 ... 250 strings (repeat piles: the rRNA operons of a bacterial genome at 20x
 // are about 140 deep, a low-copy repeat at 54x 100 ... 220), which every other tier refuses at its string count and which used to run in the
@@ -168,7 +170,21 @@ template<> struct FastTier<11> { typedef uint16_t id_t; typedef uint8_t sid_t; e
 // mins: the tier takes only the windows with MORE strings than that and passes the others on untouched (tier 3 runs what it ran before).
 // String ids stay 8 bits in the compact string list of the instance generation (maxs <= 256); a k-mer seen more than 255 times does not fit
 // the node frequency byte and sends the window on (buildNodes: overflow bit 2), nothing wraps.
-template<> struct FastTier<12> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 1000, gw = 1, wcapg = 8192, rch = 8, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 250, precap = 8192, ncap = 2048, scap = 1024, lcap = 4096, wcap = 8192, rccap = 2048, fcap = 512, siqcap = 256, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 96 }; };
+template<> struct FastTier<12> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 1000, gw = 1, wcapg = 8192, rch = 8, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 250, precap = 8192, ncap = 2048, scap = 1024, lcap = 4096, wcap = 8192, rccap = 2048, fcap = 512, siqcap = 256, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 96, gmem = 0 }; };
+
+// tiers 13 and 14: the LAST stage, behind the slots and in front of the generic engine (tier_pipeline.hpp: ID_LAST).  gmem: the whole layout FastLds<CT>
+// lives in the workgroup's slab in device memory instead of LDS (k_fast_13.hip / k_fast_14.hip compile this header with LDSQ = the global address
+// space; nothing else changes -- the emulation has always run the tiers over a plain buffer).  A dependent load that hits L2 costs 180 ... 225 cycles
+// against about 50 for ds_read, so a window costs a few times what it costs in tier 3 -- and not the seconds of the generic engine, which recomputes
+// stretches, feasibility and both enumerations for every (first, last) k-mer pair.  Without the 160 KiB of a CU as a bound every table is at least
+// as large as the largest of tiers 3, 6, 9, 10, 11 and 12, and the tables that have sent windows to the generic engine are twice tier 3's (tier 9's
+// in the wide tier 14): nodes, stretches, links, weights, both pools, score intervals; 16384 k-mer instances.
+//  - reverse pool: 4096 paths in 256 chunks of 16 (8 bit chunk ids kept: tier 3 has 256 chunks of 8, so an enumeration needs at most as many chunks here);
+//  - 16 bit weight offsets and task offsets kept: 16384 weight records per direction, at most 65535 (stretch, direction, position) tasks per traversal;
+//  - more than 4094 nodes: the stretch sort key takes 13 bit node fields and a 12 bit stretch number (FastEngine: KF, QB).
+// Windows of more than 250 strings, wider than 127 bases or with a string of more than 128 bases still go to the generic engine.
+template<> struct FastTier<13> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 2000, gw = 1, wcapg = 16384, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 250, precap = 16384, ncap = 4096, scap = 2048, lcap = 8192, wcap = 16384, rccap = 4096, fcap = 1024, siqcap = 512, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 4096, wide = 0, mins = 0, gmem = 1 }; };
+template<> struct FastTier<14> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 1000, gw = 1, wcapg = 16384, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 250, precap = 16384, ncap = 6144, scap = 1024, lcap = 8192, wcap = 16384, rccap = 4096, fcap = 2048, siqcap = 512, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 4096, wide = 1, mins = 0, gmem = 1 }; };
 
 HDEV constexpr uint32_t fcpow2(uint32_t v) { uint32_t p = 1; while ( p < v ) p <<= 1; return p; }
 HDEV constexpr uint32_t fcmax(uint32_t a, uint32_t b) { return a > b ? a : b; }
@@ -561,6 +577,8 @@ struct FastLds<CT,true>
 		g_bytes = g_inst + (((CT::precap + keycap)*8u + 255u) & ~255u);
 	static_assert((o_pre & 15u) == 0 && (CT::precap & 1u) == 0 && (keycap & 1u) == 0,"instance arrays are saved 16 bytes at a time");
 	static constexpr uint32_t xnslot = (32u*CT::wcapg) / 128u;
+	// device-memory tiers (CT::gmem): this layout itself sits behind the instance image, g_total bytes per workgroup in all
+	static constexpr uint32_t g_layout = g_bytes, g_total = CT::gmem ? g_bytes + ((((uend + 15u) & ~15u) + 255u) & ~255u) : g_bytes;
 };
 #undef FLD
 
@@ -573,7 +591,9 @@ HDEV FastCaps fastCapsOf(uint32_t const nrows, uint32_t const nsup)
 	C.nrows = nrows; C.nsup = nsup;
 	C.ldsbytes = FastLds<CT>::bytes(nrows,nsup);
 	C.tabcap = FastLds<CT>::tabcap;
-	if constexpr ( CT::gw != 0 ) C.gbytes = FastLds<CT>::g_bytes; else C.gbytes = 0;
+	if constexpr ( CT::gw != 0 ) C.gbytes = FastLds<CT>::g_total; else C.gbytes = 0;
+	C.gmem = CT::gmem;
+	static_assert(CT::gmem == 0 || CT::gw != 0,"a layout in device memory is the gw layout");
 	return C;
 }
 
@@ -1176,7 +1196,9 @@ struct FastEngine
 	}
 	// (first, ext, len desc, last) packed into 56 bits: Stretch::operator< (node ids ascend with k-mer value)
 	// (8 bit stretch ids: four 14 bit fields = 56 bits next to the id; 16 bit ids: four 12 bit fields = 48 bits)
-	enum : uint32_t { KF = (sizeof(sid_t) == 1 ? 14u : 12u), KFMAX = (1u<<KF)-1u };
+	// (16 bit ids and more than 4094 nodes -- the device-memory tiers --: four 13 bit fields = 52 bits next to a 12 bit stretch number, QB)
+	enum : uint32_t { KF = (sizeof(sid_t) == 1 ? 14u : (CT::ncap > 4094u ? 13u : 12u)), KFMAX = (1u<<KF)-1u, QB = (KF == 13u ? 12u : static_cast<uint32_t>(SB)), QMASK = (1u<<QB)-1u };
+	static_assert(4u*KF + QB <= 64u && CT::scap <= (1u<<QB) && CT::ncap <= KFMAX,"stretch sort key: four node fields and the stretch number in 64 bits");
 	DEV static uint64_t sortKey(uint32_t first, uint32_t ext, uint32_t len, uint32_t last)
 	{
 		return (static_cast<uint64_t>(first)<<(3*KF)) | (static_cast<uint64_t>(ext)<<(2*KF)) | (static_cast<uint64_t>(KFMAX-len)<<KF) | last;
@@ -1250,15 +1272,15 @@ struct FastEngine
 		wv_sync();
 		uint32_t const p2 = next_pow2(ns < 2 ? 2 : ns);
 		for ( uint32_t q = lane; q < p2; q += WSZ )
-			L.skey()[q] = q < ns ? ((sortKey(L.tfirst()[q],L.links()[L.tlink()[q]+1],L.tslen()[q] < KFMAX ? L.tslen()[q] : KFMAX,L.tlast()[q])<<SB) | q) : ~0ull;
+			L.skey()[q] = q < ns ? ((sortKey(L.tfirst()[q],L.links()[L.tlink()[q]+1],L.tslen()[q] < KFMAX ? L.tslen()[q] : KFMAX,L.tlast()[q])<<QB) | q) : ~0ull;
 		wv_sync();
 		wv_sort_keys<fcpow2(CT::scap)>(L.skey(),ns);
 		// distinct (first,ext) by construction; a duplicate would need stretchesUnique's tie handling -> generic engine
 		uint32_t dup = 0;
 		for ( uint32_t q = lane; q < ns; q += WSZ )
 		{
-			if ( q && (L.skey()[q]>>(SB+2*KF)) == (L.skey()[q-1]>>(SB+2*KF)) ) dup = 1;
-			uint32_t const raw = L.skey()[q]&SMASK;
+			if ( q && (L.skey()[q]>>(QB+2*KF)) == (L.skey()[q-1]>>(QB+2*KF)) ) dup = 1;
+			uint32_t const raw = L.skey()[q]&QMASK;
 			L.sfirst()[q] = L.tfirst()[raw]; L.slast()[q] = L.tlast()[raw]; L.sslen()[q] = L.tslen()[raw]; L.slink()[q] = L.tlink()[raw];
 		}
 		if ( wv_any(dup) ) { over(32); n0 = 0; return; }

@@ -8,6 +8,7 @@
  *   deep batches      slot 0: 4               slot 1: 2     slot 2: 11 -> 12 -> 3
  *   wide batches                              slot 1: 8     slot 2: 9
  *   shallow and deep  tier 5 on the second stream (k_window_long), in front of the generic engine there
+ *   every batch       the LAST stage, once, behind the slots and in front of the generic engine: tier 13 (shallow, deep) / tier 14 (wide)
  *
  * (TIER_CHAIN below: one row per stage, one column per batch shape.)
  *
@@ -15,6 +16,13 @@
  * windows) and hands on to the next slot, the last one to the generic engine.  FRONT tiers run before the main tier of their slot
  * with more wavefronts per CU: each hands on to the next stage of its slot.  Tiers 0 and 7 are fed by the size-class pre-pass
  * (k_classify), tiers 10 / 11 by the list of the slot in front, tier 12 (windows of 97 ... 250 strings; it passes the others on) by what they hand on.
+ *
+ * The LAST stage (ID_LAST, ROLE_LAST) is no slot: its tiers keep the layout FastLds<CT> in a slab of device memory per workgroup instead of
+ * LDS (FastCaps::gmem), with tables no CU's LDS could hold.  It reads the list the last enabled slot handed on and hands on to the generic
+ * engine (k_window), which recomputes both enumerations for every (first, last) k-mer pair and is two to three orders of magnitude slower per
+ * window.  DACC_LAST_TIER=0 removes it; it does not run when no slot runs.  DACC_LAST_AS_SLOT2=1 (tests, A/B timing) makes the last stage's
+ * tier the main tier of the third slot instead (13 for 3, 14 for 9) and switches ID_LAST off: the planner, the launches and the emulation
+ * harness then run the device-memory tiers as an ordinary slot.
  */
 #ifndef DACC_TIER_PIPELINE_HPP
 #define DACC_TIER_PIPELINE_HPP
@@ -31,14 +39,15 @@ struct FastCaps
 	uint32_t tabcap;             // 32-bit words the table overlay of this tier can hold
 	uint32_t nrows, nsup;        // dimensions of the fixed-point table copy held in LDS
 	uint32_t ldsbytes;
-	uint32_t gbytes;             // gw tiers: bytes of global scratch per workgroup (0: none)
+	uint32_t gbytes;             // gw tiers: bytes of global scratch per workgroup (0: none); with gmem: the layout (ldsbytes, at gbytes - its rounded size) included
+	uint32_t gmem;               // 1: the layout lives in the workgroup's slab in device memory -- no LDS requested, no 160 KiB gate; ldsbytes stays the layout's size
 };
 enum { FSUPCAP = 128, FSUPCAPW = 192 };      // max width (read offsets) of the model table copy in LDS (W: the wide tiers -- the table of w = 127 covers 165 read offsets)
 enum : uint32_t { T0INST_DEFAULT = 576, T7INST_DEFAULT = 704 };      // a window with more k-mer instances (upper bound of the pre-pass) starts in tier 7 / tier 1; run-time
                                                // arguments of the pre-pass (DACC_T0INST / DACC_T7INST override them for sweeps)
 
 // The tiers.  KERNEL: those with a kernel of their own (k_window_fast<N>, window_kernels.hpp); tier 5 runs inside k_window_long.
-#define DACC_KERNEL_TIERS(X) X(0) X(1) X(2) X(3) X(4) X(6) X(7) X(8) X(9) X(10) X(11) X(12)
+#define DACC_KERNEL_TIERS(X) X(0) X(1) X(2) X(3) X(4) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14)
 #define DACC_ALL_TIERS(X) DACC_KERNEL_TIERS(X) X(5)
 
 // From a run-time tier number to its compile-time capacities: f is called with a TierTag<N>, whose `type` is FastTier<N>
@@ -52,7 +61,7 @@ template<typename F> static inline auto withTier(uint32_t const tier, F && f) ->
 	std::abort();
 }
 
-enum TierRole { ROLE_FRONT, ROLE_MAIN, ROLE_LONG };      // front tier of a slot, the slot's main tier, tier 5 on the second stream
+enum TierRole { ROLE_FRONT, ROLE_MAIN, ROLE_LONG, ROLE_LAST };      // front tier of a slot, the slot's main tier, tier 5 on the second stream, the device-memory tier behind the slots
 // What switches a stage off, beside its bit of DACC_TIERS, its LDS size (at most the 160 KiB of a CU) and a batch shape it has no tier
 // for (TIER_NONE: "not in a wide batch", "not in a deep batch").  A front tier also needs the main tier of its slot.
 enum : uint32_t
@@ -63,6 +72,7 @@ enum : uint32_t
 	GATE_DENSE = 8,       // DACC_DENSE_TIER=0 switches it off
 	GATE_PREV_SLOT = 16,  // needs the main tier of the slot in front as well (the dense tiers need slots 1 and 2)
 	GATE_DEEP = 128,      // DACC_DEEP_TIER=0 switches it off (windows of more than 96 strings run in the generic engine, as before the deep-window tier)
+	GATE_LAST = 256,      // DACC_LAST_TIER=0 or DACC_LAST_AS_SLOT2=1 switches it off; needs a slot that ran
 	STAGE_PREPASS = 32,   // (no gate) fed by the size-class pre-pass instead of the list in front of it
 	STAGE_ADAPTIVE = 64   // (no gate) switches itself off for the rest of a context when it hands on too much (DACC_T7_ADAPT)
 };
@@ -71,10 +81,10 @@ enum : uint32_t { WORK_SLOT0 = 0, WORK_SLOT1 = 8, WORK_SLOT2 = 16, WORK_DENSE = 
 	WORK_PRE_MID = 56, WORK_PRE_BIG = 57,      // what the pre-pass itself put on the middle and the big list (for dacc_timing)
 	WORK_TRACE = 60, WORK_DEEP = 64,
 	WORK_DEEP_COUNT = 72,      // two words: windows of more than FastTier<12>::mins strings the deep-window tier read / handed on (for dacc_timing)
-	WORK_WORDS = 80 };
+	WORK_LAST = 80, WORK_WORDS = 88 };
 
 // The stages, in the order they run; their place in this table is their place in BatchPlan::stageCaps, TierPipeline and dacc_ctx::st.
-enum TierId { ID_T0, ID_T7, ID_SLOT0, ID_SLOT1, ID_DENSE, ID_DEEP, ID_SLOT2, ID_LONG, TIER_NSTAGES };
+enum TierId { ID_T0, ID_T7, ID_SLOT0, ID_SLOT1, ID_DENSE, ID_DEEP, ID_SLOT2, ID_LAST, ID_LONG, TIER_NSTAGES };
 enum { TIER_NSLOTS = 3, TIER_NONE = 255, TIER_SHALLOW_FIRST = 1 };      // (the first slot's main tier of shallow batches: a batch whose windows mostly overflow its strings / instances is deep)
 struct TierStage { uint8_t tier[3] /* in a shallow, deep, wide batch */, slot, role; int8_t tiersbit /* bit of DACC_TIERS */; uint32_t flags, work; };
 static TierStage const TIER_CHAIN[TIER_NSTAGES] = {
@@ -85,15 +95,19 @@ static TierStage const TIER_CHAIN[TIER_NSTAGES] = {
 	{ { 10, 11, TIER_NONE }, 2, ROLE_FRONT, -1, GATE_TABFIT|GATE_DENSE|GATE_PREV_SLOT, WORK_DENSE },
 	{ { 12, 12, TIER_NONE }, 2, ROLE_FRONT, -1, GATE_TABFIT|GATE_DEEP|GATE_PREV_SLOT, WORK_DEEP },
 	{ { 3, 3, 9 }, 2, ROLE_MAIN, 2, GATE_TABFIT, WORK_SLOT2 },
+	{ { 13, 13, 14 }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_LAST, WORK_LAST },
 	// (tier 5 holds no wide window: a wide batch's second stream is the generic engine alone, at its own occupancy instead of a CU's LDS per wavefront)
 	{ { 5, 5, TIER_NONE }, 0, ROLE_LONG, 2, GATE_TABFIT, 0 } };
 static TierId const TIER_MAIN[TIER_NSLOTS] = { ID_SLOT0, ID_SLOT1, ID_SLOT2 };
 // does the stage run in a batch of this shape, and the tier whose capacities the plan holds for it (a stage that does not run keeps
 // those of the nearest shape: the first slot of a wide batch has tier 1's or tier 4's)
 static inline bool stageRuns(TierStage const & st, bool const deep, bool const wide) { return st.tier[wide ? 2 : deep] != TIER_NONE; }
+// DACC_LAST_AS_SLOT2=1: the third slot's main tier is the last stage's tier (read by the planner and by resolveTiers alike, so once per call)
+static inline bool lastAsSlot2() { char const * const e = getenv("DACC_LAST_AS_SLOT2"); return e && e[0] == '1'; }
 static inline uint32_t stageTier(TierStage const & st, bool const deep, bool const wide)
 {
-	return (wide && st.tier[2] != TIER_NONE) ? st.tier[2] : (st.tier[deep] != TIER_NONE ? st.tier[deep] : st.tier[0]);
+	TierStage const & t = (&st == &TIER_CHAIN[ID_SLOT2] && lastAsSlot2()) ? TIER_CHAIN[ID_LAST] : st;
+	return (wide && t.tier[2] != TIER_NONE) ? t.tier[2] : (t.tier[deep] != TIER_NONE ? t.tier[deep] : t.tier[0]);
 }
 
 // the environment switches of the chain, read once per context
@@ -104,6 +118,8 @@ struct TierSwitches
 	bool widetier;            // DACC_WIDE_TIER=0: wide batches run in the generic engine only, as in rounds 4-5
 	bool dense;               // DACC_DENSE_TIER=0: the second slot hands on to tier 3 directly (before round 6's dense tiers)
 	bool deepwin;             // DACC_DEEP_TIER=0: no deep-window tier (tier 12) in front of tier 3
+	bool lasttier;            // DACC_LAST_TIER=0: no device-memory stage in front of the generic engine (the chain as it was before that stage)
+	bool last_as_slot2;       // DACC_LAST_AS_SLOT2=1: tier 13 / 14 as the third slot's main tier, no last stage
 	bool long128;             // DACC_LONG128=0: windows with a string of 65 ... 128 bases run in tier 5 on the second stream (rounds 3-5)
 	bool hand;                // DACC_HAND=0: no hand-over buffer, every hand-over restarts from the strings
 	uint32_t t0inst, t7inst;  // DACC_T0INST / DACC_T7INST: size-class thresholds (k-mer instances) of tiers 0 and 7
@@ -116,7 +132,7 @@ static inline TierSwitches readTierSwitches()
 	TierSwitches S;
 	{ char const * const e = getenv("DACC_NOFAST"); S.nofast = e && e[0] == '1'; }
 	S.tiers = num("DACC_TIERS",31);
-	S.widetier = !off("DACC_WIDE_TIER"); S.dense = !off("DACC_DENSE_TIER"); S.deepwin = !off("DACC_DEEP_TIER"); S.long128 = !off("DACC_LONG128"); S.hand = !off("DACC_HAND");
+	S.widetier = !off("DACC_WIDE_TIER"); S.dense = !off("DACC_DENSE_TIER"); S.deepwin = !off("DACC_DEEP_TIER"); S.lasttier = !off("DACC_LAST_TIER"); S.last_as_slot2 = lastAsSlot2(); S.long128 = !off("DACC_LONG128"); S.hand = !off("DACC_HAND");
 	S.t0inst = num("DACC_T0INST",T0INST_DEFAULT); S.t7inst = num("DACC_T7INST",T7INST_DEFAULT);
 	S.lds_t1 = num("DACC_LDS_T1",0); S.lds_t0 = num("DACC_LDS_T0",0);
 	return S;
@@ -124,10 +140,24 @@ static inline TierSwitches readTierSwitches()
 
 enum : uint32_t { TIER_LDS_CU = 160*1024 };
 // launch geometry of a tier: floor(160 KiB / ldsbytes) wavefronts per CU, 1 ... 8, and a workgroup per window up to 256 CUs' worth
+// (a device-memory tier is launched with tierGridGmem below)
 static inline uint32_t tierGrid(uint32_t const ldsbytes, uint64_t const nwindows)
 {
 	uint64_t const percu = std::min<uint64_t>(8,std::max<uint64_t>(1,TIER_LDS_CU / (ldsbytes ? ldsbytes : 1)));
 	return static_cast<uint32_t>(std::min<uint64_t>(256*percu,std::max<uint64_t>(8,((nwindows+7)/8)*8)));
+}
+
+// Launch geometry of a device-memory tier (FastCaps::gmem): no LDS and 512 registers, so up to four workgroups per CU would fit; what bounds the
+// grid is the slab, gbytes per workgroup (tier 13: 1 059 840 B, tier 14: 1 125 632 B), kept to TIER_GMEM_SLAB = 256 MiB per context:
+// 256 MiB / 1 059 840 B = 253 -> 248 workgroups (a multiple of 8, one share per XCD), 232 for tier 14 -- about one per CU, whose working sets
+// (1 MB each) then share the L2 of their XCD with no more than 31 others.  The stage sees a few windows per batch, hundreds on high-error data;
+// a small batch gets a workgroup per window and a slab to match.
+enum : uint64_t { TIER_GMEM_SLAB = 256ull << 20 };
+static inline uint32_t tierGridGmem(uint32_t const gbytes, uint64_t const nwindows)
+{
+	uint64_t g = std::min<uint64_t>(1024,std::max<uint64_t>(8,((nwindows+7)/8)*8));
+	uint64_t const fit = (TIER_GMEM_SLAB / (gbytes ? gbytes : 1)) & ~7ull;
+	return static_cast<uint32_t>(std::max<uint64_t>(8,std::min<uint64_t>(g,fit)));
 }
 
 // The chain of one batch with every gate resolved, by TierId.
@@ -159,13 +189,15 @@ static inline TierPipeline resolveTiers(TierSwitches const & S, bool const fastp
 	auto const gated = [&](uint32_t const i) -> bool
 	{
 		TierStage const & st = TIER_CHAIN[i]; FastCaps const & F = capsOf(i);
-		return R.usefast && stageRuns(st,deep,wide) && F.ldsbytes <= TIER_LDS_CU && (st.tiersbit < 0 || ((S.tiers >> st.tiersbit) & 1))
+		return R.usefast && stageRuns(st,deep,wide) && (F.gmem || F.ldsbytes <= TIER_LDS_CU) && (st.tiersbit < 0 || ((S.tiers >> st.tiersbit) & 1))
 			&& (!(st.flags & GATE_TABFIT) || static_cast<uint64_t>(nrows+1)*(nsup+1) <= F.tabcap)
-			&& (!(st.flags & GATE_T7_ABOVE_T0) || S.t7inst > S.t0inst) && (!(st.flags & GATE_DENSE) || S.dense) && (!(st.flags & GATE_DEEP) || S.deepwin);
+			&& (!(st.flags & GATE_T7_ABOVE_T0) || S.t7inst > S.t0inst) && (!(st.flags & GATE_DENSE) || S.dense) && (!(st.flags & GATE_DEEP) || S.deepwin)
+			&& (!(st.flags & GATE_LAST) || (S.lasttier && !S.last_as_slot2));
 	};
 	{ FastCaps & F = capsOf(ID_SLOT0); if ( S.lds_t1 > F.ldsbytes && S.lds_t1 <= TIER_LDS_CU ) F.ldsbytes = S.lds_t1; }
 	{ FastCaps & F = capsOf(ID_T0); if ( S.lds_t0 > F.ldsbytes && S.lds_t0 <= TIER_LDS_CU ) F.ldsbytes = S.lds_t0; }
 	for ( uint32_t i = 0; i < TIER_NSTAGES; ++i ) { R.tier[i] = stageTier(TIER_CHAIN[i],deep,wide); if ( TIER_CHAIN[i].role != ROLE_FRONT ) R.ok[i] = gated(i); }
+	R.ok[ID_LAST] = R.ok[ID_LAST] && R.anytier();      // it reads what a slot handed on: no slot, no last stage (generic-only configurations stay generic-only)
 	// the front tiers, in chain order (a front tier stands before the main tier of its slot)
 	for ( uint32_t i = 0; i < TIER_NSTAGES; ++i )
 	{

@@ -159,7 +159,12 @@
 #endif
 
 // address space qualifiers: on the device LDS pointers are 32 bit ds_* addresses, on the host (planning, emulation) plain pointers
-#if defined(__HIP_DEVICE_COMPILE__)
+// (DACC_LAYOUT_IN_GLOBAL, set by k_fast_13.hip / k_fast_14.hip in front of their includes: the tier layout of THAT unit lives in device memory,
+// so its "LDS" pointers are global ones; no other unit sees the macro)
+#if defined(__HIP_DEVICE_COMPILE__) && defined(DACC_LAYOUT_IN_GLOBAL)
+#define LDSQ __attribute__((address_space(1)))
+#define GLBQ __attribute__((address_space(1)))
+#elif defined(__HIP_DEVICE_COMPILE__)
 #define LDSQ __attribute__((address_space(3)))
 #define GLBQ __attribute__((address_space(1)))
 #else

@@ -176,7 +176,8 @@ typedef struct dacc_timing {
 	uint64_t nblocks;        /* trace blocks aligned */
 	uint64_t algo_bytes;     /* algorithmic bytes of the batch */
 	float tier_ms[3];        /* LDS capacity tiers of the window kernel (3, 2, 1 wavefronts per CU); window_ms = all + generic */
-	uint32_t tier_out[3];    /* windows each tier handed on (tier_out[2] = windows run by the generic engine) */
+	uint32_t tier_out[3];    /* windows each tier slot handed on; tier_out[2]: what the last slot handed on -- the input of the last stage (last_windows + last_out),
+	                            the windows of the generic engine where that stage does not run */
 	uint32_t first_tier;     /* kernel of the first slot: 1 = k_window_fast<1>, 4 = k_window_fast<4> (batch of deep piles) */
 	uint32_t long_windows;   /* windows the second stream ran (a string of more than 64 bases, or a shape no LDS tier takes) */
 	float tier0_ms;          /* size classes (shallow batches): pre-pass + k_window_fast<0>, the part of tier_ms[0] in front of k_window_fast<1>; 0 if tier 0 did not run */
@@ -196,6 +197,11 @@ typedef struct dacc_timing {
 	uint32_t deep_windows;   /* windows of more than 96 strings that finished in tier 12 */
 	uint32_t deep_out;       /* windows of more than 96 strings tier 12 handed on (more than 250 strings, a k-mer seen more than 255 times, a graph or pool beyond its capacities): they end in the generic engine */
 	uint32_t pad3_;
+	/* the last stage: k_window_fast<13> (wide batches: <14>), the tier whose layout lives in device memory, behind the slots and in front of k_window; not a part of tier_ms[] */
+	float last_ms;           /* its kernel; 0 if it did not run (DACC_LAST_TIER=0, DACC_LAST_AS_SLOT2=1, no slot ran, no memory for its slab) */
+	uint32_t last_windows;   /* windows that finished in it */
+	uint32_t last_out;       /* windows it handed on to k_window (more than 250 strings, w = 128, a string of more than 128 bases, a table beyond its capacities) */
+	uint32_t pad4_;
 } dacc_timing;
 #define DACC_TIMING_SIZE_V1 128
 /* dacc_last_timing fills the first DACC_TIMING_SIZE_V1 bytes only (the record as it was when the call was introduced: a caller built against

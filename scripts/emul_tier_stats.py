@@ -1,5 +1,7 @@
 """CPU design aid: run the 1-lane host emulation of the window kernels on a slice of BASELINE config 2 and report how many
-windows each capacity tier hands on and why (DACC_EMUL_OVER lines).  No GPU needed; the counts are deterministic."""
+windows each capacity tier hands on and why (DACC_EMUL_OVER lines).  No GPU needed; the counts are deterministic.
+The harness runs the slots of the chain: with DACC_LAST_AS_SLOT2=1 in the environment the third slot is the device-memory tier (13, wide
+batches 14), so its lines say what the last stage still hands on to the generic engine."""
 import os, sys, re, subprocess, collections, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -13,8 +15,10 @@ if os.environ.get("DACC_EMUL_OVER") is None and "--child" not in sys.argv:
             cnt[(int(m.group(1)), m.group(3), int(m.group(2)))] += 1
         elif l.strip():
             print(l)
+    # the key of a line is maxs * 10000 + ncap of the tier that overflowed: the tiers that share their string count with none
+    names = {2502048: " (tier 12)", 2504096: " (tier 13, device memory)", 2506144: " (tier 14, device memory, wide)"}
     for key, v in sorted(cnt.items()):
-        print("tier maxs=%d bits=%s line=%d : %d" % (key[0], key[1], key[2], v))
+        print("tier maxs=%d%s bits=%s line=%d : %d" % (key[0], names.get(key[0], ""), key[1], key[2], v))
     sys.exit(p.returncode)
 import numpy as np
 import emul_lib
