@@ -446,7 +446,7 @@ int dacc_create(dacc_ctx ** out, dacc_params const * p)
 	if ( !out || !p ) return DACC_EINVAL;
 	*out = 0;
 	if ( p->klow < 3 || p->khigh > 16 || p->klow > p->khigh || !p->w || !p->a || p->w > DACC_WMAX || p->minfilterfreq < 0 ||
-	     p->maxfilterfreq < p->minfilterfreq || p->tspace <= 0 )
+	     p->maxfilterfreq < p->minfilterfreq || p->tspace <= 0 || p->tspace > 512 )      // (tspace: 1..512, what the planner and the trace kernels hold)
 		return DACC_EINVAL;
 	int ndev = 0;
 	if ( hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || p->device < 0 || p->device >= ndev )

@@ -43,10 +43,44 @@ def test_no_cpu_fallback():
 
 
 def test_bad_params_rejected():
-    for kw in (dict(k=2), dict(k=17), dict(klow=9, khigh=8), dict(w=0), dict(w=129)):
+    for kw in (dict(k=2), dict(k=17), dict(klow=9, khigh=8), dict(w=0), dict(w=129), dict(tspace=0), dict(tspace=513), dict(tspace=1000)):
         h = C.c_void_p()
         rc = engine.lib().dacc_create(C.byref(h), C.byref(default_params(**kw)))
-        assert rc == -1
+        assert rc == -1, kw
+
+
+def _plan_only(p, d, ovl, piles):
+    L = engine.lib()
+    L.dacc_plan_only.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int,
+                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    rlen = np.ascontiguousarray(d.rlen, np.uint32); piles = np.ascontiguousarray(piles); ovl = np.ascontiguousarray(ovl); tr = np.ascontiguousarray(d.trace)
+    nw = C.c_uint64(12345); nb = C.c_uint64(12345)
+    rc = L.dacc_plan_only(C.byref(p), rlen.ctypes.data, len(rlen), piles.ctypes.data if len(piles) else None, len(piles), ovl.ctypes.data, len(ovl),
+                          tr.ctypes.data, tr.nbytes // d.trace_bytes, d.trace_bytes, C.byref(nw), C.byref(nb))
+    return rc, nw.value, nb.value
+
+
+def test_trace_spacing_contract_of_the_planner():
+    """include/daccord_hip.h: tspace 1 ... 512.  The planner (batch_plan.hpp, before anything is uploaded) refuses a larger spacing with
+    DACC_ENOTSUP and plans 512 and 1; no device is involved, and no test submits a spacing above 512 to one."""
+    import edge_cases as EC
+    d, ovl, piles = EC.data("tspace512")
+    assert d.trace_bytes == 2
+    rc, nw, nb = _plan_only(default_params(k=8, tspace=512), d, ovl, piles)
+    assert rc == 0 and nw == EC.CASES["tspace512"][3][0] and nb > 0
+    for ts in (513, 1000):
+        rc, nw, nb = _plan_only(default_params(k=8, tspace=ts), d, ovl, piles)
+        assert rc == -6 and nw == 0 and nb == 0, (ts, rc, nw, nb)          # DACC_ENOTSUP
+    # spacing 1: one trace block per base
+    from daccord_amd.synth import SynthData
+    d1 = SynthData(3000, 30, 300, seed=5, min_overlap=100, tspace=1)
+    o1, p1 = pyoracle.pile_select(d1.ovl, d1.piles)
+    assert len(o1) > 0 and (o1["tlen"] == 2 * (o1["aepos"] - o1["abpos"])).all()
+    rc, nw, nb = _plan_only(default_params(k=8, tspace=1), d1, o1, p1[:4])
+    assert rc == 0 and nw > 0 and nb == int(o1["tlen"][:int(p1[3]["first_ovl"] + p1[3]["novl"])].sum()) // 2, (rc, nw, nb)
+    # and an empty batch
+    assert _plan_only(default_params(k=8, tspace=1), d1, o1, p1[:0])[0] == 0
+    assert _plan_only(default_params(k=8, tspace=513), d1, o1, p1[:0])[0] == -6
 
 
 def test_pile_select_matches_oracle(small_data):
