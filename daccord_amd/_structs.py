@@ -40,7 +40,9 @@ class DaccTiming(C.Structure):
                 # (everything above: DACC_TIMING_SIZE_V1 bytes, what dacc_last_timing fills; the deep-window tier: dacc_last_timing2)
                 ("deep_ms", C.c_float), ("deep_windows", C.c_uint32), ("deep_out", C.c_uint32), ("pad3_", C.c_uint32),
                 # the last stage (tier 13 / 14, layout in device memory, in front of k_window)
-                ("last_ms", C.c_float), ("last_windows", C.c_uint32), ("last_out", C.c_uint32), ("pad4_", C.c_uint32)]
+                ("last_ms", C.c_float), ("last_windows", C.c_uint32), ("last_out", C.c_uint32), ("pad4_", C.c_uint32),
+                # the very deep stage (k_window_fast<15>, windows of 251 ... 1000 strings, behind the last stage)
+                ("vdeep_ms", C.c_float), ("vdeep_windows", C.c_uint32), ("vdeep_out", C.c_uint32), ("pad5_", C.c_uint32)]
 
 
 TIMING_SIZE_V1 = 128

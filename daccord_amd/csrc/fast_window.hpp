@@ -30,7 +30,7 @@
  *  - stretches are looked up by first / last node through small index arrays, the weights of a feasible (stretch,
  *    position) entry carry the weights of its end nodes, candidates are kept as stretch sequences and decoded once.
  *
- * The same code is instantiated for fifteen capacity tiers (FastTier<N> below; the layout FastLds<CT> is a compile time constant,
+ * The same code is instantiated for sixteen capacity tiers (FastTier<N> below; the layout FastLds<CT> is a compile time constant,
  * so every LDS access has an immediate offset).  Which of them a batch runs, in which order and behind which switches, is
  * written down once, in tier_pipeline.hpp.
  *
@@ -50,6 +50,7 @@
  *      5  second stream (k_window_long): strings of up to 128 bases   legacy  16 /  8 bit       1
  *     13  last stage, shallow and deep (layout in device memory)      gw      16 / 16 bit       no LDS
  *     14  last stage, wide batches (layout in device memory)          gw      16 / 16 bit       no LDS
+ *     15  very deep stage, shallow and deep: 251 ... 1000 strings     gw      16 / 16 bit       no LDS
  *
  * processWindowFast returns
  * FW_NEXT when a window overflows a tier (flags say what overflowed: 1 instances, 2 nodes, 8 candidates, 16 walk,
@@ -182,12 +183,34 @@ template<> struct FastTier<12> { typedef uint16_t id_t; typedef uint16_t sid_t; 
 //  - reverse pool: 4096 paths in 256 chunks of 16 (8 bit chunk ids kept: tier 3 has 256 chunks of 8, so an enumeration needs at most as many chunks here);
 //  - 16 bit weight offsets and task offsets kept: 16384 weight records per direction, at most 65535 (stretch, direction, position) tasks per traversal;
 //  - more than 4094 nodes: the stretch sort key takes 13 bit node fields and a 12 bit stretch number (FastEngine: KF, QB).
-// Windows of more than 250 strings, wider than 127 bases or with a string of more than 128 bases still go to the generic engine.
+// Windows of more than 250 strings go on to tier 15; wider than 127 bases or with a string of more than 128 bases they still go to the generic engine.
 template<> struct FastTier<13> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 2000, gw = 1, wcapg = 16384, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 250, precap = 16384, ncap = 4096, scap = 2048, lcap = 8192, wcap = 16384, rccap = 4096, fcap = 1024, siqcap = 512, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 4096, wide = 0, mins = 0, gmem = 1 }; };
 template<> struct FastTier<14> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 1000, gw = 1, wcapg = 16384, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 250, precap = 16384, ncap = 6144, scap = 1024, lcap = 8192, wcap = 16384, rccap = 4096, fcap = 2048, siqcap = 512, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 4096, wide = 1, mins = 0, gmem = 1 }; };
+// tier 15: the VERY DEEP stage, behind the last stage and in front of the generic engine (tier_pipeline.hpp: ID_VDEEP): windows of 251 ... 1000 strings
+// (a repeat pile of several hundred overlaps), which every other tier refuses at its string count and the generic engine runs at a handful of
+// wavefronts (its arena is 200 MB per wavefront at depth 1000).  Tier 13's graph, pool, weight and interval capacities with 1000 strings and 65536
+// k-mer instances (FastLds<CT>::icap = 4 x precap: the instances are split by their first symbol into four ranges, each sorted on its own with the sort
+// of 16384 keys that tier 13 has -- precap stays the capacity of one sort); mins = 250: what tier 13 could have held is passed on as it came.  What a string count above 256 widens (FastLds<CT>::wides, all
+// other tiers keep their fields bit for bit):
+//  - compact string list of the instance generation: 10 bit string id | 16 bit first slot (4 x 1000 bytes <= the 65536 bytes of irpos);
+//  - node frequency: 16 bits, capped at fqmax = 1023 -- a k-mer seen more often sets overflow bit 2 and the window goes on, nothing wraps;
+//  - node weight: at most 1023 table words of < 2^32, so < 2^42 (10 bit high part); a feasible stretch has at most nrows <= 64 nodes, so < 2^48
+//    (16 bit high part, as before): the reverse record packs 16 + 10 bits into its third word, the forward record (16 + 10 + 10 = 36 bits) becomes
+//    32 bytes of three 64 bit words; path weights (rc_w, f_w, score intervals, candidates) are 64 bit sums of at most FSEQCAP stretches, < 2^54;
+//  - first instance of a node (nps): 32 bits, 1000 strings carry up to 65536 instances;
+//  - the 16 chunks of 64 strings of the instance generation are walked twice (count, then place) instead of being kept in 48 registers;
+//  - key tables (mfirst, mlast, lastk) of 1024 entries, 16000 candidate error bytes.
+// One capacity is not tier 13's: 32768 weight records per direction instead of 16384 (the 16 bit weight offsets hold that).  At k = 8 a window of
+// 700 strings has a graph of 2100 nodes in 1200 stretches at filter frequency 2, and 24 of the 197 windows of such a pile have more than 16384
+// feasible (stretch, position) pairs in one direction (emulation, tests/vdeep_cases.py shape D); the slab is device memory, the records cost 1.5 MB.
+template<> struct FastTier<15> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 2000, gw = 1, wcapg = 32768, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 1000, precap = 16384, ncap = 4096, scap = 2048, lcap = 8192, wcap = 32768, rccap = 4096, fcap = 1024, siqcap = 512, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 4096, wide = 0, mins = 250, gmem = 1 }; };
+
+static_assert(FastTier<15>::mins == VDEEP_MINS && FastTier<13>::maxs == VDEEP_MINS,"the very deep stage takes what the last stage refuses at its string count");
 
 HDEV constexpr uint32_t fcpow2(uint32_t v) { uint32_t p = 1; while ( p < v ) p <<= 1; return p; }
 HDEV constexpr uint32_t fcmax(uint32_t a, uint32_t b) { return a > b ? a : b; }
+template<bool W, typename A, typename B> struct FWideSel { typedef A type; };
+template<typename A, typename B> struct FWideSel<false,A,B> { typedef B type; };
 
 /*
  * LDS layout of one wavefront.  FLD(name,type,count,start) declares an array at byte offset `start` (a constant
@@ -207,6 +230,8 @@ struct FastLds<CT,false>
 {
 	LDSQ uint8_t * base;
 	static constexpr uint32_t keycap = fcpow2(CT::maxs < 2 ? 2 : CT::maxs);
+	static constexpr bool wides = false; static constexpr uint32_t fqmax = 255u, icap = CT::precap;      // (more than 256 strings: gw layout only)
+	static_assert(CT::maxs <= 256,"the legacy layout has 8 bit node frequencies and string ids");
 	static_assert((CT::precap & (CT::precap-1)) == 0,"precap must be a power of two: the bitonic sorts pad to one");
 	static_assert(sizeof(typename CT::id_t) > 1 || (CT::fcap <= 256 && CT::rccap <= 256),"pool slots are recorded as id_t (pout)");
 	static_assert(CT::blcap <= 128 && (CT::blcap & 7) == 0,"base length buckets: two 64 bit occupancy words, cleared 8 at a time");
@@ -416,6 +441,15 @@ struct FastLds<CT,true>
 	static_assert(CT::lstr == 64 || CT::lstr == 128,"the gw layout holds strings of up to 64 bases in one word per pattern mask, of up to 128 in two (round 6)");
 	static constexpr uint32_t pw = CT::lstr/64;
 	typedef typename CT::sid_t sid_t;      // stretch ids: 8 bits (at most 250 stretches) or 16 bits
+	// more than 256 strings (tier 15): 16 bit node frequencies capped at fqmax, 32 bit first-instance offsets, a 32 byte forward weight record
+	static constexpr bool wides = CT::maxs > 256;
+	static constexpr uint32_t fqmax = wides ? 1023u : 255u;
+	// k-mer instances the layout holds: precap, the capacity of one instance sort -- with more than 256 strings four such ranges (buildInstances)
+	static constexpr uint32_t icap = wides ? 4u*CT::precap : CT::precap;
+	typedef typename FWideSel<wides,uint16_t,uint8_t>::type nfreq_t;
+	typedef typename FWideSel<wides,uint32_t,uint16_t>::type nps_t;
+	static_assert(fqmax <= (1u << (8u*sizeof(nfreq_t))) - 1u,"a node frequency holds fqmax");
+	static_assert(icap <= (sizeof(nps_t) == 2 ? 65535u : 0xFFFFFFFFu),"nps[nn] = npre <= icap must fit a first-instance offset");
 	// ---- P ----
 	FLD(slen,uint8_t,CT::maxs,0)
 	static constexpr uint32_t supcap = CT::wide ? static_cast<uint32_t>(FSUPCAPW) : static_cast<uint32_t>(FSUPCAP);
@@ -442,10 +476,10 @@ struct FastLds<CT,true>
 	// (round 5: no string array -- the pattern masks ARE the strings: symbol c at position p of string j <=> bit p of peq[4*j+c]; they are
 	// built by ballots while the bases are gathered and the k-mers are cut from them; the 64 bytes per string went into the node tables)
 	FLD(peq,uint64_t,CT::maxs*4*pw,sbase)
-	FLD(ipos,uint8_t,CT::precap,e_peq)
-	FLD(irpos,uint8_t,CT::precap,e_ipos)
-	FLD(nps,uint16_t,CT::ncap+1,e_irpos)
-	FLD(nfreq,uint8_t,CT::ncap,e_nps)
+	FLD(ipos,uint8_t,icap,e_peq)
+	FLD(irpos,uint8_t,icap,e_ipos)
+	FLD(nps,nps_t,CT::ncap+1,e_irpos)
+	FLD(nfreq,nfreq_t,CT::ncap,e_nps)
 	FLD(succ0,uint16_t,CT::ncap,e_nfreq)
 	FLD(sinfo,uint16_t,CT::ncap,e_succ0)
 	FLD(nrange,uint32_t,CT::ncap,e_sinfo)
@@ -496,7 +530,7 @@ struct FastLds<CT,true>
 	static_assert(e_rchb <= o_pout,"reverse chunk lists must fit the per first k-mer tables");
 	static constexpr uint32_t ubase = fcmax(send,(upool + 15u) & ~15u);
 	// ---- overlay A: build phase ----
-	FLD(pre,uint64_t,CT::precap,ubase)
+	FLD(pre,uint64_t,icap,ubase)
 	FLD(lastk,uint64_t,keycap,e_pre)
 	static constexpr uint32_t uA = e_lastk;
 	// ---- overlay B: traversal ----
@@ -563,7 +597,9 @@ struct FastLds<CT,true>
 	HDEV LDSQ uint16_t * xsid() const { return reinterpret_cast<LDSQ uint16_t *>(base + xbase); }
 	HDEV LDSQ uint8_t * xspos() const { return reinterpret_cast<LDSQ uint8_t *>(base + xbase + 2u*CT::ncap + 8u); }
 	HDEV LDSQ uint8_t * xreach() const { return reinterpret_cast<LDSQ uint8_t *>(base + xbase); }
-	static constexpr uint32_t uend = fcmax(uA,uB);
+	// (more than 256 strings: the instances as they are generated, before they are split into the four sorted ranges of `pre`; behind both overlays)
+	FLD(pregen,uint64_t,(wides ? icap : 0u),((fcmax(uA,uB) + 15u) & ~15u))
+	static constexpr uint32_t uend = wides ? e_pregen : fcmax(uA,uB);
 	// scratch behind the build overlay (gap filling): small in this layout, a window that needs more goes to the next tier
 	FLD(gfbuf,uint64_t,(uB > uA ? (uB-uA)/8 : 0u),uA)
 	static constexpr uint32_t gfcap = uB > uA ? (uB-uA)/8 : 0u;
@@ -573,10 +609,12 @@ struct FastLds<CT,true>
 	// the stretch construction borrow the weight part
 	// (round 4) behind the spill image: the sorted k-mer instances and last k-mers of the current k, saved before the first
 	// traversal of a pass overwrites overlay A, so that the next filter frequency pass reloads them instead of sorting again
-	static constexpr uint32_t g_wF = 0, g_wR = 16u*CT::wcapg, g_spill = 32u*CT::wcapg, g_inst = ((32u*CT::wcapg + sbytes + 255u) & ~255u),
-		g_bytes = g_inst + (((CT::precap + keycap)*8u + 255u) & ~255u);
-	static_assert((o_pre & 15u) == 0 && (CT::precap & 1u) == 0 && (keycap & 1u) == 0,"instance arrays are saved 16 bytes at a time");
-	static constexpr uint32_t xnslot = (32u*CT::wcapg) / 128u;
+	// (wides: the forward record is 32 bytes -- three 64 bit weights --, the reverse record stays 16)
+	static constexpr uint32_t recFbytes = wides ? 32u : 16u;
+	static constexpr uint32_t g_wF = 0, g_wR = recFbytes*CT::wcapg, g_spill = (recFbytes+16u)*CT::wcapg, g_inst = ((g_spill + sbytes + 255u) & ~255u),
+		g_bytes = g_inst + (((icap + keycap)*8u + 255u) & ~255u);
+	static_assert((o_pre & 15u) == 0 && (icap & 1u) == 0 && (keycap & 1u) == 0,"instance arrays are saved 16 bytes at a time");
+	static constexpr uint32_t xnslot = g_spill / 128u;
 	// device-memory tiers (CT::gmem): this layout itself sits behind the instance image, g_total bytes per workgroup in all
 	static constexpr uint32_t g_layout = g_bytes, g_total = CT::gmem ? g_bytes + ((((uend + 15u) & ~15u) + 255u) & ~255u) : g_bytes;
 };
@@ -586,7 +624,7 @@ template<typename CT>
 HDEV FastCaps fastCapsOf(uint32_t const nrows, uint32_t const nsup)
 {
 	FastCaps C;
-	C.maxs = CT::maxs; C.precap = CT::precap; C.ncap = CT::ncap; C.scap = CT::scap; C.lcap = CT::lcap; C.wcap = CT::wcap; C.rccap = CT::rccap;
+	C.maxs = CT::maxs; C.precap = FastLds<CT>::icap; C.ncap = CT::ncap; C.scap = CT::scap; C.lcap = CT::lcap; C.wcap = CT::wcap; C.rccap = CT::rccap;
 	C.fcap = CT::fcap; C.siqcap = CT::siqcap; C.blcap = CT::blcap;
 	C.nrows = nrows; C.nsup = nsup;
 	C.ldsbytes = FastLds<CT>::bytes(nrows,nsup);
@@ -794,10 +832,29 @@ struct FastEngine
 #else
 		enum : bool { GENMARKS = true };
 #endif
-		static_assert(4u*CT::maxs <= CT::precap && CT::maxs <= 256 && CT::precap <= (1u<<24),"compact string list: string | first slot << 8, in the bytes of irpos");
+		// compact string list entry: string | first slot << CLB.  8 bit string ids and 24 bit slots; more than 256 strings: 10 bit ids, 16 bit slots
+		// (a first slot is below npre <= 65536)
+		enum : bool { WIDES = FastLds<CT>::wides };
+		enum : uint32_t { CLB = WIDES ? 10u : 8u, CLMASK = (1u << CLB) - 1u };
+		static_assert(4u*CT::maxs <= FastLds<CT>::icap && CT::maxs <= (1u << CLB) && FastLds<CT>::icap <= (1u << (WIDES ? 16 : 24)),"compact string list: string | first slot << CLB, in the bytes of irpos");
+		static_assert(!WIDES || GENMARKS,"the two-pass generation of more than 256 strings needs the marks");
 		LDSQ uint8_t * const marks = L.ipos();                                             // free until buildNodes writes the positions
 		LDSQ uint32_t * const clist = reinterpret_cast<LDSQ uint32_t *>(L.irpos());
-		uint32_t nkc[NCH], offc[NCH], rkc[NCH]; uint32_t base = 0, nl = 0;
+		// (more than 256 strings: 16 chunks would be 48 live registers -- the chunks are walked twice instead, first for the instance count, then,
+		// the marks cleared, for the places; a chunk costs a length byte and two scans)
+		enum { NCHR = WIDES ? 1 : NCH };
+		uint32_t nkc[NCHR], offc[NCHR], rkc[NCHR]; uint32_t base = 0, nl = 0;
+		if constexpr ( WIDES )
+		{
+			for ( uint32_t c = 0; c*WSZ < mao; ++c )
+			{
+				uint32_t const j = c*WSZ + lane;
+				uint32_t const len = j < mao ? L.slen()[j] : 0u;
+				base += wv_sum(len >= k ? (len-k+1) : 0u);
+			}
+		}
+		else
+		{
 		#pragma unroll
 		for ( int c = 0; c < NCH; ++c )
 		{
@@ -808,17 +865,35 @@ struct FastEngine
 			offc[c] = base + pre; base += tot;
 			uint32_t t2; rkc[c] = nl + wv_scan_flag(nkc[c] != 0,t2); nl += t2;
 		}
+		}
 		npre = base;
 		nlast = 0;
-		if ( npre > CT::precap ) { over(1); npre = 0; return; }
+		if ( npre > FastLds<CT>::icap ) { over(1); npre = 0; return; }
 		SITE_T0
-		if constexpr ( GENMARKS )
+		if constexpr ( WIDES )
+		{
+			for ( uint32_t i = 8*lane; i < npre; i += 8*WSZ ) *reinterpret_cast<LDSQ uint64_t *>(marks + i) = 0;
+			wv_sync();
+			base = 0;
+			for ( uint32_t c = 0; c*WSZ < mao; ++c )
+			{
+				uint32_t const j = c*WSZ + lane;
+				uint32_t const len = j < mao ? L.slen()[j] : 0u;
+				uint32_t const nk = len >= k ? (len-k+1) : 0u;
+				uint32_t tot; uint32_t const pre = wv_scan_excl(nk,tot);
+				uint32_t t2; uint32_t const rk = nl + wv_scan_flag(nk != 0,t2);
+				if ( nk ) { marks[base+pre] = 1; clist[rk] = j | ((base+pre) << CLB); }
+				base += tot; nl += t2;
+			}
+			wv_sync();
+		}
+		else if constexpr ( GENMARKS )
 		{
 			for ( uint32_t i = 8*lane; i < npre; i += 8*WSZ ) *reinterpret_cast<LDSQ uint64_t *>(marks + i) = 0;      // (precap is a multiple of 8)
 			wv_sync();
 			#pragma unroll
 			for ( int c = 0; c < NCH; ++c )
-				if ( nkc[c] ) { marks[offc[c]] = 1; clist[rkc[c]] = (c*WSZ + lane) | (offc[c] << 8); }
+				if ( nkc[c] ) { marks[offc[c]] = 1; clist[rkc[c]] = (c*WSZ + lane) | (offc[c] << CLB); }
 			wv_sync();
 		}
 		uint32_t cum = 0;
@@ -832,7 +907,7 @@ struct FastEngine
 				uint32_t tot; uint32_t const before = wv_scan_flag(mk,tot);
 				lo = cum + before + (mk ? 1u : 0u);      // strings with k-mers that begin at or before slot t (slot 0 begins one)
 				cum += tot;
-				if ( t < npre ) { uint32_t const e = clist[lo-1]; j = e & 0xFFu; oj = e >> 8; }
+				if ( t < npre ) { uint32_t const e = clist[lo-1]; j = e & CLMASK; oj = e >> CLB; }
 			}
 			else
 			{
@@ -880,7 +955,7 @@ struct FastEngine
 					for ( uint32_t q = 0; q < 16; ++q ) { uint32_t const c = sp[q]; v = q < k ? ((v<<2) | c) : v; }
 				}
 				uint64_t const word = (static_cast<uint64_t>(v)<<32) | (static_cast<uint64_t>(i)<<16) | j;
-				L.pre()[t] = word;
+				if constexpr ( WIDES ) L.pregen()[t] = word; else L.pre()[t] = word;
 				if ( i + k == L.slen()[j] ) L.lastk()[lo-1] = word;
 			}
 		}
@@ -891,6 +966,41 @@ struct FastEngine
 		SITE(31)      // buildInstances: generation of the k-mer instances (lane = instance)
 		wv_sort_keys<FastLds<CT>::keycap>(L.lastk(),nlast);
 		SITE(32)      // buildInstances: sort of the last k-mers
+		if constexpr ( WIDES )
+		{
+			// Up to 4 x precap instances: split by the first symbol of the k-mer (the two highest bits of the key) into four ranges, range r behind
+			// range r-1, and sort every range on its own with the sort of precap keys; the concatenation is the sorted array.  A range of more than
+			// precap keys (a window of one symbol) sends the window on like a full instance array.
+			uint32_t const sh = 32u + 2u*k - 2u;
+			uint32_t cnt0 = 0, cnt1 = 0, cnt2 = 0, cnt3 = 0;
+			for ( uint32_t t0 = 0; t0 < npre; t0 += WSZ )
+			{
+				uint32_t const t = t0 + lane; bool const a = t < npre;
+				uint32_t const b = a ? static_cast<uint32_t>(L.pregen()[t] >> sh) & 3u : 4u;
+				cnt0 += dacc_popc64(wv_ballot(b == 0)); cnt1 += dacc_popc64(wv_ballot(b == 1)); cnt2 += dacc_popc64(wv_ballot(b == 2)); cnt3 += dacc_popc64(wv_ballot(b == 3));
+			}
+			if ( cnt0 > CT::precap || cnt1 > CT::precap || cnt2 > CT::precap || cnt3 > CT::precap ) { over(1); npre = 0; nlast = 0; return; }
+			uint32_t const o1 = cnt0, o2 = o1 + cnt1, o3 = o2 + cnt2;
+			uint32_t p0 = 0, p1 = o1, p2 = o2, p3 = o3;
+			uint64_t const ltm = wv_lanemask_lt();
+			for ( uint32_t t0 = 0; t0 < npre; t0 += WSZ )
+			{
+				uint32_t const t = t0 + lane; bool const a = t < npre;
+				uint64_t const w = a ? L.pregen()[t] : 0ull;
+				uint32_t const b = a ? static_cast<uint32_t>(w >> sh) & 3u : 4u;
+				uint64_t const m0 = wv_ballot(b == 0), m1 = wv_ballot(b == 1), m2 = wv_ballot(b == 2), m3 = wv_ballot(b == 3);
+				uint64_t const mine = b == 0 ? m0 : (b == 1 ? m1 : (b == 2 ? m2 : m3));
+				uint32_t const at = (b == 0 ? p0 : (b == 1 ? p1 : (b == 2 ? p2 : p3))) + dacc_popc64(mine & ltm);
+				if ( a ) L.pre()[at] = w;
+				p0 += dacc_popc64(m0); p1 += dacc_popc64(m1); p2 += dacc_popc64(m2); p3 += dacc_popc64(m3);
+			}
+			wv_sync();
+			wv_sort_keys<CT::precap>(L.pre(),cnt0);
+			wv_sort_keys<CT::precap>(L.pre()+o1,cnt1);
+			wv_sort_keys<CT::precap>(L.pre()+o2,cnt2);
+			wv_sort_keys<CT::precap>(L.pre()+o3,cnt3);
+		}
+		else
 		wv_sort_keys<CT::precap,(CT::precap == 2048 && CT::ncap == 256)>(L.pre(),npre);      // 2048 keys in registers: the deep tier (FastTier<4>) only
 		SITE(33)      // buildInstances: sort of the instances (register bitonic network)
 	}
@@ -915,7 +1025,7 @@ struct FastEngine
 			if ( keep )
 			{
 				uint32_t const z = base+pre;
-				if ( z < CT::ncap ) { L.nv()[z] = static_cast<uint32_t>(L.pre()[i]>>32); L.nps()[z] = i; L.nfreq()[z] = (e-i) > 255 ? 255 : (e-i); if ( (e-i) > 255 ) over(2); }
+				if ( z < CT::ncap ) { L.nv()[z] = static_cast<uint32_t>(L.pre()[i]>>32); L.nps()[z] = i; L.nfreq()[z] = (e-i) > FastLds<CT>::fqmax ? FastLds<CT>::fqmax : (e-i); if ( (e-i) > FastLds<CT>::fqmax ) over(2); }
 			}
 			base += tot;
 		}
@@ -1136,6 +1246,8 @@ struct FastEngine
 			if ( ok && npre+base+pre < CT::precap ) L.pre()[npre+base+pre] = (cv<<32) | (static_cast<uint64_t>(pos)<<16) | seqid;
 			base += tot;
 		}
+		// (the whole array is sorted again below with the sort of precap keys: a window of more than 256 strings and more than precap instances that comes
+		// down to gap filling goes on to the generic engine here)
 		if ( npre + base > CT::precap ) { over(1); return; }
 		npre += base;
 		wv_sync();
@@ -1709,8 +1821,16 @@ struct FastEngine
 		FEAS_DUMP()
 		wv_sync();
 	}
-	// weights of feasible (stretch, position) entry i.  A node weight is a sum of at most 255 table words (< 2^40), a
-	// feasible stretch has at most nrows <= 64 nodes (< 2^46)
+	// weights of feasible (stretch, position) entry i.  A node weight is a sum of at most fqmax table words of < 2^32: 255 of them stay below 2^40
+	// (8 bit high part), 1023 below 2^42 (10 bits, the tier of more than 256 strings); a feasible stretch has at most nrows <= 64 nodes: < 2^46 / 2^48
+	// (16 bit high part either way).  Everything summed from these -- link weights, path weights rc_w / f_w, score intervals, candidates -- is a 64 bit
+	// word: a path has at most FSEQCAP stretches (< 2^54).
+	enum : uint32_t { FQMAX = FastLds<CT>::fqmax, NWHB = FQMAX <= 255u ? 8u : 10u, NWHMASK = (1u << NWHB) - 1u };
+	static_assert((static_cast<uint64_t>(FQMAX)*0xFFFFFFFFull) >> (32u+NWHB) == 0,"high part of a node weight: fqmax table words");
+	static_assert((64ull*static_cast<uint64_t>(FQMAX)*0xFFFFFFFFull) >> 48 == 0,"high part of a stretch weight: 64 nodes, 16 bits");
+	static_assert(16u + NWHB <= 32u,"reverse record: both high parts in its third word");
+	static_assert(FastLds<CT>::wides || 16u + 2u*NWHB <= 32u,"forward record: three high parts in its fourth word, or the 32 byte record");
+	struct G8 { G4 a, b; };      // the 32 byte forward record of more than 256 strings: w, w1 | wl, unused (two 16 byte loads)
 	// One record per feasible (stretch, position) entry.  Forward: whole stretch (w), its first node at the start position
 	// (w1), its last node at the end position (wl); reverse: whole stretch and its last node (= first in reverse direction).
 	// gw tiers: 16 byte records in the workgroup's global slab (one load per lookup); legacy tiers: split LDS arrays.
@@ -1719,7 +1839,12 @@ struct FastEngine
 	DEV WF recF(uint32_t const i) const
 	{
 		WF r;
-		if constexpr ( GW )
+		if constexpr ( GW && FastLds<CT>::wides )
+		{
+			G8 const v = reinterpret_cast<G8 const *>(gslab + FastLds<CT>::g_wF)[i];
+			r.w = v.a.x | (static_cast<uint64_t>(v.a.y)<<32); r.w1 = v.a.z | (static_cast<uint64_t>(v.a.w)<<32); r.wl = v.b.x | (static_cast<uint64_t>(v.b.y)<<32);
+		}
+		else if constexpr ( GW )
 		{
 			G4 const v = reinterpret_cast<G4 const *>(gslab + FastLds<CT>::g_wF)[i];
 			r.w = v.x | (static_cast<uint64_t>(v.w & 0xFFFFu)<<32); r.w1 = v.y | (static_cast<uint64_t>((v.w>>16)&0xFFu)<<32); r.wl = v.z | (static_cast<uint64_t>(v.w>>24)<<32);
@@ -1738,7 +1863,7 @@ struct FastEngine
 		if constexpr ( GW )
 		{
 			G4 const v = reinterpret_cast<G4 const *>(gslab + FastLds<CT>::g_wR)[i];
-			r.w = v.x | (static_cast<uint64_t>(v.z & 0xFFFFu)<<32); r.w1 = v.y | (static_cast<uint64_t>((v.z>>16)&0xFFu)<<32);
+			r.w = v.x | (static_cast<uint64_t>(v.z & 0xFFFFu)<<32); r.w1 = v.y | (static_cast<uint64_t>((v.z>>16)&NWHMASK)<<32);
 		}
 		else
 		{
@@ -1749,7 +1874,13 @@ struct FastEngine
 	}
 	DEV void putF(uint32_t const o, uint64_t const sum, uint64_t const f1, uint64_t const fl) const
 	{
-		if constexpr ( GW )
+		if constexpr ( GW && FastLds<CT>::wides )
+		{
+			G8 v; v.a.x = static_cast<uint32_t>(sum); v.a.y = static_cast<uint32_t>(sum>>32); v.a.z = static_cast<uint32_t>(f1); v.a.w = static_cast<uint32_t>(f1>>32);
+			v.b.x = static_cast<uint32_t>(fl); v.b.y = static_cast<uint32_t>(fl>>32); v.b.z = 0; v.b.w = 0;
+			reinterpret_cast<G8 *>(gslab + FastLds<CT>::g_wF)[o] = v;
+		}
+		else if constexpr ( GW )
 		{
 			G4 v; v.x = static_cast<uint32_t>(sum); v.y = static_cast<uint32_t>(f1); v.z = static_cast<uint32_t>(fl);
 			v.w = (static_cast<uint32_t>(sum>>32)&0xFFFFu) | ((static_cast<uint32_t>(f1>>32)&0xFFu)<<16) | ((static_cast<uint32_t>(fl>>32)&0xFFu)<<24);
@@ -1767,7 +1898,7 @@ struct FastEngine
 		if constexpr ( GW )
 		{
 			G4 v; v.x = static_cast<uint32_t>(rsum); v.y = static_cast<uint32_t>(r1);
-			v.z = (static_cast<uint32_t>(rsum>>32)&0xFFFFu) | ((static_cast<uint32_t>(r1>>32)&0xFFu)<<16); v.w = 0;
+			v.z = (static_cast<uint32_t>(rsum>>32)&0xFFFFu) | ((static_cast<uint32_t>(r1>>32)&NWHMASK)<<16); v.w = 0;
 			reinterpret_cast<G4 *>(gslab + FastLds<CT>::g_wR)[o] = v;
 		}
 		else
@@ -3125,7 +3256,7 @@ struct FastEngine
 			LDSQ G4 const * const sp = reinterpret_cast<LDSQ G4 const *>(L.pre());
 			LDSQ G4 const * const sl = reinterpret_cast<LDSQ G4 const *>(L.lastk());
 			for ( uint32_t i = lane; i < (npre+1)/2; i += WSZ ) dst[i] = sp[i];
-			for ( uint32_t i = lane; i < (nlast+1)/2; i += WSZ ) dst[CT::precap/2 + i] = sl[i];
+			for ( uint32_t i = lane; i < (nlast+1)/2; i += WSZ ) dst[FastLds<CT>::icap/2 + i] = sl[i];
 		}
 	}
 	// hand-over slots (FastBatch::hand): slot = number + 1, 0 = none.  A window keeps its slot from tier to tier (the instances of a k
@@ -3150,7 +3281,7 @@ struct FastEngine
 		uint64_t const * const src = FB.hand + static_cast<uint64_t>(hslot-1)*FB.handwords;
 		uint64_t const h0 = src[0];
 		uint32_t const n = static_cast<uint32_t>(h0), nl = static_cast<uint32_t>(h0>>32);
-		if ( n > CT::precap || nl > FastLds<CT>::keycap || src[1] != k ) return false;      // (cannot happen between the tiers of one batch)
+		if ( n > FastLds<CT>::icap || nl > FastLds<CT>::keycap || src[1] != k ) return false;      // (cannot happen between the tiers of one batch)
 		npre = n; nlast = nl;
 		FSTAT_ADD(31,1);
 		uint32_t const po = 2, lo = 2 + ((n+1)&~1u);
@@ -3170,7 +3301,7 @@ struct FastEngine
 			LDSQ G4 * const dl = reinterpret_cast<LDSQ G4 *>(L.lastk());
 			wv_sync();
 			for ( uint32_t i = lane; i < (npre+1)/2; i += WSZ ) dp[i] = src[i];
-			for ( uint32_t i = lane; i < (nlast+1)/2; i += WSZ ) dl[i] = src[CT::precap/2 + i];
+			for ( uint32_t i = lane; i < (nlast+1)/2; i += WSZ ) dl[i] = src[FastLds<CT>::icap/2 + i];
 			wv_sync();
 		}
 	}

@@ -1,5 +1,5 @@
 /*
- * The window kernels of libdaccord_hip.so, one translation unit each (k_fast_<tier>.hip for the fourteen tiers of DACC_KERNEL_TIERS,
+ * The window kernels of libdaccord_hip.so, one translation unit each (k_fast_<tier>.hip for the fifteen tiers of DACC_KERNEL_TIERS,
  * tier_pipeline.hpp -- the table of the tiers is at the head of fast_window.hpp --, and k_generic.hip, which also holds tier 5): they are
  * 150-260 KB of gfx950 code apiece and took 25 minutes to compile one after the other inside capi.hip; as separate objects they compile
  * side by side (daccord_amd/build.py).  This header holds what the units share: the work distribution, the kernel template of the LDS tiers (defined

@@ -200,8 +200,15 @@ typedef struct dacc_timing {
 	/* the last stage: k_window_fast<13> (wide batches: <14>), the tier whose layout lives in device memory, behind the slots and in front of k_window; not a part of tier_ms[] */
 	float last_ms;           /* its kernel; 0 if it did not run (DACC_LAST_TIER=0, DACC_LAST_AS_SLOT2=1, no slot ran, no memory for its slab) */
 	uint32_t last_windows;   /* windows that finished in it */
-	uint32_t last_out;       /* windows it handed on to k_window (more than 250 strings, w = 128, a string of more than 128 bases, a table beyond its capacities) */
+	uint32_t last_out;       /* windows it handed on (more than 250 strings, w = 128, a string of more than 128 bases, a table beyond its capacities): what k_window ran --
+	                            where the very deep stage ran, what that stage read (k_window then ran last_out - vdeep_windows) */
 	uint32_t pad4_;
+	/* the very deep stage: k_window_fast<15> (layout in device memory, windows of 251 ... 1000 strings), behind the last stage and in front of k_window; launched only in a
+	   shallow or deep batch whose deepest window has more than 250 strings; not a part of tier_ms[] */
+	float vdeep_ms;          /* its kernel; 0 if it did not run (no window of more than 250 strings in the batch, a wide batch, DACC_VDEEP_TIER=0, DACC_VDEEP_AS_SLOT2=1, no slot ran, no memory for its slab) */
+	uint32_t vdeep_windows;  /* windows of more than 250 strings that finished in it */
+	uint32_t vdeep_out;      /* windows of more than 250 strings it handed on to k_window (more than 1000 strings, a k-mer seen more than 1023 times, a table beyond its capacities) */
+	uint32_t pad5_;
 } dacc_timing;
 #define DACC_TIMING_SIZE_V1 128
 /* dacc_last_timing fills the first DACC_TIMING_SIZE_V1 bytes only (the record as it was when the call was introduced: a caller built against
