@@ -78,6 +78,12 @@ DEV void heap_popvoid(T * H, uint32_t & f)
 	if ( l < f && !cmp(H[i].w,H[l].w) ) { T const t = H[i]; H[i] = H[l]; H[l] = t; }
 }
 
+// test harness hook (tests/sortprobe): the sort probe defines it to learn that arpSort took libstdc++'s heapsort fallback; it is empty
+// everywhere else, the kernels included
+#if !defined(DACC_ARP_FALLBACK_NOTE)
+#define DACC_ARP_FALLBACK_NOTE()
+#endif
+
 // ---------- the per-wavefront engine ----------
 struct WindowEngine
 {
@@ -779,8 +785,8 @@ struct WindowEngine
 		return true;
 	}
 
-	// libstdc++ std::sort (introsort + final insertion sort) on the ARP index array with
-	// comparator (front, baselen) -- reproduces the permutation of DebruijnGraph.hpp:3742 exactly
+	// libstdc++ std::sort (introsort with its heapsort fallback + final insertion sort) on the ARP index array with
+	// comparator (front, baselen) -- reproduces the permutation of DebruijnGraph.hpp:3742 exactly, tied keys included
 	DEV bool arpLess(int32_t const a, int32_t const b) const
 	{
 		uint32_t const fa = A.rp_front[a], fb = A.rp_front[b];
@@ -808,6 +814,46 @@ struct WindowEngine
 			else arpUnguardedLinearInsert(i);
 		}
 	}
+	// libstdc++'s heapsort fallback of introsort, std::__partial_sort(first,last,last): __make_heap, then __sort_heap, with
+	// __adjust_heap / __push_heap in libstdc++'s order of comparisons (the permutation of tied keys is part of the result)
+	DEV void arpAdjustHeap(int32_t * first, int64_t hole, int64_t const len, int32_t const val)
+	{
+		int64_t const top = hole;
+		int64_t child = hole;
+		while ( child < (len-1)/2 )
+		{
+			child = 2*(child+1);
+			if ( arpLess(first[child],first[child-1]) ) --child;
+			first[hole] = first[child]; hole = child;
+		}
+		if ( (len & 1) == 0 && child == (len-2)/2 )
+		{
+			child = 2*(child+1);
+			first[hole] = first[child-1]; hole = child-1;
+		}
+		// __push_heap
+		int64_t parent = (hole-1)/2;
+		while ( hole > top && arpLess(first[parent],val) ) { first[hole] = first[parent]; hole = parent; parent = (hole-1)/2; }
+		first[hole] = val;
+	}
+	DEV void arpHeapSort(int32_t * first, int32_t * last)
+	{
+		int64_t const len = last-first;
+		if ( len < 2 ) return;
+		// __make_heap
+		for ( int64_t parent = (len-2)/2; ; --parent )
+		{
+			arpAdjustHeap(first,parent,len,first[parent]);
+			if ( parent == 0 ) break;
+		}
+		// __sort_heap: __pop_heap(first,last,last) for a shrinking last
+		while ( last-first > 1 )
+		{
+			--last;
+			int32_t const val = *last; *last = *first;
+			arpAdjustHeap(first,0,last-first,val);
+		}
+	}
 	DEV void arpSort(int32_t * first, int32_t * last)
 	{
 		if ( first == last ) return;
@@ -822,7 +868,9 @@ struct WindowEngine
 			int32_t * f = stF[sp]; int32_t * l = stL[sp]; int d = stD[sp];
 			while ( l-f > 16 )
 			{
-				if ( d == 0 ) { setOverflow(1024); return; } // heapsort fallback of introsort: not reproduced, fail loudly
+				// depth limit 2*floor(log2 n) of __introsort_loop reached: this range is finished by libstdc++'s heapsort, the stack goes
+				// on with the other ranges (heavily tied keys of low-complexity sequence drive median-of-3 here; random genomes never did)
+				if ( d == 0 ) { DACC_ARP_FALLBACK_NOTE(); arpHeapSort(f,l); break; }
 				--d;
 				// __unguarded_partition_pivot
 				int32_t * mid = f + (l-f)/2;
@@ -987,21 +1035,26 @@ struct WindowEngine
 	// candidate text of (forward path, reverse path) (decodePathPair :4267-4300); returns new conso or ~0 on overflow
 	DEV uint32_t decodePathPair(int32_t const path, int32_t const rp, uint32_t o)
 	{
-		// forward stretches root -> leaf
-		int32_t chain[64]; uint32_t cl = 0;
-		for ( int32_t q = path; q >= 0; q = A.p_parent[q] ) { if ( cl >= 64 ) { setOverflow(4096); return ~0u; } chain[cl++] = A.p_stretch[q]; }
-		uint32_t need = k;
-		for ( uint32_t i = 0; i < cl; ++i ) need += A.sslen[chain[i]]-1;
+		// forward stretches root -> leaf.  The path is a leaf -> root list of any number of stretches (low-complexity sequence at w = 128
+		// makes paths of more than 64), so its text is written from its end backwards instead of through a list of its stretches.
+		uint32_t flen = 0;
+		for ( int32_t q = path; q >= 0; q = A.p_parent[q] ) flen += A.sslen[A.p_stretch[q]]-1;
+		uint32_t need = k + flen;
 		for ( int32_t q = rp; q >= 0 && A.rp_len[q]; q = A.rp_parent[q] ) need += A.sslen[A.rp_stretch[q]]-1;
 		if ( o + need > C.conscap - DACC_MAXCONS_OF(P.w) ) { setOverflow(4096); return ~0u; } // the tail holds the accepted consensus
-		uint32_t const firstv = A.nv[A.sfirst[chain[cl-1]]];
-		for ( uint32_t i = 0; i < k; ++i ) A.cons[o++] = (firstv >> (2*(k-1-i))) & 3;
-		for ( uint32_t ii = 0; ii < cl; ++ii )
+		uint32_t e = o + k + flen;
+		int32_t root = path;
+		for ( int32_t q = path; q >= 0; q = A.p_parent[q] )
 		{
-			uint32_t const s = chain[cl-1-ii];
+			uint32_t const s = A.p_stretch[q];
 			int32_t const * L = A.links + A.slink[s];
-			for ( uint32_t j = 1; j < A.sslen[s]; ++j ) A.cons[o++] = A.nv[L[j]] & 3;
+			e -= A.sslen[s]-1;
+			for ( uint32_t j = 1; j < A.sslen[s]; ++j ) A.cons[e+j-1] = A.nv[L[j]] & 3;
+			root = q;
 		}
+		uint32_t const firstv = A.nv[A.sfirst[A.p_stretch[root]]];
+		for ( uint32_t i = 0; i < k; ++i ) A.cons[o++] = (firstv >> (2*(k-1-i))) & 3;
+		o += flen;
 		for ( int32_t q = rp; q >= 0 && A.rp_len[q]; q = A.rp_parent[q] )
 		{
 			uint32_t const s = A.rp_stretch[q];

@@ -55,8 +55,9 @@
  * processWindowFast returns
  * FW_NEXT when a window overflows a tier (flags say what overflowed: 1 instances, 2 nodes, 8 candidates, 16 walk,
  * 32 stretches, 64 links, 128 weights, 512 pools (0x4000 reverse cache, 0x8000 path ids, 0x10000 forward pool,
- * 0x20000 popped paths, 0x40000 score intervals), 1024 introsort depth, 2048 base length, 4096 candidate length /
- * sequence, 8192 gap filling) and FW_GENERIC for shapes the tier does not support (a window wider than it holds, a string
+ * 0x20000 popped paths, 0x40000 score intervals), 1024 introsort's depth limit reached in the replayed std::sort (the tiers
+ * stop there; the generic engine finishes such a range with libstdc++'s heapsort fallback), 2048 base length, 4096 candidate
+ * length / sequence, 8192 gap filling) and FW_GENERIC for shapes the tier does not support (a window wider than it holds, a string
  * longer than its string stride lstr: 64 or 128 bases); those go to tier 5 / the generic engine (dbg_window.hpp).
  */
 #ifndef DACC_FAST_WINDOW_HPP
@@ -2301,7 +2302,8 @@ struct FastEngine
 		}
 	}
 	// libstdc++ std::sort permutation (introsort + final insertion sort), see dbg_window.hpp arpSort; more than 16
-	// elements need the (single) explicit stack L.sstack, so only one lane at a time may sort such a block
+	// elements need the (single) explicit stack L.sstack, so only one lane at a time may sort such a block.  At introsort's depth
+	// limit the window is handed on with flag 1024: the heapsort fallback is reproduced in the generic engine only
 	DEV void arpSort(LDSQ id_t * first, LDSQ id_t * last, uint32_t const lk)
 	{
 		if ( first == last ) return;

@@ -33,6 +33,8 @@ def _load():
         _lib = C.CDLL(_SO)
         _lib.synth_generate.restype = C.c_void_p
         _lib.synth_generate.argtypes = [C.POINTER(SynthParams)]
+        _lib.synth_generate_genome.restype = C.c_void_p
+        _lib.synth_generate_genome.argtypes = [C.POINTER(SynthParams), C.c_void_p]
         _lib.synth_destroy.argtypes = [C.c_void_p]
         _lib.synth_get.argtypes = [C.c_void_p] + [C.c_void_p] * 13
     return _lib
@@ -42,8 +44,10 @@ class SynthData:
     """Host-side synthetic data set: 2-bit read store + overlaps + trace points + piles."""
 
     def __init__(self, genome_len, nreads, read_len, erate=0.15, ins_frac=0.8, del_frac=0.1333333333, sub_frac=0.0666666667,
-                 min_overlap=1000, tspace=100, seed=1, nthreads=None, aread_range=None):
-        """aread_range = (first, last): overlaps and piles only for these A reads (every read of the set is generated, B reads
+                 min_overlap=1000, tspace=100, seed=1, nthreads=None, aread_range=None, genome=None):
+        """genome: a uint8 array of genome_len 2-bit codes to draw the reads, overlaps and traces from instead of the seed's random genome
+        (low-complexity sequence, tests/lowcomplex_cases.py); without it every byte is what it always was.
+        aread_range = (first, last): overlaps and piles only for these A reads (every read of the set is generated, B reads
         are arbitrary); the records are identical to the corresponding ones of the full set."""
         lib = _load()
         p = SynthParams(genome_len, nreads, read_len, erate * ins_frac, erate * del_frac, erate * sub_frac,
@@ -51,7 +55,13 @@ class SynthData:
                         aread_range[0] if aread_range else 0, aread_range[1] if aread_range else 0)
         self.p_ins, self.p_del, self.p_sub = p.p_ins, p.p_del, p.p_sub
         self.tspace = tspace
-        self._h = lib.synth_generate(C.byref(p))
+        if genome is None:
+            self._h = lib.synth_generate(C.byref(p))
+        else:
+            g = np.ascontiguousarray(genome, dtype=np.uint8)
+            if g.shape != (genome_len,) or (len(g) and int(g.max()) > 3):
+                raise ValueError("genome: %d 2-bit codes expected" % genome_len)
+            self._h = lib.synth_generate_genome(C.byref(p), g.ctypes.data_as(C.c_void_p))
         bps = C.c_void_p(); nb = C.c_uint64(); boff = C.c_void_p(); rlen = C.c_void_p(); nr = C.c_uint64()
         ovl = C.c_void_p(); novl = C.c_uint64(); tr = C.c_void_p(); ntr = C.c_uint64()
         piles = C.c_void_p(); npiles = C.c_uint64(); genome = C.c_void_p(); truth = C.c_void_p()

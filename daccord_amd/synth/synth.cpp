@@ -67,12 +67,13 @@ typedef struct synth_params
 	uint32_t afirst, alast;      // overlaps / piles only for the A reads in [afirst,alast) (alast == 0: all); every read is generated either way
 } synth_params;
 
-void * synth_generate(synth_params const * P)
+static void * synth_generate_from(synth_params const * P, uint8_t const * genome)
 {
 	Synth * S = new Synth;
 	Rng grng(P->seed*7919+1);
 	S->genome.resize(P->genome_len);
-	for ( uint64_t i = 0; i < P->genome_len; ++i ) S->genome[i] = grng.next() & 3;
+	if ( genome ) for ( uint64_t i = 0; i < P->genome_len; ++i ) S->genome[i] = genome[i] & 3;
+	else for ( uint64_t i = 0; i < P->genome_len; ++i ) S->genome[i] = grng.next() & 3;
 	uint32_t const L = P->read_len;
 	S->reads.resize(P->nreads);
 	uint64_t const maxspan = static_cast<uint64_t>(L) + 64; // a read never spans more genome than this
@@ -271,6 +272,12 @@ void * synth_generate(synth_params const * P)
 	S->trace.resize(S->trace.size()+16,0);
 	return S;
 }
+
+void * synth_generate(synth_params const * P) { return synth_generate_from(P,0); }
+
+// the same reads, overlaps and traces drawn from a caller's genome (P->genome_len 2-bit codes, one per byte) instead of a random one:
+// low-complexity sequence for the parity tests (tests/lowcomplex_cases.py).  The read streams do not depend on the genome's content.
+void * synth_generate_genome(synth_params const * P, uint8_t const * genome) { return genome ? synth_generate_from(P,genome) : 0; }
 
 void synth_destroy(void * v) { delete static_cast<Synth *>(v); }
 

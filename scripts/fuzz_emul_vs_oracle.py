@@ -1,6 +1,8 @@
 """Randomized parity runs: kernel logic (1-lane emulation, tests/emul) vs the CPU oracle over random run parameters
 (w, a, k ranges, filter frequencies, -d, -m, -f, -l, -e), error profiles and coverages.
-usage: python scripts/fuzz_emul_vs_oracle.py <seed> <rounds> [--wide] [--w128] [--lanes64] [--warp]      (found the -f / empty pile and the scratch overflow bugs)"""
+usage: python scripts/fuzz_emul_vs_oracle.py <seed> <rounds> [--wide] [--w128] [--lanes64] [--warp] [--lowcomplex]      (found the -f / empty pile and the scratch overflow bugs)
+--lowcomplex: the genome of every configuration is low-complexity sequence (tests/lowcomplex_cases.py: homopolymer runs and tandem repeats), its
+mode and seed drawn per configuration (found the missing heapsort fallback of the replayed std::sort and the 64 stretch limit of the candidate decoder)"""
 import sys, os, time, random, collections
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,7 +19,12 @@ for r in range(nrounds):
     if '--warp' in sys.argv and not data.get('warp'):   # every round with badly aligned trace blocks
         data['warp'] = (rng.choice([3, 5]), rng.choice([300, 580, 900]), 2000) if data['tspace'] > 125 else (rng.choice([2, 3, 5]), rng.choice([60, 115, 150]))
     try:
-        d=SynthData(data['genome_len'],data['nreads'],data['read_len'],**{k:v for k,v in data.items() if k not in ('genome_len','nreads','read_len','profile','warp')})
+        gkw = {}
+        if '--lowcomplex' in sys.argv:
+            import lowcomplex_cases
+            lcmode = rng.choice(['mixed', 'dense']); lcseed = rng.randrange(1, 10 ** 6)
+            gkw['genome'] = lowcomplex_cases.genome(data['genome_len'], lcseed, lcmode)
+        d=SynthData(data['genome_len'],data['nreads'],data['read_len'],**gkw,**{k:v for k,v in data.items() if k not in ('genome_len','nreads','read_len','profile','warp')})
         prof=data.get('profile') or d.error_profile()
         ovl,piles=pyoracle.pile_select(d.ovl,d.piles,maxinput=maxin)
         npl=min(len(piles),nplc)
@@ -34,7 +41,7 @@ for r in range(nrounds):
             same = x['status']==y['status'] and x['mao']==y['mao'] and x['elength']==y['elength'] and (x['status']!=1 or (bytes(x['cons'])==bytes(y['cons']) and x['minrate']==y['minrate'] and x['filterfreq']==y['filterfreq'] and x['k']==y['k']))
             nb += (not same)
         ok = nb==0 and len(fo)==len(fe) and bo==be and len(wo)==len(we)
-        print(("OK  " if ok else "BAD "), r, kw, data, "maxinput",maxin,"piles",npl,"nwin",len(wo),"counts",E.counts(),"wdiff",nb, flush=True)
+        print(("OK  " if ok else "BAD "), r, kw, data, "maxinput",maxin,"piles",npl,"nwin",len(wo),"counts",E.counts(),"wdiff",nb, *((("lowcomplex",lcmode,lcseed)) if gkw else ()), flush=True)
         bad += (not ok)
     except Exception as ex:
         print("EXC ", r, kw, data, maxin, repr(ex)[:200], flush=True)
