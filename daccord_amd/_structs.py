@@ -42,7 +42,9 @@ class DaccTiming(C.Structure):
                 # the last stage (tier 13 / 14, layout in device memory, in front of k_window)
                 ("last_ms", C.c_float), ("last_windows", C.c_uint32), ("last_out", C.c_uint32), ("pad4_", C.c_uint32),
                 # the very deep stage (k_window_fast<15>, windows of 251 ... 1000 strings, behind the last stage)
-                ("vdeep_ms", C.c_float), ("vdeep_windows", C.c_uint32), ("vdeep_out", C.c_uint32), ("pad5_", C.c_uint32)]
+                ("vdeep_ms", C.c_float), ("vdeep_windows", C.c_uint32), ("vdeep_out", C.c_uint32),
+                # k_emit (consensus -> A alignment, one lane per window; a part of vote_ms): in the place of a former pad word
+                ("emit_ms", C.c_float)]
 
 
 TIMING_SIZE_V1 = 128

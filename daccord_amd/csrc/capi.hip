@@ -16,6 +16,7 @@
 #include "window_kernels.hpp"
 #include "trace_kernel.hpp"
 #include "vote_kernel.hpp"
+#include "emit_record.hpp"
 
 using namespace dacc;
 
@@ -150,6 +151,16 @@ __global__ void k_check_done(WindowOut const * wout, uint64_t n, uint32_t * errf
 		while ( hi-lo > 1 ) { uint32_t const mid = (lo+hi)>>1; if ( piles[mid].winbase <= i ) lo = mid; else hi = mid; }
 		pilebad[lo] = 1;
 	}
+}
+
+// behind all engines and in front of the vote: one lane per window turns the pending record a tier left (narrow windows, dev_types.hpp:
+// WREC_PENDING) into the final one (emit_record.hpp: the consensus -> A alignment); final and empty records -- the generic engine's, the
+// windows without a consensus -- stay as they are, so a second run over the same records changes nothing.  A wide batch has none pending.
+__global__ void __launch_bounds__(256) k_emit(uint8_t * wrec, uint64_t n, uint32_t w)
+{
+	uint64_t const i = static_cast<uint64_t>(blockIdx.x)*256 + threadIdx.x;
+	if ( i >= n || w == 0 || DACC_WIDE_W(w) ) return;
+	emitPendingRecord(wrec + i*WREC,w);
 }
 
 // dacc_timing's counters of the deep-window tier: the windows with more than `mins` strings on the list the tier read (out[0]) and on the
@@ -377,7 +388,7 @@ struct dacc_ctx
 	dacc_params par;
 	int device;
 	hipStream_t stream; hipStream_t stream2; hipEvent_t evFirstTier, evEarlyGeneric, evPrescan;   // stream2: generic engine for the windows no LDS tier can run, concurrent with tiers 2 and 3
-	hipEvent_t ev[6]; hipEvent_t evslot[TIER_NSLOTS];      // evslot[t]: slot t of the tier chain is done
+	hipEvent_t ev[6]; hipEvent_t evEmit[2]; hipEvent_t evslot[TIER_NSLOTS];      // evslot[t]: slot t of the tier chain is done
 	std::string err;
 	bool haveprofile, havedb, havebatch;
 	double est_cor;
@@ -473,6 +484,7 @@ int dacc_create(dacc_ctx ** out, dacc_params const * p)
 	{ int lo = 0, hi = 0; hipDeviceGetStreamPriorityRange(&lo,&hi); if ( hipStreamCreateWithPriority(&c->stream2,hipStreamNonBlocking,hi) != hipSuccess ) { delete c; return DACC_EHIP; } }
 	hipEventCreateWithFlags(&c->evFirstTier,hipEventDisableTiming); hipEventCreateWithFlags(&c->evEarlyGeneric,hipEventDisableTiming); hipEventCreateWithFlags(&c->evPrescan,hipEventDisableTiming);
 	for ( int i = 0; i < 6; ++i ) hipEventCreate(&c->ev[i]);
+	for ( int i = 0; i < 2; ++i ) hipEventCreate(&c->evEmit[i]);
 	for ( int i = 0; i < TIER_NSLOTS; ++i ) hipEventCreate(&c->evslot[i]);
 	for ( int i = 0; i < TIER_NSTAGES; ++i ) { hipEventCreate(&c->st[i].done); c->st[i].ran = false; c->st[i].grid = 0; c->st[i].in = 0; }
 	*out = c;
@@ -490,6 +502,7 @@ void dacc_destroy(dacc_ctx * c)
 	c->d_wrec.release(); c->d_wout.release(); c->d_arena.release();
 	c->h_outsym.release(); c->d_pilebad.release(); c->d_has.release(); c->d_oc.release(); c->d_outsym.release(); c->d_ld0.release(); c->d_ocs.release(); c->d_nfrag.release(); c->d_err.release(); c->d_frags.release(); c->d_fragbase.release(); c->d_prof.release(); c->d_vst.release(); c->d_tab32.release(); c->d_gslab.release(); c->d_lastslab.release(); c->d_vdeepslab.release(); for ( int i = 0; i < 3; ++i ) c->d_retry[i].release(); c->d_work.release(); c->d_gearly.release(); c->d_pregen.release(); c->d_pregen2.release(); c->d_pregenlist.release(); c->d_arena2.release(); c->d_trslab.release(); c->d_hand.release(); c->d_handctr.release();
 	for ( int i = 0; i < 6; ++i ) hipEventDestroy(c->ev[i]);
+	for ( int i = 0; i < 2; ++i ) hipEventDestroy(c->evEmit[i]);
 	hipStreamDestroy(c->stream); hipStreamDestroy(c->stream2); hipEventDestroy(c->evFirstTier); hipEventDestroy(c->evEarlyGeneric); hipEventDestroy(c->evPrescan); for ( int i = 0; i < TIER_NSLOTS; ++i ) hipEventDestroy(c->evslot[i]);
 	c->d_small.release(); for ( int i = 0; i < TIER_NSTAGES; ++i ) { hipEventDestroy(c->st[i].done); c->st[i].handon.release(); }
 	delete c;
@@ -783,6 +796,11 @@ static int runDevice(dacc_ctx * c)
 	auto voteAndFetch = [&]() -> int
 	{
 		HIPCHK(hipMemsetAsync(c->d_pilebad.p,0,BP.piles.size()+1,s));
+		// the tiers' pending records become final ones (every engine is done: the main stream has waited for the second one); on the
+		// path where all windows went through k_window it finds nothing pending
+		HIPCHK(hipEventRecord(c->evEmit[0],s));
+		if ( BP.nwindows ) { hipLaunchKernelGGL(k_emit,dim3((BP.nwindows+255)/256),dim3(256),0,s,c->d_wrec.p,static_cast<uint64_t>(BP.nwindows),c->par.w); mark("k_emit"); }
+		HIPCHK(hipEventRecord(c->evEmit[1],s));
 		if ( BP.nwindows ) hipLaunchKernelGGL(k_check_done,dim3((BP.nwindows+255)/256),dim3(256),0,s,c->d_wout.p,BP.nwindows,c->d_err.p+3,c->d_piles.p,static_cast<uint32_t>(BP.piles.size()),c->d_pilebad.p);
 		if ( BP.piles.size() )
 		{
@@ -883,7 +901,7 @@ static int runDevice(dacc_ctx * c)
 		c->timing.last_out = nout; c->timing.last_windows = nin > nout ? nin - nout : 0u;
 	}
 	// the very deep stage passes the windows of at most VDEEP_MINS strings on untouched, like the deep-window tier: its own share is counted the same way
-	c->timing.vdeep_windows = 0; c->timing.vdeep_out = 0; c->timing.pad5_ = 0;
+	c->timing.vdeep_windows = 0; c->timing.vdeep_out = 0;
 	if ( dacc_ctx::Stage const * const fV = ranOf(ID_VDEEP) )
 	{
 		HIPCHK(hipMemsetAsync(c->d_work.p+WORK_VDEEP_COUNT,0,2*sizeof(uint32_t),s));
@@ -945,6 +963,7 @@ static int runDevice(dacc_ctx * c)
 	if ( dacc_ctx::Stage const * const fV = ranOf(ID_VDEEP) ) { dacc_ctx::Stage const * const fZ = ranOf(ID_LAST); hipEventElapsedTime(&ms,fZ ? fZ->done : c->evslot[TIER_NSLOTS-1],fV->done); c->timing.vdeep_ms = ms; }
 	if ( fX ) { hipEventElapsedTime(&ms,fD ? fD->done : c->evslot[1],fX->done); c->timing.deep_ms = ms; }
 	hipEventElapsedTime(&ms,c->ev[2],c->ev[3]); c->timing.vote_ms = ms;
+	hipEventElapsedTime(&ms,c->evEmit[0],c->evEmit[1]); c->timing.emit_ms = ms;      // (of the last vote of the batch; a part of vote_ms)
 	hipEventElapsedTime(&ms,c->ev[3],c->ev[4]); c->timing.d2h_ms = ms;
 	hipEventElapsedTime(&ms,c->ev[0],c->ev[3]); c->timing.total_ms = ms;
 	c->timing.first_tier = (TP.usefast && BP.deep) ? 4u : 1u;
@@ -1127,6 +1146,7 @@ void dacc_release(dacc_ctx * c) { if ( c ) { c->frags.clear(); c->bases.clear();
 // that header is not overrun; dacc_last_timing2 copies as much of today's record as the caller says it has room for
 static_assert(offsetof(dacc_timing,deep_ms) == DACC_TIMING_SIZE_V1,"dacc_last_timing fills the record in front of deep_ms");
 static_assert(offsetof(dacc_timing,vdeep_ms) == 160 && sizeof(dacc_timing) == 176,"the very deep stage's fields are appended behind last_*");
+static_assert(offsetof(dacc_timing,emit_ms) == 172,"emit_ms is the last word of the record, where the very deep stage's pad word was");
 int dacc_last_timing(dacc_ctx * c, dacc_timing * t)
 {
 	if ( !c || !t ) return DACC_EINVAL;
@@ -1207,7 +1227,8 @@ int dacc_debug_windows(dacc_ctx * c, dacc_window_result * out, uint64_t cap, uin
 			dacc_window_result r; std::memset(&r,0,sizeof(r));
 			r.pile = pi; r.y = y; r.status = o.status; r.mao = o.mao; r.elength = o.elength; r.k = o.k;
 			r.filterfreq = (o.status == WS_OK) ? o.filterfreq : 0; r.conslen = o.conslen; r.minrate = o.minrate;
-			if ( o.status == WS_OK )
+			// (a record that is not final -- a run that failed between the tiers and k_emit -- has no symbols to show)
+			if ( o.status == WS_OK && wrec[wdx*wrecb] == WREC_FINAL )
 			{
 				// (the consensus as text, cut at 79 symbols: a debugging view)
 				uint8_t const * rec = wrec.data() + wdx*wrecb;

@@ -85,6 +85,14 @@ enum { LPW = LSTR/64 };     // 64 bit words of such a column
 enum { LSTRMAX = 4096 };   // largest string stride the host plan asks for (a longer B window string drops its pile)
 enum { WREC = 256 };       // bytes per window output record (w <= 64)
 enum { MAXCONS = 96 };     // max consensus length (w <= 64)
+// rec[0] of a window record: 0 = no consensus, WREC_FINAL = the record the vote reads, WREC_PENDING = a tier has found the consensus of a narrow
+// window (w <= 64) and left the consensus -> A alignment to k_emit (emit_record.hpp), which turns the record into the final one in place.  The
+// vote reads nothing but final records.  Pending layout (little endian, the slot is 8 byte aligned):
+//   rec[0] = WREC_PENDING, rec[PEND_LEN] = consensus length n (<= MAXCONS), rec[2..8) unused,
+//   rec[PEND_PEQ + 8c ..) = 64 bit pattern mask of symbol c = 0..3 of the A window (bit i <=> A[i] == c, i < w),
+//   rec[PEND_CONS + j] = consensus symbol j (bits above the low two ignored); the bytes from n up to the next multiple of 8 are unspecified.
+enum { WREC_FINAL = 1, WREC_PENDING = 2 };
+enum { PEND_LEN = 1, PEND_PEQ = 8, PEND_CONS = 40 };
 // Wide windows (w in 65..128; generic engine only): consensus up to MAXCONSW symbols, records of WRECW bytes with 16 bit group
 // offsets: rec[0] = status, offset of group r (r = 0..w+1) little endian at rec[2+2r], symbols from rec[2+2(w+2)] on (at most
 // w + MAXCONSW of them: one per A position plus the inserted ones).  The narrow layout (rec[1+r], symbols from rec[1+(w+2)]) is

@@ -67,6 +67,7 @@
 #include "arena.hpp"
 #include "window_main.hpp"
 #include "tier_pipeline.hpp"
+#include "emit_record.hpp"
 
 namespace dacc {
 
@@ -3934,13 +3935,11 @@ struct FastEngine
 		return maxvprodindex;
 	}
 
-	// lane 0: alignment of the consensus to the A window; returns the number of steps of the edit script left in alops.
-	// cons is 8 byte aligned and readable up to the next multiple of 8 behind n (bestL).  The pattern masks of the A window
-	// and the consensus (2 bits per symbol) stay in registers: the forward pass only stores its columns, the traceback
-	// loads a column when it moves to it (A[i-1] == cons[j-1] <=> bit i-1 of the pattern mask of cons[j-1]).
-	// the same for a wide window (w in 65 ... 127, wide tier): two words per column (rows 0-63 / 64-m-1; column c at alpv[2c], alpv[2c+1]),
-	// the horizontal delta leaving word 0 enters word 1 (as in the two-word distance kernel); same traceback priority
-	// (diagonal > DEL > INS), same steps as the generic engine's alignAndEmitWide (dbg_window.hpp)
+	// The consensus -> A alignment of a narrow window (w <= 64) is not done here: the tier leaves a pending record (storePending) and k_emit
+	// aligns one window per lane (emit_record.hpp).  A wide window (w in 65 ... 127, wide tier) is aligned on lane 0: two words per column
+	// (rows 0-63 / 64-m-1; column c at alpv[2c], alpv[2c+1]), the horizontal delta leaving word 0 enters word 1 (as in the two-word distance
+	// kernel); traceback priority diagonal > DEL > INS, same steps as the generic engine's alignAndEmitWide (dbg_window.hpp); returns the
+	// number of steps of the edit script left in alops
 	DEV uint32_t alignAndEmitWide(LDSQ uint8_t const * cons, uint32_t const n)
 	{
 		if constexpr ( CT::wide != 0 )
@@ -4004,128 +4003,47 @@ struct FastEngine
 		}
 		else return 0;
 	}
-	DEV uint32_t alignAndEmit(LDSQ uint8_t const * cons, uint32_t const n)
-	{
-		if constexpr ( CT::wide != 0 ) { if ( DACC_WIDE_W(P.w) ) return alignAndEmitWide(cons,n); }
-		uint32_t const m = P.w;
-		LDSQ uint64_t const * PEQ = L.peq();
-		enum { PW = FastLds<CT>::pw };      // the A window has at most 63 bases: word 0 of every symbol
-		uint64_t const e0 = PEQ[0*PW], e1 = PEQ[1*PW], e2 = PEQ[2*PW], e3 = PEQ[3*PW];
-		LDSQ uint64_t const * T8 = reinterpret_cast<LDSQ uint64_t const *>(cons);
-		static_assert(MAXCONS <= 96 && (FastLds<CT>::o_bestL & 7) == 0,"consensus packed into three 64 bit words");
-		uint64_t const mask = (m == 64) ? ~0ull : ((1ull<<m)-1);
-		uint64_t Pv = mask, Mv = 0; uint32_t score = m;
-		L.alpv()[0] = Pv; L.almv()[0] = Mv; L.albot()[0] = m;
-		uint64_t const top = 1ull<<(m-1);
-		uint64_t ck0 = 0, ck1 = 0, ck2 = 0;      // consensus symbols 0-31, 32-63, 64-95
-		uint64_t w = n ? T8[0] : 0ull;
-		for ( uint32_t c0 = 0; c0 < n; c0 += 8 )
-		{
-			uint64_t const wn = (c0+8 < n) ? T8[(c0>>3)+1] : 0ull;
-			uint32_t const cnt = (n-c0 < 8) ? (n-c0) : 8u;
-			for ( uint32_t u = 0; u < cnt; ++u )
-			{
-				uint32_t const c = c0+u;
-				uint64_t const ch = (w >> (8*u)) & 3u;
-				uint64_t const cs = ch << (2*(c&31));
-				ck0 |= c < 32 ? cs : 0ull; ck1 |= (c >= 32 && c < 64) ? cs : 0ull; ck2 |= c >= 64 ? cs : 0ull;
-				uint64_t const Eq = (ch & 2) ? ((ch & 1) ? e3 : e2) : ((ch & 1) ? e1 : e0);
-				uint64_t const Xv = Eq | Mv;
-				uint64_t const Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-				uint64_t Ph = Mv | ~(Xh | Pv);
-				uint64_t Mh = Pv & Xh;
-				if ( Ph & top ) ++score; else if ( Mh & top ) --score;
-				Ph = (Ph<<1) | 1ull; Mh <<= 1;
-				Pv = (Mh | ~(Xv | Ph)) & mask;
-				Mv = (Ph & Xv) & mask;
-				L.alpv()[c+1] = Pv; L.almv()[c+1] = Mv; L.albot()[c+1] = score;
-			}
-			w = wn;
-		}
-		uint32_t i = m, j = n; uint32_t d = score; uint32_t nops = 0;
-		// column j (its Pv) and column j-1 (Pv, Mv, bottom score) in registers
-		uint64_t pvj = Pv, pv1 = 0, mv1 = 0; uint32_t bot1 = 0;
-		if ( j ) { pv1 = L.alpv()[j-1]; mv1 = L.almv()[j-1]; bot1 = L.albot()[j-1]; }
-		while ( i || j )
-		{
-			uint32_t op = 2; bool done = false; bool left = false;
-			if ( i && j )
-			{
-				uint64_t const sh = i-1;
-				uint32_t const dd = bot1 - dacc_popc64(pv1>>sh) + dacc_popc64(mv1>>sh);
-				uint32_t const jj = j-1;
-				uint64_t const ckw = jj < 32 ? ck0 : (jj < 64 ? ck1 : ck2);
-				uint32_t const ch = static_cast<uint32_t>(ckw >> (2*(jj&31))) & 3u;
-				uint64_t const Eq = (ch & 2) ? ((ch & 1) ? e3 : e2) : ((ch & 1) ? e1 : e0);
-				uint32_t const neq = ((Eq >> sh) & 1) ? 0u : 1u;
-				if ( dd + neq == d ) { op = neq ? 1 : 0; --i; --j; d = dd; done = true; left = true; }
-			}
-			if ( !done && i )
-			{
-				uint64_t const bit = 1ull<<(i-1);
-				if ( pvj & bit ) { op = 3; --i; d = d-1; done = true; }
-			}
-			if ( !done ) { op = 2; --j; d = d-1; left = true; }
-			if ( left )
-			{
-				pvj = pv1;
-				if ( j ) { pv1 = L.alpv()[j-1]; mv1 = L.almv()[j-1]; bot1 = L.albot()[j-1]; }
-			}
-			L.alops()[nops++] = op;
-		}
-		return nops;
-	}
 	// window record from the edit script alops[0..nops) (traceback order: last step first), all lanes.  Every step emits
 	// exactly one symbol (INS / MATCH / MISMATCH: the next consensus symbol, DEL: 'D' = 4), so symbol q belongs to step q
 	// in forward order; off[r] = number of symbols before the group of A column r = index behind the (r-1)-th step that
 	// consumes an A symbol (HandleContext.hpp:2448-2489)
-	DEV void emitRecord(LDSQ uint8_t const * cons, uint32_t const nops, uint8_t * rec)
+	DEV void emitRecordWide(LDSQ uint8_t const * cons, uint32_t const nops, uint8_t * rec)
 	{
-		uint32_t const m = P.w;
 		if constexpr ( CT::wide != 0 )
 		{
-			if ( DACC_WIDE_W(m) )
+			uint32_t const m = P.w;
+			// wide record (dev_types.hpp): 16 bit group offsets from rec[2] on, symbols behind the m+2 offsets
+			uint8_t * const off = rec+2; uint8_t * const sym = rec + 2 + 2*(m+2);
+			if ( lane == 0 ) { rec[0] = WREC_FINAL; rec[1] = 0; off[0] = 0; off[1] = 0; off[2*(m+1)] = nops & 0xFFu; off[2*(m+1)+1] = nops >> 8; }
+			uint32_t cbase = 0, abase = 0;
+			for ( uint32_t c0 = 0; c0 < nops; c0 += WSZ )
 			{
-				// wide record (dev_types.hpp): 16 bit group offsets from rec[2] on, symbols behind the m+2 offsets
-				uint8_t * const off = rec+2; uint8_t * const sym = rec + 2 + 2*(m+2);
-				if ( lane == 0 ) { rec[0] = 1; rec[1] = 0; off[0] = 0; off[1] = 0; off[2*(m+1)] = nops & 0xFFu; off[2*(m+1)+1] = nops >> 8; }
-				uint32_t cbase = 0, abase = 0;
-				for ( uint32_t c0 = 0; c0 < nops; c0 += WSZ )
+				uint32_t const q = c0 + lane;
+				bool const act = q < nops;
+				uint32_t const op = act ? L.alops()[nops-1-q] : 2u;
+				uint32_t ctot, atot;
+				uint32_t const cpos = cbase + wv_scan_flag(act && op != 3,ctot);
+				uint32_t const arank = abase + wv_scan_flag(act && op != 2,atot);
+				if ( act )
 				{
-					uint32_t const q = c0 + lane;
-					bool const act = q < nops;
-					uint32_t const op = act ? L.alops()[nops-1-q] : 2u;
-					uint32_t ctot, atot;
-					uint32_t const cpos = cbase + wv_scan_flag(act && op != 3,ctot);
-					uint32_t const arank = abase + wv_scan_flag(act && op != 2,atot);
-					if ( act )
-					{
-						sym[q] = (op == 3) ? 4 : cons[cpos];
-						if ( op != 2 ) { off[2*(arank+1)] = (q+1) & 0xFFu; off[2*(arank+1)+1] = (q+1) >> 8; }
-					}
-					cbase += ctot; abase += atot;
+					sym[q] = (op == 3) ? 4 : cons[cpos];
+					if ( op != 2 ) { off[2*(arank+1)] = (q+1) & 0xFFu; off[2*(arank+1)+1] = (q+1) >> 8; }
 				}
-				return;
+				cbase += ctot; abase += atot;
 			}
 		}
-		uint8_t * off = rec+1; uint8_t * sym = rec + 1 + (m+2);
-		if ( lane == 0 ) { rec[0] = 1; off[0] = 0; off[m+1] = nops; }
-		uint32_t cbase = 0, abase = 0;
-		for ( uint32_t c0 = 0; c0 < nops; c0 += WSZ )
-		{
-			uint32_t const q = c0 + lane;
-			bool const act = q < nops;
-			uint32_t const op = act ? L.alops()[nops-1-q] : 2u;
-			uint32_t ctot, atot;
-			uint32_t const cpos = cbase + wv_scan_flag(act && op != 3,ctot);
-			uint32_t const arank = abase + wv_scan_flag(act && op != 2,atot);
-			if ( act )
-			{
-				sym[q] = (op == 3) ? 4 : cons[cpos];
-				if ( op != 2 ) off[arank+1] = q+1;
-			}
-			cbase += ctot; abase += atot;
-		}
+	}
+	// pending record of a narrow window (dev_types.hpp: WREC_PENDING), all lanes: one 64 bit word per lane -- the header, the four pattern
+	// masks of the A window (string 0: word 0 of every symbol), the consensus.  cons is 8 byte aligned and readable up to the next
+	// multiple of 8 behind n (bestL); rec is the window's 256 byte slot
+	DEV void storePending(LDSQ uint8_t const * cons, uint32_t const n, uint8_t * rec)
+	{
+		enum { PW = FastLds<CT>::pw };
+		static_assert(MAXCONS <= 96 && (FastLds<CT>::o_bestL & 7) == 0 && PEND_PEQ == 8 && PEND_CONS == 40,"one 64 bit word per lane: header, four masks, twelve words of consensus");
+		LDSQ uint64_t const * T8 = reinterpret_cast<LDSQ uint64_t const *>(cons);
+		uint64_t * const R8 = reinterpret_cast<uint64_t *>(rec);
+		for ( uint32_t q = lane; q < PEND_CONS/8 + (n+7)/8; q += WSZ )
+			R8[q] = (q == 0) ? (static_cast<uint64_t>(WREC_PENDING) | (static_cast<uint64_t>(n) << (8*PEND_LEN))) : ((q < PEND_CONS/8) ? L.peq()[(q-1)*PW] : T8[q-PEND_CONS/8]);
 	}
 };
 
@@ -4418,15 +4336,30 @@ DEV int processWindowFast(FastBatch const & FB, uint64_t const widx, LDSQ uint8_
 		{
 			out.status = WS_OK; out.conslen = bestlen; out.minrate = minrate;
 			PROF_T0
-			uint32_t nops = 0;
 			LEDGER_REPX(E,15)
 			{
-			nops = 0;
-			wv_sync();      // the alignment scratch may lie over the candidate buffers the lanes have just read (gw layout)
-			if ( lane == 0 ) nops = E.alignAndEmit(best,bestlen);
-			wv_sync();
-			nops = wv_bcast(nops,0);
-			E.emitRecord(best,nops,rec);
+			bool wide = false;
+			if constexpr ( CT::wide != 0 ) wide = DACC_WIDE_W(B.P.w);
+			if ( wide )
+			{
+				uint32_t nops = 0;
+				wv_sync();      // the alignment scratch may lie over the candidate buffers the lanes have just read (gw layout)
+				if ( lane == 0 ) nops = E.alignAndEmitWide(best,bestlen);
+				wv_sync();
+				nops = wv_bcast(nops,0);
+				E.emitRecordWide(best,nops,rec);
+			}
+			else
+			{
+				// narrow record: the alignment is k_emit's (one lane per window, behind all engines)
+				E.storePending(best,bestlen,rec);
+#if defined(DACC_EMUL)
+				// (host emulation: no k_emit; lane 0 converts the record with the same routine right away)
+				wv_sync();
+				if ( lane == 0 ) emitPendingRecord(rec,B.P.w);
+				wv_sync();
+#endif
+			}
 			}
 			PROF(E,14)
 		}

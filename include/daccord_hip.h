@@ -208,7 +208,8 @@ typedef struct dacc_timing {
 	float vdeep_ms;          /* its kernel; 0 if it did not run (no window of more than 250 strings in the batch, a wide batch, DACC_VDEEP_TIER=0, DACC_VDEEP_AS_SLOT2=1, no slot ran, no memory for its slab) */
 	uint32_t vdeep_windows;  /* windows of more than 250 strings that finished in it */
 	uint32_t vdeep_out;      /* windows of more than 250 strings it handed on to k_window (more than 1000 strings, a k-mer seen more than 1023 times, a table beyond its capacities) */
-	uint32_t pad5_;
+	float emit_ms;           /* k_emit: the consensus -> A alignment of the tiers' windows (w <= 64), one lane per window, behind all window kernels and in front of the
+	                            vote; a part of vote_ms, not of window_ms.  It took the place of a pad word (always 0 before): the record keeps its size */
 } dacc_timing;
 #define DACC_TIMING_SIZE_V1 128
 /* dacc_last_timing fills the first DACC_TIMING_SIZE_V1 bytes only (the record as it was when the call was introduced: a caller built against

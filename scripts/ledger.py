@@ -18,7 +18,7 @@ PHASES = [(0, "gather: overlap selection, string descriptors, bases -> pattern m
           (8, "computeStretchFeasLanes: stretch feasibility + weight records"), (9, "spillS (build-phase arrays -> slab)"),
           (10, "reverse enumerations of all last k-mers + block copy / sort / rank"), (11, "forward trees of a batch of first k-mers + finish"),
           (12, "pairs, lane-parallel part: classify, matchPops, interval tasks, heaps + pops"), (13, "restoreS (slab -> build-phase arrays)"),
-          (14, "candidate errors: Myers distance of every (candidate, string)"), (15, "alignAndEmit (lane 0) + emitRecord")]
+          (14, "candidate errors: Myers distance of every (candidate, string)"), (15, "window record: pending store (the alignment is k_emit's); wide windows: alignAndEmitWide (lane 0) + emitRecordWide")]
 COUNTERS = ["SQ_WAVE_CYCLES", "SQ_WAIT_ANY", "SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_BRANCH", "SQ_INSTS_LDS", "SQ_INSTS_VMEM_RD", "SQ_INSTS_VMEM_WR"]
 
 
