@@ -724,9 +724,63 @@ static inline void feasit_dump()
 static inline bool feasit_on() { static int on = -1; if ( on < 0 ) on = getenv("DACC_EMUL_FEAS") ? 1 : 0; return on == 1; }      // single threaded design aid only
 #define FEAS_ITERS(t,len,n) { if ( feasit_on() ) { g_feasit.it.push_back(n); g_feasit.ln.push_back(len); } }
 #define FEAS_DUMP() { if ( feasit_on() ) feasit_dump(); }
+// test aid (DACC_EMUL_FEASCASES=<file>): per traversal of computeStretchFeasLanes one line of counters that say which situations of the unit
+// order, of the task rounds (as 64 lanes would run them, whatever the emulation's width) and of the node pipeline it went through
+// (tests/test_feas_pipeline.py asserts that its cases reach each of them).  One window at a time: the emulation of one context is sequential.
+struct FeasCases
+{
+	enum { NU = 0, NCU, NTASK, EMPTY_FIRST, EMPTY_MID, EMPTY_LAST, START_AT_ROUND, START_AT_ROUND_END, SPANS_ROUNDS, ROUNDS, LENMASK, MAXLEN, AT_CLAMP, PAST_CLAMP, MULTI, FAIL0, FAIL1, FAILLAST, NODES, N };
+	uint64_t v[N];
+	void clear() { for ( int i = 0; i < N; ++i ) v[i] = 0; }
+	// widths of the units in processing order, before they become offsets
+	template<typename PT> void units(PT W, uint32_t const nu)
+	{
+		clear();
+		v[NU] = nu;
+		uint32_t first = nu, last = 0;
+		for ( uint32_t q = 0; q < nu; ++q ) if ( W[q] ) { if ( first == nu ) first = q; last = q; }
+		uint64_t t = 0;
+		for ( uint32_t q = 0; q < nu; ++q )
+		{
+			uint32_t const w = W[q];
+			if ( !w ) { if ( q < first ) ++v[EMPTY_FIRST]; else if ( q > last ) ++v[EMPTY_LAST]; else ++v[EMPTY_MID]; continue; }
+			++v[NCU];
+			if ( t && t % 64 == 0 ) ++v[START_AT_ROUND];
+			if ( t % 64 == 63 ) ++v[START_AT_ROUND_END];
+			if ( t/64 != (t+w-1)/64 ) ++v[SPANS_ROUNDS];
+			t += w;
+		}
+		v[NTASK] = t; v[ROUNDS] = (t+63)/64;
+	}
+	void node(uint32_t const j, uint32_t const len, uint32_t const pp, uint32_t const nrows, uint32_t const f)
+	{
+		++v[NODES];
+		if ( j == 0 ) { v[LENMASK] |= 1ull << (len < 63 ? len : 63); if ( len > v[MAXLEN] ) v[MAXLEN] = len; }
+		if ( pp+1 == nrows ) ++v[AT_CLAMP];          // the table word fetched for the node behind this one is the clamp row's
+		if ( pp >= nrows ) ++v[PAST_CLAMP];         // a node's own position on or behind the clamp row
+		if ( f > 1 ) ++v[MULTI];
+	}
+	void fail(uint32_t const j, uint32_t const len) { if ( j == 0 ) ++v[FAIL0]; if ( j == 1 ) ++v[FAIL1]; if ( j+1 == len && len > 2 ) ++v[FAILLAST]; }
+	void dump(int const tier, uint32_t const nwF, uint32_t const nwR)
+	{
+		static FILE * f = 0; static bool tried = false;
+		if ( !tried ) { tried = true; char const * fn = getenv("DACC_EMUL_FEASCASES"); if ( fn ) f = fopen(fn,"w"); }
+		if ( !f ) return;
+		fprintf(f,"%d",tier); for ( int i = 0; i < N; ++i ) fprintf(f," %llu",(unsigned long long)v[i]); fprintf(f," %u %u\n",nwF,nwR); fflush(f);
+	}
+};
+static FeasCases g_feascases;
+#define FEAS_UNITS(W,nu) { if ( lane == 0 ) g_feascases.units(W,nu); }
+#define FEAS_NODE(j,len,pp,nrows,f) g_feascases.node(j,len,pp,nrows,f);
+#define FEAS_FAIL(j,len) g_feascases.fail(j,len);
+#define FEAS_CASES_DUMP() { if ( lane == 0 ) g_feascases.dump(int(CT::maxs),nwF,nwR); }
 #else
 #define FEAS_ITERS(t,len,n)
 #define FEAS_DUMP()
+#define FEAS_UNITS(W,nu)
+#define FEAS_NODE(j,len,pp,nrows,f)
+#define FEAS_FAIL(j,len)
+#define FEAS_CASES_DUMP()
 #define FSTAT_MX(i,x)
 #define FSTAT_ADD(i,x)
 #endif
@@ -1710,32 +1764,43 @@ struct FastEngine
 			if ( u < nu ) { urec[upos_r[cc]] = ulo_r[cc] | (u << 7); L.toff()[upos_r[cc]] = static_cast<uint16_t>(uw_r[cc]); }
 		}
 		wv_sync();
+		FEAS_UNITS(L.toff(),nu)
 		uint32_t tbase = 0;
+		// widths -> first tasks, and the units without a task leave the order: position p of the compacted order (p <= q, so it is
+		// written in place behind the reads of its chunk) holds the record and the first task of the p-th unit that has tasks.
+		// The first tasks are strictly increasing; toff[ncu] = number of tasks ends the list.
+		uint32_t ncu = 0;
 		for ( uint32_t c = 0; c < nu; c += WSZ )
 		{
 			uint32_t const q = c + lane;
 			uint32_t const w = q < nu ? L.toff()[q] : 0u;
+			uint32_t const r = q < nu ? urec[q] : 0u;
 			uint32_t tot; uint32_t const pre = wv_scan_excl(w,tot);
-			if ( q < nu ) L.toff()[q] = tbase + pre;
-			tbase += tot;
+			uint32_t ntot; uint32_t const npre = wv_scan_flag(w != 0,ntot);
+			if ( w != 0 ) { urec[ncu+npre] = r; L.toff()[ncu+npre] = static_cast<uint16_t>(tbase + pre); }
+			tbase += tot; ncu += ntot;
 		}
 		PROFX(18)
 		if ( tbase > 0xFFFF ) { over(128); return; }
-		if ( lane == 0 ) L.toff()[nu] = tbase;
+		if ( lane == 0 ) L.toff()[ncu] = static_cast<uint16_t>(tbase);
 		wv_sync();
 		uint32_t const ntask = tbase;
 		uint64_t const ltmask = wv_lanemask_lt();
+		uint32_t ubase = 0;          // wave-uniform: the unit (position in the compacted order) of the round's first task
 		for ( uint32_t c = 0; c < ntask; c += WSZ )
 		{
 			uint32_t const t = c + lane;
 			bool const act = t < ntask;
 			uint32_t u = 0;
-			if ( act )
 			{
-				// unit of task t: last u with toff[u] <= t (empty units share their successor's offset)
-				uint32_t lo = 0, hi = nu;
-				while ( hi-lo > 1 ) { uint32_t const mid = (lo+hi)>>1; if ( L.toff()[mid] <= t ) lo = mid; else hi = mid; }
-				u = lo;
+				// unit of task t without a search: the tasks of a unit are consecutive, so u = ubase + the number of units that start
+				// in (c,t].  Every unit has a task, so at most WSZ of them start in (c,c+WSZ]: lane i looks at unit ubase+1+i (the
+				// end of the list stands in for the units behind it) and sets bit (first task - c - 1) of a mask the lanes OR together.
+				uint32_t const qi = ubase + 1u + static_cast<uint32_t>(lane);
+				uint32_t const d = static_cast<uint32_t>(L.toff()[qi < ncu ? qi : ncu]) - c - 1u;
+				uint64_t const starts = wv_or64(d < static_cast<uint32_t>(WSZ) ? (1ull << d) : 0ull);
+				u = ubase + dacc_popc64(starts & ltmask);
+				ubase += dacc_popc64(starts);          // a start at c+WSZ (bit WSZ-1) is the next round's first task
 			}
 			uint32_t const ur = act ? urec[u] : 0u;          // u = position in the processing order
 			uint32_t const uu = ur >> 7;
@@ -1749,18 +1814,28 @@ struct FastEngine
 				uint32_t const len = L.sslen()[s]; LDSQ uint16_t const * Lk = L.links() + L.slink()[s];
 				LDSQ uint8_t const * IP = rev ? L.irpos() : L.ipos();
 				#define DACC_LKN(J) static_cast<uint32_t>(Lk[rev ? (len-1-(J)) : (J)])
-				// software pipeline over the nodes: a = node j (first instance known), b = node j+1 (index known), c = node j+2
-				uint32_t z_b = len > 1 ? DACC_LKN(1) : 0u, z_c = len > 2 ? DACC_LKN(2) : 0u;
-				uint32_t i0_a, f_a, ip_a, i0_b, f_b;
-				{ uint32_t const z_a = DACC_LKN(0); i0_a = L.nps()[z_a]; f_a = L.nfreq()[z_a]; ip_a = IP[i0_a]; i0_b = L.nps()[z_b]; f_b = L.nfreq()[z_b]; }
+				// software pipeline over the nodes, every stage one node ahead of the next: link j+4, first instance and frequency
+				// of node j+3, position byte of node j+2, table word of node j+1 -- the word of node j is in a register when its
+				// iteration starts, so the test waits for a load issued a whole iteration ago.  Behind the stretch's end the
+				// stages run on node 0 and on the clamp row: loads of valid indices whose values nothing reads.
+				uint32_t z_d = len > 3 ? DACC_LKN(3) : 0u;
+				uint32_t i0_a, f_a, i0_b, f_b, ip_b, i0_c, f_c;
+				uint32_t U_a;
+				{
+					uint32_t const z_a = DACC_LKN(0), z_b = len > 1 ? DACC_LKN(1) : 0u, z_c = len > 2 ? DACC_LKN(2) : 0u;
+					i0_a = L.nps()[z_a]; f_a = L.nfreq()[z_a]; i0_b = L.nps()[z_b]; f_b = L.nfreq()[z_b]; i0_c = L.nps()[z_c]; f_c = L.nfreq()[z_c];
+					uint32_t const ip_a = IP[i0_a]; ip_b = IP[i0_b];
+					U_a = tabR(ip_a*stride + (P < nrows ? P : nrows));
+				}
 				for ( uint32_t j = 0; j < len; ++j )
 				{
-					uint32_t const z_d = j+3 < len ? DACC_LKN(j+3) : 0u;
-					uint32_t const i0_c = L.nps()[z_c], f_c = L.nfreq()[z_c];
-					uint32_t const ip_b = IP[i0_b];
+					uint32_t const z_e = j+4 < len ? DACC_LKN(j+4) : 0u;
+					uint32_t const i0_d = L.nps()[z_d], f_d = L.nfreq()[z_d];
+					uint32_t const ip_c = IP[i0_c];
 					uint32_t const pp = P+j;
-					uint32_t const pc = pp < nrows ? pp : nrows;
-					uint64_t U = tabR(ip_a*stride + pc);
+					uint32_t const pc = pp < nrows ? pp : nrows, pn = pp+1 < nrows ? pp+1 : nrows;
+					uint32_t const U_b = tabR(ip_b*stride + pn);
+					uint64_t U = U_a;
 					// (round 5) the other instances of the node four at a time: their position bytes, then their table words, are in
 					// flight together -- one instance per step was two dependent round trips (LDS byte, table word in L1 / L2) each
 					for ( uint32_t q = 1; q < f_a; q += 4 )
@@ -1770,11 +1845,12 @@ struct FastEngine
 						uint32_t const t0 = tabR(b0*stride + pc), t1 = tabR(b1*stride + pc), t2 = tabR(b2*stride + pc), t3 = tabR(b3*stride + pc);
 						U += t0; U += m > 1 ? t1 : 0u; U += m > 2 ? t2 : 0u; U += m > 3 ? t3 : 0u;
 					}
-					if ( U < FW_THRES_FEAS ) { ok = false; FEAS_ITERS(t,len,j+1) break; }
+					FEAS_NODE(j,len,pp,nrows,f_a)
+					if ( U < FW_THRES_FEAS ) { ok = false; FEAS_ITERS(t,len,j+1) FEAS_FAIL(j,len) break; }
 					sum += U;
 					if ( j == 0 ) f1 = U;
 					fl = U;
-					i0_a = i0_b; f_a = f_b; ip_a = ip_b; i0_b = i0_c; f_b = f_c; z_c = z_d;
+					i0_a = i0_b; f_a = f_b; U_a = U_b; i0_b = i0_c; f_b = f_c; ip_b = ip_c; i0_c = i0_d; f_c = f_d; z_d = z_e;
 				}
 				if ( ok ) { FEAS_ITERS(t,len,len) }
 				#undef DACC_LKN
@@ -1822,6 +1898,7 @@ struct FastEngine
 		}
 		FEAS_DUMP()
 		wv_sync();
+		FEAS_CASES_DUMP()
 	}
 	// weights of feasible (stretch, position) entry i.  A node weight is a sum of at most fqmax table words of < 2^32: 255 of them stay below 2^40
 	// (8 bit high part), 1023 below 2^42 (10 bits, the tier of more than 256 strings); a feasible stretch has at most nrows <= 64 nodes: < 2^46 / 2^48

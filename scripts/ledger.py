@@ -8,6 +8,8 @@ cannot run twice -- the lane 0 replay of the pairs into the candidate heap, cand
 slots -- is the remainder (total minus the phases).
 
 usage: python scripts/ledger.py <outdir> [reads=1500] [extra bench.py args...]        (needs rocprofv3; ~25 s per pass, 19 passes)
+LEDGER_BITS=8,11 restricts the passes to these phases (the remainder line is then everything else); LEDGER_LIB=<path> measures another
+-DDACC_LEDGER build than daccord_amd/libvar_ledger.so (say the parent's, for a before / after of one phase).
 The library: python -c "from daccord_amd import build; build.build_variant('ledger', ['-DDACC_LEDGER'])"   (here, before the GPU call)"""
 import collections, csv, glob, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,7 +26,7 @@ COUNTERS = ["SQ_WAVE_CYCLES", "SQ_WAIT_ANY", "SQ_INSTS_VALU", "SQ_INSTS_SALU", "
 
 def one_pass(out, tag, mask, reads, extra):
     d = os.path.join(out, "pass_" + tag)
-    env = dict(os.environ, DACC_LIB=os.path.join(ROOT, "daccord_amd", "libvar_ledger.so"), DACC_LEDGER_MASK=str(mask), TMPDIR="/tmp")
+    env = dict(os.environ, DACC_LIB=os.environ.get("LEDGER_LIB") or os.path.join(ROOT, "daccord_amd", "libvar_ledger.so"), DACC_LEDGER_MASK=str(mask), TMPDIR="/tmp")
     cmd = ["rocprofv3", "--pmc"] + COUNTERS + ["--kernel-trace", "--output-format", "csv", "-d", d, "-o", "pmc", "--",
            sys.executable, os.path.join(ROOT, "bench.py"), "--reads", str(reads), "--steps", "1", "--warmup", "0", "--full", "--no-cpu", "--e2e-steps", "0"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd="/tmp", timeout=600)
@@ -43,6 +45,10 @@ def one_pass(out, tag, mask, reads, extra):
 def main():
     out = sys.argv[1]; reads = int(sys.argv[2]) if len(sys.argv) > 2 else 1500; extra = sys.argv[3:]
     os.makedirs(out, exist_ok=True)
+    global PHASES
+    if os.environ.get("LEDGER_BITS"):
+        want = set(int(b) for b in os.environ["LEDGER_BITS"].split(","))
+        PHASES = [p for p in PHASES if p[0] in want]
     base_res, base = one_pass(out, "base", 0, reads, extra)
     sha = base_res["parity"]["gpu_fasta_sha256_all"]
     wins = base_res["roofline"]["windows_by_kernel"]; launches = 2      # first pass + one step
