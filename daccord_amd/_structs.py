@@ -36,11 +36,12 @@ class DaccTiming(C.Structure):
                 ("algo_bytes", C.c_uint64), ("tier_ms", C.c_float * 3), ("tier_out", C.c_uint32 * 3),
                 ("first_tier", C.c_uint32), ("long_windows", C.c_uint32), ("tier0_ms", C.c_float), ("tier0_in", C.c_uint32),
                 ("tier0_out", C.c_uint32), ("tier7_ms", C.c_float), ("tier7_in", C.c_uint32), ("tier7_out", C.c_uint32), ("pad_", C.c_uint32),
-                ("long_first_tier", C.c_uint32), ("tier10_ms", C.c_float), ("tier10_out", C.c_uint32), ("tier10_ran", C.c_uint32), ("pad2_", C.c_uint32),
+                ("long_first_tier", C.c_uint32), ("tier10_ms", C.c_float), ("tier10_out", C.c_uint32), ("tier10_ran", C.c_uint32), ("xdeep_out", C.c_uint32),
                 # (everything above: DACC_TIMING_SIZE_V1 bytes, what dacc_last_timing fills; the deep-window tier: dacc_last_timing2)
-                ("deep_ms", C.c_float), ("deep_windows", C.c_uint32), ("deep_out", C.c_uint32), ("pad3_", C.c_uint32),
+                ("deep_ms", C.c_float), ("deep_windows", C.c_uint32), ("deep_out", C.c_uint32), ("xdeep_ms", C.c_float),
                 # the last stage (tier 13 / 14, layout in device memory, in front of k_window)
-                ("last_ms", C.c_float), ("last_windows", C.c_uint32), ("last_out", C.c_uint32), ("pad4_", C.c_uint32),
+                ("last_ms", C.c_float), ("last_windows", C.c_uint32), ("last_out", C.c_uint32), ("xdeep_windows", C.c_uint32),
+                # (xdeep_out, xdeep_ms, xdeep_windows above: the deepest stage, k_window_fast<16>, windows of 1001 ... 2000 strings; in three former pad words)
                 # the very deep stage (k_window_fast<15>, windows of 251 ... 1000 strings, behind the last stage)
                 ("vdeep_ms", C.c_float), ("vdeep_windows", C.c_uint32), ("vdeep_out", C.c_uint32),
                 # k_emit (consensus -> A alignment, one lane per window; a part of vote_ms): in the place of a former pad word

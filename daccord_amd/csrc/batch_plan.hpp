@@ -68,7 +68,8 @@ struct BatchPlan
 	FastCaps ftierL;          // tier 5: windows with a string of 65..128 bases (second stream, before the generic engine)
 	FastCaps ftierZ;          // the last stage, behind the slots and in front of the generic engine (layout in device memory: tier 13, wide batches 14)
 	FastCaps ftierV;          // the very deep stage behind it (windows of 251 ... 1000 strings, layout in device memory: tier 15)
-	FastCaps & stageCaps(uint32_t const id) { FastCaps * const F[TIER_NSTAGES] = { &ftier0,&ftier7,&ftier[0],&ftier[1],&ftierD,&ftierX,&ftier[2],&ftierZ,&ftierV,&ftierL }; return *F[id]; }
+	FastCaps ftierW;          // the deepest stage behind that (windows of 1001 ... 2000 strings and what tier 15 overflowed on, layout in device memory: tier 16)
+	FastCaps & stageCaps(uint32_t const id) { FastCaps * const F[TIER_NSTAGES] = { &ftier0,&ftier7,&ftier[0],&ftier[1],&ftierD,&ftierX,&ftier[2],&ftierZ,&ftierV,&ftierW,&ftierL }; return *F[id]; }
 	// strings of the deepest window of the batch: the A window and its active overlaps (maxdepth), capped by -d like the kernels' mao
 	uint32_t maxstrings(dacc_params const & par) const { uint64_t const nb = par.maxalign > 0 ? static_cast<uint64_t>(par.maxalign-1) : 0; return 1u + static_cast<uint32_t>(std::min<uint64_t>(maxdepth,nb)); }
 	uint64_t ndeepwin;        // windows with more strings / k-mer instances than the first tier of shallow batches holds

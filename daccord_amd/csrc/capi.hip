@@ -403,7 +403,7 @@ struct dacc_ctx
 	DevBuf<uint8_t> d_wrec; DevBuf<WindowOut> d_wout; DevBuf<uint8_t> d_arena;
 	DevBuf<uint8_t> d_has, d_oc, d_outsym, d_pilebad; DevBuf<uint16_t> d_ld0; DevBuf<uint32_t> d_ocs, d_nfrag, d_err;
 	DevBuf<VoteFragment> d_frags; DevBuf<uint64_t> d_fragbase; DevBuf<uint64_t> d_prof;
-	DevBuf<uint64_t> d_vst; DevBuf<uint32_t> d_tab32; DevBuf<uint8_t> d_gslab, d_lastslab /* the last stage's own slab (layout included) */, d_vdeepslab /* the very deep stage's, allocated by the first batch with a window of more than 250 strings */; DevBuf<uint32_t> d_retry[TIER_NSLOTS], d_work, d_gearly, d_pregen, d_pregen2, d_pregenlist; DevBuf<uint8_t> d_arena2; DevBuf<uint64_t> d_trslab; DevBuf<uint32_t> d_small; DevBuf<uint64_t> d_hand; DevBuf<uint32_t> d_handctr; uint32_t handcap; uint64_t handwant, nruns; bool nohand, oom; bool tier7_adapt_off; int env_t7adapt; int env_trdyn;
+	DevBuf<uint64_t> d_vst; DevBuf<uint32_t> d_tab32; DevBuf<uint8_t> d_gslab, d_lastslab /* the last stage's own slab (layout included) */, d_vdeepslab /* the very deep stage's, allocated by the first batch with a window of more than 250 strings */, d_xdeepslab /* the deepest stage's, allocated by the first batch with a window of more than 1000 strings */; DevBuf<uint32_t> d_retry[TIER_NSLOTS], d_work, d_gearly, d_pregen, d_pregen2, d_pregenlist; DevBuf<uint8_t> d_arena2; DevBuf<uint64_t> d_trslab; DevBuf<uint32_t> d_small; DevBuf<uint64_t> d_hand; DevBuf<uint32_t> d_handctr; uint32_t handcap; uint64_t handwant, nruns; bool nohand, oom; bool tier7_adapt_off; int env_t7adapt; int env_trdyn;
 	// the LDS tiers (tier_pipeline.hpp): their switches, the resolved chain of the current batch (capacities: BP.stageCaps), by TierId and the launch state of its stages.
 	// A main tier hands on through d_retry[slot] and is done at evslot[slot]; `handon` and `done` are those of the front tiers.
 	TierSwitches sw; TierPipeline TP;
@@ -459,7 +459,7 @@ int dacc_create(dacc_ctx ** out, dacc_params const * p)
 	if ( p->klow < 3 || p->khigh > 16 || p->klow > p->khigh || !p->w || !p->a || p->w > DACC_WMAX || p->minfilterfreq < 0 ||
 	     p->maxfilterfreq < p->minfilterfreq || p->tspace <= 0 || p->tspace > 512 )      // (tspace: 1..512, what the planner and the trace kernels hold)
 		return DACC_EINVAL;
-	// DACC_LAST_AS_SLOT2=1 and DACC_VDEEP_AS_SLOT2=1 both name the third slot's main tier: refused before anything is set up
+	// DACC_LAST_AS_SLOT2=1, DACC_VDEEP_AS_SLOT2=1 and DACC_XDEEP_AS_SLOT2=1 each name the third slot's main tier: more than one is refused before anything is set up
 	if ( readTierSwitches().conflict() ) return DACC_EINVAL;
 	int ndev = 0;
 	if ( hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || p->device < 0 || p->device >= ndev )
@@ -474,7 +474,7 @@ int dacc_create(dacc_ctx ** out, dacc_params const * p)
 	c->retry_grid = c->early_grid = c->win_grid = 0; c->tier7_adapt_off = false; c->sched = 0;
 	c->tr_grid = c->tr_lds = c->tr_words = c->tr_lanes = c->trace_bytes = 0;
 	{
-		c->sw = readTierSwitches();      // DACC_NOFAST, DACC_TIERS, DACC_WIDE_TIER, DACC_DENSE_TIER, DACC_DEEP_TIER, DACC_LAST_TIER, DACC_LAST_AS_SLOT2, DACC_VDEEP_TIER, DACC_VDEEP_AS_SLOT2, DACC_LONG128, DACC_HAND, DACC_T0INST, DACC_T7INST, DACC_LDS_T1, DACC_LDS_T0
+		c->sw = readTierSwitches();      // DACC_NOFAST, DACC_TIERS, DACC_WIDE_TIER, DACC_DENSE_TIER, DACC_DEEP_TIER, DACC_LAST_TIER, DACC_LAST_AS_SLOT2, DACC_VDEEP_TIER, DACC_VDEEP_AS_SLOT2, DACC_XDEEP_TIER, DACC_XDEEP_AS_SLOT2, DACC_LONG128, DACC_HAND, DACC_T0INST, DACC_T7INST, DACC_LDS_T1, DACC_LDS_T0
 		char const * sc = getenv("DACC_SCHED"); c->env_sched = sc ? atoi(sc) : 1;      // bit 0: LDS tiers pull work from a counter, bit 1: generic engine too
 		{ char const * td = getenv("DACC_TRACE_DYN"); c->env_trdyn = !(td && td[0] == '0'); }      // 0: k_trace walks its blocks with a fixed stride (rounds 1-5)
 		char const * ta = getenv("DACC_T7_ADAPT"); c->env_t7adapt = !(ta && ta[0] == '0');      // 0: tier 7 stays on whatever it hands on
@@ -500,7 +500,7 @@ void dacc_destroy(dacc_ctx * c)
 	c->d_bps.release(); c->d_boff.release(); c->d_rlen.release();
 	c->d_piles.release(); c->d_ovl.release(); c->d_ovl_pile.release(); c->d_trace.release(); c->d_blk_ovl.release(); c->d_blk_b0.release(); c->d_wt_b.release(); c->d_wt_e.release();
 	c->d_wrec.release(); c->d_wout.release(); c->d_arena.release();
-	c->h_outsym.release(); c->d_pilebad.release(); c->d_has.release(); c->d_oc.release(); c->d_outsym.release(); c->d_ld0.release(); c->d_ocs.release(); c->d_nfrag.release(); c->d_err.release(); c->d_frags.release(); c->d_fragbase.release(); c->d_prof.release(); c->d_vst.release(); c->d_tab32.release(); c->d_gslab.release(); c->d_lastslab.release(); c->d_vdeepslab.release(); for ( int i = 0; i < 3; ++i ) c->d_retry[i].release(); c->d_work.release(); c->d_gearly.release(); c->d_pregen.release(); c->d_pregen2.release(); c->d_pregenlist.release(); c->d_arena2.release(); c->d_trslab.release(); c->d_hand.release(); c->d_handctr.release();
+	c->h_outsym.release(); c->d_pilebad.release(); c->d_has.release(); c->d_oc.release(); c->d_outsym.release(); c->d_ld0.release(); c->d_ocs.release(); c->d_nfrag.release(); c->d_err.release(); c->d_frags.release(); c->d_fragbase.release(); c->d_prof.release(); c->d_vst.release(); c->d_tab32.release(); c->d_gslab.release(); c->d_lastslab.release(); c->d_vdeepslab.release(); c->d_xdeepslab.release(); for ( int i = 0; i < 3; ++i ) c->d_retry[i].release(); c->d_work.release(); c->d_gearly.release(); c->d_pregen.release(); c->d_pregen2.release(); c->d_pregenlist.release(); c->d_arena2.release(); c->d_trslab.release(); c->d_hand.release(); c->d_handctr.release();
 	for ( int i = 0; i < 6; ++i ) hipEventDestroy(c->ev[i]);
 	for ( int i = 0; i < 2; ++i ) hipEventDestroy(c->evEmit[i]);
 	hipStreamDestroy(c->stream); hipStreamDestroy(c->stream2); hipEventDestroy(c->evFirstTier); hipEventDestroy(c->evEarlyGeneric); hipEventDestroy(c->evPrescan); for ( int i = 0; i < TIER_NSLOTS; ++i ) hipEventDestroy(c->evslot[i]);
@@ -766,6 +766,19 @@ static int runDevice(dacc_ctx * c)
 				HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = list;
 				list = S.handon.p;
 			}
+			if ( TP.ok[ID_XDEEP] && list && lastslot >= 0 )
+			{
+				// the deepest stage (tier 16: windows of 1001 ... 2000 strings and what tier 15 overflowed on, layout in device memory; resolved only for a
+				// batch with a window of more than 1000 strings) takes what the very deep stage handed on -- the last stage's or the last slot's list where
+				// the stages in front did not run --, passes the windows of at most 250 strings on as they came and hands on to the generic engine
+				dacc_ctx::Stage & S = c->st[ID_XDEEP];
+				FZ.F = BP.stageCaps(ID_XDEEP); FZ.retry = S.handon.p; FZ.gearly = 0; FZ.gslab = c->d_xdeepslab.p; FZ.gstride = FZ.F.gbytes;
+				FZ.W.pregen = (TP.late_long || TP.widetier) ? c->d_pregen2.p : c->d_pregen.p;
+				HIPCHK(hipMemsetAsync(S.handon.p,0,sizeof(uint32_t),s));
+				hipLaunchKernelGGL(fastKernel(TP.tier[ID_XDEEP]),dim3(S.grid),dim3(64),0,s,FZ,list,work(TIER_CHAIN[ID_XDEEP].work));
+				HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = list;
+				list = S.handon.p;
+			}
 			if ( c->env_dbgretry && slotlist )
 			{
 				uint32_t const * const list = slotlist;
@@ -890,10 +903,10 @@ static int runDevice(dacc_ctx * c)
 	}
 	// the deep-window tier passes the windows of at most FastTier<12>::mins strings on untouched: its own share are the windows with more strings
 	// on the list it read (deep_windows + deep_out) and on the list it handed on (deep_out), counted from the final window records (behind the scratch retries of the generic engine)
-	c->timing.deep_windows = 0; c->timing.deep_out = 0; c->timing.pad3_ = 0;
+	c->timing.deep_windows = 0; c->timing.deep_out = 0;
 	// the last stage: what it read is what the last slot handed on, what it handed on is what k_window ran -- or, in a batch with a window of more
 	// than 250 strings, what the very deep stage read
-	c->timing.last_windows = 0; c->timing.last_out = 0; c->timing.pad4_ = 0;
+	c->timing.last_windows = 0; c->timing.last_out = 0;
 	if ( dacc_ctx::Stage const * const fZ = ranOf(ID_LAST) )
 	{
 		uint32_t nin = 0, nout = 0;
@@ -910,6 +923,17 @@ static int runDevice(dacc_ctx * c)
 		HIPCHK(hipMemcpyAsync(cnt,c->d_work.p+WORK_VDEEP_COUNT,sizeof(cnt),hipMemcpyDeviceToHost,s));
 		HIPCHK(hipStreamSynchronize(s));
 		c->timing.vdeep_out = cnt[1]; c->timing.vdeep_windows = cnt[0] > cnt[1] ? cnt[0] - cnt[1] : 0u;
+	}
+	// the deepest stage, counted the same way with the same threshold: what it read with more than VDEEP_MINS strings is vdeep_out where the very deep stage ran
+	c->timing.xdeep_windows = 0; c->timing.xdeep_out = 0;
+	if ( dacc_ctx::Stage const * const fW = ranOf(ID_XDEEP) )
+	{
+		HIPCHK(hipMemsetAsync(c->d_work.p+WORK_XDEEP_COUNT,0,2*sizeof(uint32_t),s));
+		hipLaunchKernelGGL(k_count_deeper,dim3(64),dim3(256),0,s,fW->in,static_cast<uint32_t const *>(fW->handon.p),c->d_wout.p,static_cast<uint32_t>(VDEEP_MINS),c->d_work.p+WORK_XDEEP_COUNT);
+		uint32_t cnt[2] = {0,0};
+		HIPCHK(hipMemcpyAsync(cnt,c->d_work.p+WORK_XDEEP_COUNT,sizeof(cnt),hipMemcpyDeviceToHost,s));
+		HIPCHK(hipStreamSynchronize(s));
+		c->timing.xdeep_out = cnt[1]; c->timing.xdeep_windows = cnt[0] > cnt[1] ? cnt[0] - cnt[1] : 0u;
 	}
 	if ( fX && fX->in )
 	{
@@ -958,9 +982,10 @@ static int runDevice(dacc_ctx * c)
 	if ( f0 ) { hipEventElapsedTime(&ms,c->ev[1],f0->done); c->timing.tier0_ms = ms; }
 	if ( f7 ) { hipEventElapsedTime(&ms,f0->done,f7->done); c->timing.tier7_ms = ms; }
 	if ( fD ) { hipEventElapsedTime(&ms,c->evslot[1],fD->done); c->timing.tier10_ms = ms; }
-	c->timing.deep_ms = 0; c->timing.last_ms = 0; c->timing.vdeep_ms = 0;
+	c->timing.deep_ms = 0; c->timing.last_ms = 0; c->timing.vdeep_ms = 0; c->timing.xdeep_ms = 0;
 	if ( dacc_ctx::Stage const * const fZ = ranOf(ID_LAST) ) { hipEventElapsedTime(&ms,c->evslot[TIER_NSLOTS-1],fZ->done); c->timing.last_ms = ms; }
 	if ( dacc_ctx::Stage const * const fV = ranOf(ID_VDEEP) ) { dacc_ctx::Stage const * const fZ = ranOf(ID_LAST); hipEventElapsedTime(&ms,fZ ? fZ->done : c->evslot[TIER_NSLOTS-1],fV->done); c->timing.vdeep_ms = ms; }
+	if ( dacc_ctx::Stage const * const fW = ranOf(ID_XDEEP) ) { dacc_ctx::Stage const * const fV = ranOf(ID_VDEEP), * const fZ = ranOf(ID_LAST); hipEventElapsedTime(&ms,fV ? fV->done : (fZ ? fZ->done : c->evslot[TIER_NSLOTS-1]),fW->done); c->timing.xdeep_ms = ms; }
 	if ( fX ) { hipEventElapsedTime(&ms,fD ? fD->done : c->evslot[1],fX->done); c->timing.deep_ms = ms; }
 	hipEventElapsedTime(&ms,c->ev[2],c->ev[3]); c->timing.vote_ms = ms;
 	hipEventElapsedTime(&ms,c->evEmit[0],c->evEmit[1]); c->timing.emit_ms = ms;      // (of the last vote of the batch; a part of vote_ms)
@@ -1063,7 +1088,7 @@ static int dacc_submit_piles_body(dacc_ctx * c, dacc_pile const * piles, uint64_
 				// the last stage: its own hand-on list (what k_window reads) and its own slab, grid x gbytes <= TIER_GMEM_SLAB.  Both are optional like the
 				// hand-over buffer: a device that cannot spare them runs the batch without the stage, on the route it had before
 				// (the very deep stage, resolved only in a batch with a window of more than 250 strings, has a slab of its own: the two kernels' grids differ)
-				DevBuf<uint8_t> & slab = i == ID_VDEEP ? c->d_vdeepslab : c->d_lastslab;
+				DevBuf<uint8_t> & slab = i == ID_XDEEP ? c->d_xdeepslab : (i == ID_VDEEP ? c->d_vdeepslab : c->d_lastslab);
 				hipError_t e = c->st[i].handon.ensure(BP.nwindows+2);
 				if ( e == hipSuccess ) e = slab.ensure(static_cast<size_t>(c->st[i].grid)*F.gbytes + 256);
 				if ( e == hipErrorOutOfMemory ) { (void)hipGetLastError(); slab.release(); c->TP.ok[i] = false; }
@@ -1146,6 +1171,7 @@ void dacc_release(dacc_ctx * c) { if ( c ) { c->frags.clear(); c->bases.clear();
 // that header is not overrun; dacc_last_timing2 copies as much of today's record as the caller says it has room for
 static_assert(offsetof(dacc_timing,deep_ms) == DACC_TIMING_SIZE_V1,"dacc_last_timing fills the record in front of deep_ms");
 static_assert(offsetof(dacc_timing,vdeep_ms) == 160 && sizeof(dacc_timing) == 176,"the very deep stage's fields are appended behind last_*");
+static_assert(offsetof(dacc_timing,xdeep_ms) == 140 && offsetof(dacc_timing,xdeep_windows) == 156 && offsetof(dacc_timing,xdeep_out) == 124,"the deepest stage's fields take the pad words: the record keeps its size");
 static_assert(offsetof(dacc_timing,emit_ms) == 172,"emit_ms is the last word of the record, where the very deep stage's pad word was");
 int dacc_last_timing(dacc_ctx * c, dacc_timing * t)
 {

@@ -30,7 +30,7 @@
  *  - stretches are looked up by first / last node through small index arrays, the weights of a feasible (stretch,
  *    position) entry carry the weights of its end nodes, candidates are kept as stretch sequences and decoded once.
  *
- * The same code is instantiated for sixteen capacity tiers (FastTier<N> below; the layout FastLds<CT> is a compile time constant,
+ * The same code is instantiated for seventeen capacity tiers (FastTier<N> below; the layout FastLds<CT> is a compile time constant,
  * so every LDS access has an immediate offset).  Which of them a batch runs, in which order and behind which switches, is
  * written down once, in tier_pipeline.hpp.
  *
@@ -51,6 +51,7 @@
  *     13  last stage, shallow and deep (layout in device memory)      gw      16 / 16 bit       no LDS
  *     14  last stage, wide batches (layout in device memory)          gw      16 / 16 bit       no LDS
  *     15  very deep stage, shallow and deep: 251 ... 1000 strings     gw      16 / 16 bit       no LDS
+ *     16  deepest stage, shallow and deep: 1001 ... 2000 strings      gw      16 / 16 bit       no LDS
  *
  * processWindowFast returns
  * FW_NEXT when a window overflows a tier (flags say what overflowed: 1 instances, 2 nodes, 8 candidates, 16 walk,
@@ -185,7 +186,7 @@ template<> struct FastTier<12> { typedef uint16_t id_t; typedef uint16_t sid_t; 
 //  - reverse pool: 4096 paths in 256 chunks of 16 (8 bit chunk ids kept: tier 3 has 256 chunks of 8, so an enumeration needs at most as many chunks here);
 //  - 16 bit weight offsets and task offsets kept: 16384 weight records per direction, at most 65535 (stretch, direction, position) tasks per traversal;
 //  - more than 4094 nodes: the stretch sort key takes 13 bit node fields and a 12 bit stretch number (FastEngine: KF, QB).
-// Windows of more than 250 strings go on to tier 15; wider than 127 bases or with a string of more than 128 bases they still go to the generic engine.
+// Windows of more than 250 strings go on to tiers 15 and 16; wider than 127 bases or with a string of more than 128 bases they still go to the generic engine.
 template<> struct FastTier<13> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 2000, gw = 1, wcapg = 16384, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 250, precap = 16384, ncap = 4096, scap = 2048, lcap = 8192, wcap = 16384, rccap = 4096, fcap = 1024, siqcap = 512, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 4096, wide = 0, mins = 0, gmem = 1 }; };
 template<> struct FastTier<14> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 1000, gw = 1, wcapg = 16384, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 250, precap = 16384, ncap = 6144, scap = 1024, lcap = 8192, wcap = 16384, rccap = 4096, fcap = 2048, siqcap = 512, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 4096, wide = 1, mins = 0, gmem = 1 }; };
 // tier 15: the VERY DEEP stage, behind the last stage and in front of the generic engine (tier_pipeline.hpp: ID_VDEEP): windows of 251 ... 1000 strings
@@ -208,6 +209,22 @@ template<> struct FastTier<14> { typedef uint16_t id_t; typedef uint16_t sid_t; 
 template<> struct FastTier<15> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 2000, gw = 1, wcapg = 32768, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 1000, precap = 16384, ncap = 4096, scap = 2048, lcap = 8192, wcap = 32768, rccap = 4096, fcap = 1024, siqcap = 512, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 4096, wide = 0, mins = 250, gmem = 1 }; };
 
 static_assert(FastTier<15>::mins == VDEEP_MINS && FastTier<13>::maxs == VDEEP_MINS,"the very deep stage takes what the last stage refuses at its string count");
+// tier 16: the DEEPEST stage, behind the very deep stage and in front of the generic engine (tier_pipeline.hpp: ID_XDEEP): windows of 1001 ... 2000 strings
+// and the windows of 251 ... 1000 strings that overflowed one of tier 15's tables (mins = 250: everything else is passed on as it came).  Tier 15's code
+// with twice its graph: 8190 nodes (the most the 13 bit node fields of the stretch sort key name), 4096 stretches (its 12 bit stretch number), 16384
+// links, 4000 pool stretches.  What a string count above 1024 widens (FastLds<CT>::xwides, all other tiers keep their fields bit for bit):
+//  - compact string list: 11 bit string id | 17 bit first slot;
+//  - node frequency capped at fqmax = 4095: node weight < 2^44 (12 bit high part), stretch weight < 2^50 (18 bit high part), the reverse record's third
+//    word holds 18 + 12 bits; the forward record is the three 64 bit words of tier 15;
+//  - 131072 k-mer instances (icap = 8 x precap) as 64 ranges by the first three symbols of the k-mer: a histogram pass counts them, every range is sorted
+//    with the sort of precap = 16384 keys (a uniform window of 2000 strings has 5200 in its largest range); a range of more than precap hands the window on;
+//  - 32 bit task offsets and weight offsets (FastLds<CT>::toff_t): a traversal of 3400 stretches at k = 8 has more than 65535 (stretch, direction,
+//    position) tasks and up to 45324 feasible ones in a direction, so 65536 weight records per direction (with tier 15's 32768, 19 of the 37 windows of
+//    tests/xdeep_cases.py shape P overflow at k = 8; with 65536 none).
+// Pools, intervals and the lane scratch are tier 15's: the pending-path heap of a reverse enumeration that outgrows its lane's 32 ids is run again on the
+// whole scratch (lscrids = 4096 ids), which holds every path of the pool (rccap = 4096), so it never sends a window on by itself.
+template<> struct FastTier<16> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 4000, gw = 1, wcapg = 65536, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 8000, rpstcap = 768, lstr = 128, maxs = 2000, precap = 16384, ncap = 8190, scap = 4096, lcap = 16384, wcap = 65536, rccap = 4096, fcap = 1024, siqcap = 512, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 4096, wide = 0, mins = 250, gmem = 1 }; };
+static_assert(FastTier<16>::mins == VDEEP_MINS && FastTier<15>::maxs == XDEEP_MINS,"the deepest stage takes what the very deep stage hands on with more than 250 strings");
 
 HDEV constexpr uint32_t fcpow2(uint32_t v) { uint32_t p = 1; while ( p < v ) p <<= 1; return p; }
 HDEV constexpr uint32_t fcmax(uint32_t a, uint32_t b) { return a > b ? a : b; }
@@ -232,7 +249,7 @@ struct FastLds<CT,false>
 {
 	LDSQ uint8_t * base;
 	static constexpr uint32_t keycap = fcpow2(CT::maxs < 2 ? 2 : CT::maxs);
-	static constexpr bool wides = false; static constexpr uint32_t fqmax = 255u, icap = CT::precap;      // (more than 256 strings: gw layout only)
+	typedef uint16_t toff_t; static constexpr bool wides = false, xwides = false; static constexpr uint32_t fqmax = 255u, icap = CT::precap;      // (more than 256 strings: gw layout only)
 	static_assert(CT::maxs <= 256,"the legacy layout has 8 bit node frequencies and string ids");
 	static_assert((CT::precap & (CT::precap-1)) == 0,"precap must be a power of two: the bitonic sorts pad to one");
 	static_assert(sizeof(typename CT::id_t) > 1 || (CT::fcap <= 256 && CT::rccap <= 256),"pool slots are recorded as id_t (pout)");
@@ -445,9 +462,13 @@ struct FastLds<CT,true>
 	typedef typename CT::sid_t sid_t;      // stretch ids: 8 bits (at most 250 stretches) or 16 bits
 	// more than 256 strings (tier 15): 16 bit node frequencies capped at fqmax, 32 bit first-instance offsets, a 32 byte forward weight record
 	static constexpr bool wides = CT::maxs > 256;
-	static constexpr uint32_t fqmax = wides ? 1023u : 255u;
-	// k-mer instances the layout holds: precap, the capacity of one instance sort -- with more than 256 strings four such ranges (buildInstances)
-	static constexpr uint32_t icap = wides ? 4u*CT::precap : CT::precap;
+	// more than 1024 strings (tier 16): node frequencies up to 4095, 64 instance ranges, 32 bit task offsets
+	static constexpr bool xwides = CT::maxs > 1024;
+	static constexpr uint32_t fqmax = xwides ? 4095u : (wides ? 1023u : 255u);
+	// k-mer instances the layout holds: precap, the capacity of one instance sort -- with more than 256 strings four such ranges, with more than
+	// 1024 strings 64 ranges that share eight times precap (buildInstances)
+	static constexpr uint32_t icap = xwides ? 8u*CT::precap : (wides ? 4u*CT::precap : CT::precap);
+	typedef typename FWideSel<xwides,uint32_t,uint16_t>::type toff_t;
 	typedef typename FWideSel<wides,uint16_t,uint8_t>::type nfreq_t;
 	typedef typename FWideSel<wides,uint32_t,uint16_t>::type nps_t;
 	static_assert(fqmax <= (1u << (8u*sizeof(nfreq_t))) - 1u,"a node frequency holds fqmax");
@@ -544,8 +565,9 @@ struct FastLds<CT,true>
 	FLD(maskR,uint64_t,CT::scap,e_maskF)
 	FLD(maskFh,uint64_t,(CT::wide ? CT::scap : 0u),e_maskR)      // wide tier: start positions 64 ... 127
 	FLD(maskRh,uint64_t,(CT::wide ? CT::scap : 0u),e_maskFh)
-	FLD(woffF,uint16_t,CT::scap,e_maskRh)
-	FLD(woffR,uint16_t,CT::scap,e_woffF)
+	FLD(woffF,toff_t,CT::scap,e_maskRh)      // (toff_t: 16 bits, wcap <= 65535; more than 1024 strings: 32 bits)
+	FLD(woffR,toff_t,CT::scap,e_woffF)
+	static_assert(sizeof(toff_t) == 4 || CT::wcap <= 65535u,"weight offsets of 16 bits");
 	FLD(links,uint16_t,CT::lcap,e_woffR)
 	FLD(lhead,sid_t,CT::ncap,e_links)
 	FLD(lord,uint32_t,CT::scap,e_lhead)
@@ -574,7 +596,7 @@ struct FastLds<CT,true>
 	static_assert(sizeof(FSI)*CT::siqcap <= lscrbytes,"the serial score interval heap shares the lane scratch");
 	// (the scratch tables of the stretch construction need 3 bytes per node: the region is at least that long)
 	static constexpr uint32_t alnbytes = 2u*8u*alw*(consmax+1u) + 2u*(consmax+1u) + 8u + (2u*consmax + 2u*64u + 8u) + 16u;      // alpv, almv, albot, alops
-	static constexpr uint32_t uB = fcmax(fcmax(fcmax(fcmax(e_consL,e_lscr),xbase + 3u*CT::ncap + 16u),xbase + (2u*CT::scap+2u)*2u + 8u + 8u*CT::scap + 16u),CT::wide ? xbase + alnbytes : 0u);
+	static constexpr uint32_t uB = fcmax(fcmax(fcmax(fcmax(e_consL,e_lscr),xbase + 3u*CT::ncap + 16u),xbase + (2u*CT::scap+2u)*static_cast<uint32_t>(sizeof(toff_t)) + 8u + 8u*CT::scap + 16u),CT::wide ? xbase + alnbytes : 0u);
 	static constexpr uint32_t xbytes = uB - xbase;
 	// raw stretches: over the pattern masks and weight offsets, which the feasibility writes later
 	FLD(tfirst,uint16_t,CT::scap,o_maskF)
@@ -589,7 +611,7 @@ struct FastLds<CT,true>
 	FLD(albot,uint16_t,consmax+1,e_almv)
 	FLD(alops,uint8_t,2*consmax+2*64+8,e_albot)
 	static_assert(e_alops <= uB,"final alignment scratch");
-	FLD(toff,uint16_t,2*CT::scap+2,xbase)
+	FLD(toff,toff_t,2*CT::scap+2,xbase)
 	FLD(urec,uint32_t,2*CT::scap,e_toff)      // unit at position q of the processing order: lo | unit << 7
 	static_assert(e_urec <= uB,"feasibility tasks");
 	static_assert(3u*CT::ncap + 16u <= xbytes,"predecessor counts (a byte per node) and walking table must fit the scratch");
@@ -889,10 +911,10 @@ struct FastEngine
 		enum : bool { GENMARKS = true };
 #endif
 		// compact string list entry: string | first slot << CLB.  8 bit string ids and 24 bit slots; more than 256 strings: 10 bit ids, 16 bit slots
-		// (a first slot is below npre <= 65536)
-		enum : bool { WIDES = FastLds<CT>::wides };
-		enum : uint32_t { CLB = WIDES ? 10u : 8u, CLMASK = (1u << CLB) - 1u };
-		static_assert(4u*CT::maxs <= FastLds<CT>::icap && CT::maxs <= (1u << CLB) && FastLds<CT>::icap <= (1u << (WIDES ? 16 : 24)),"compact string list: string | first slot << CLB, in the bytes of irpos");
+		// (a first slot is below npre <= 65536); more than 1024 strings: 11 bit ids, 17 bit slots (npre <= 131072)
+		enum : bool { WIDES = FastLds<CT>::wides, XWIDES = FastLds<CT>::xwides };
+		enum : uint32_t { CLB = XWIDES ? 11u : (WIDES ? 10u : 8u), CLMASK = (1u << CLB) - 1u };
+		static_assert(4u*CT::maxs <= FastLds<CT>::icap && CT::maxs <= (1u << CLB) && FastLds<CT>::icap <= (1u << (XWIDES ? 17 : (WIDES ? 16 : 24))),"compact string list: string | first slot << CLB, in the bytes of irpos");
 		static_assert(!WIDES || GENMARKS,"the two-pass generation of more than 256 strings needs the marks");
 		LDSQ uint8_t * const marks = L.ipos();                                             // free until buildNodes writes the positions
 		LDSQ uint32_t * const clist = reinterpret_cast<LDSQ uint32_t *>(L.irpos());
@@ -1022,7 +1044,44 @@ struct FastEngine
 		SITE(31)      // buildInstances: generation of the k-mer instances (lane = instance)
 		wv_sort_keys<FastLds<CT>::keycap>(L.lastk(),nlast);
 		SITE(32)      // buildInstances: sort of the last k-mers
-		if constexpr ( WIDES )
+		if constexpr ( XWIDES )
+		{
+			// Up to 8 x precap instances in 64 ranges by the first three symbols of the k-mer (the six highest bits of the key; k >= 3), range r behind
+			// range r-1, each sorted on its own with the sort of precap keys.  A histogram pass counts the ranges -- a counter per range in the bytes
+			// of the generation's marks, which nothing reads any more, bumped by workgroup atomics --, lane 0 turns the counts into first places, and a
+			// second pass takes a place per instance from the same counters: the order inside a range is whatever the atomics gave, the keys are
+			// distinct and the sort settles it.  A range of more than precap keys sends the window on like a full instance array.
+			enum : uint32_t { NR = 64 };
+			static_assert(NR*8u <= FastLds<CT>::icap && (FastLds<CT>::o_ipos & 3u) == 0,"range counters and places: two 32 bit words per range in the bytes of ipos");
+			static_assert(FastLds<CT>::icap <= NR*CT::precap,"the ranges can hold every instance");
+			LDSQ uint32_t * const rcnt = reinterpret_cast<LDSQ uint32_t *>(L.ipos()), * const rat = rcnt + NR;
+			uint32_t const sh = 32u + 2u*k - 6u;
+			for ( uint32_t r = lane; r < 2u*NR; r += WSZ ) rcnt[r] = 0;
+			wv_sync();
+			for ( uint32_t t = lane; t < npre; t += WSZ ) wv_atomic_add(rcnt + (static_cast<uint32_t>(L.pregen()[t] >> sh) & (NR-1u)),1u);
+			wv_sync();
+			uint32_t big = 0;
+			if ( lane == 0 )
+			{
+				uint32_t o = 0;
+				for ( uint32_t r = 0; r < NR; ++r ) { uint32_t const n = rcnt[r]; big |= n > CT::precap; rat[r] = o; o += n; }
+			}
+			if ( wv_or(big) ) { over(1); npre = 0; nlast = 0; return; }
+			wv_sync();
+			for ( uint32_t t = lane; t < npre; t += WSZ )
+			{
+				uint64_t const w = L.pregen()[t];
+				L.pre()[wv_atomic_add(rat + (static_cast<uint32_t>(w >> sh) & (NR-1u)),1u)] = w;
+			}
+			wv_sync();
+			// (rat[r] is now the end of range r)
+			for ( uint32_t r = 0; r < NR; ++r )
+			{
+				uint32_t const n = wv_uni(rcnt[r]), e = wv_uni(rat[r]);
+				if ( n > 1 ) wv_sort_keys<CT::precap>(L.pre()+(e-n),n);
+			}
+		}
+		else if constexpr ( WIDES )
 		{
 			// Up to 4 x precap instances: split by the first symbol of the k-mer (the two highest bits of the key) into four ranges, range r behind
 			// range r-1, and sort every range on its own with the sort of precap keys; the concatenation is the sorted array.  A range of more than
@@ -1713,6 +1772,11 @@ struct FastEngine
 		// the units gives the same weights: a unit's entries stay consecutive and ascending in its own list, only the place
 		// of the list in the weight arrays changes.  Position q of the order holds (lo | unit << 7) in the bytes of ulo/uhi.
 		enum { NCHU = (2*CT::scap + WSZ - 1)/WSZ, NCLS = 12 };
+		// task offsets: 16 bits, at most 65535 tasks per traversal; 32 bits with more than 1024 strings (FastLds<CT>::toff_t) -- a task there is one of
+		// at most 2 x scap x nrows <= 2^19 triples, and the running sum below is a 32 bit word either way
+		typedef typename FastLds<CT>::toff_t toff_t;
+		enum : uint32_t { TOFFMAX = sizeof(toff_t) == 2 ? 0xFFFFu : 0xFFFFFFu };
+		static_assert(sizeof(toff_t) == 2 || 2ull*CT::scap*128ull <= TOFFMAX,"task offsets: every (stretch, direction, position) triple can be named");
 		// (legacy layout: 16 bit records over the bytes of ulo / uhi, at most 511 units; gw layout: 32 bit records)
 		auto const urec = unitRecords();
 		uint32_t ulo_r[NCHU], uw_r[NCHU], ucls_r[NCHU], upos_r[NCHU];
@@ -1761,7 +1825,7 @@ struct FastEngine
 		for ( uint32_t cc = 0; cc < NCHU; ++cc )
 		{
 			uint32_t const u = cc*WSZ + lane;
-			if ( u < nu ) { urec[upos_r[cc]] = ulo_r[cc] | (u << 7); L.toff()[upos_r[cc]] = static_cast<uint16_t>(uw_r[cc]); }
+			if ( u < nu ) { urec[upos_r[cc]] = ulo_r[cc] | (u << 7); L.toff()[upos_r[cc]] = static_cast<toff_t>(uw_r[cc]); }
 		}
 		wv_sync();
 		FEAS_UNITS(L.toff(),nu)
@@ -1777,12 +1841,12 @@ struct FastEngine
 			uint32_t const r = q < nu ? urec[q] : 0u;
 			uint32_t tot; uint32_t const pre = wv_scan_excl(w,tot);
 			uint32_t ntot; uint32_t const npre = wv_scan_flag(w != 0,ntot);
-			if ( w != 0 ) { urec[ncu+npre] = r; L.toff()[ncu+npre] = static_cast<uint16_t>(tbase + pre); }
+			if ( w != 0 ) { urec[ncu+npre] = r; L.toff()[ncu+npre] = static_cast<toff_t>(tbase + pre); }
 			tbase += tot; ncu += ntot;
 		}
 		PROFX(18)
-		if ( tbase > 0xFFFF ) { over(128); return; }
-		if ( lane == 0 ) L.toff()[ncu] = static_cast<uint16_t>(tbase);
+		if ( tbase > TOFFMAX ) { over(128); return; }
+		if ( lane == 0 ) L.toff()[ncu] = static_cast<toff_t>(tbase);
 		wv_sync();
 		uint32_t const ntask = tbase;
 		uint64_t const ltmask = wv_lanemask_lt();
@@ -1904,10 +1968,15 @@ struct FastEngine
 	// (8 bit high part), 1023 below 2^42 (10 bits, the tier of more than 256 strings); a feasible stretch has at most nrows <= 64 nodes: < 2^46 / 2^48
 	// (16 bit high part either way).  Everything summed from these -- link weights, path weights rc_w / f_w, score intervals, candidates -- is a 64 bit
 	// word: a path has at most FSEQCAP stretches (< 2^54).
-	enum : uint32_t { FQMAX = FastLds<CT>::fqmax, NWHB = FQMAX <= 255u ? 8u : 10u, NWHMASK = (1u << NWHB) - 1u };
+	// (more than 1024 strings, fqmax = 4095: node weight < 2^44, 12 bit high part; stretch weight < 2^50, 18 bit high part -- SWHB; the forward record
+	// of that tier holds whole 64 bit words, the reverse record's third word 18 + 12 bits)
+	enum : uint32_t { FQMAX = FastLds<CT>::fqmax, NWHB = FQMAX <= 255u ? 8u : (FQMAX <= 1023u ? 10u : 12u), NWHMASK = (1u << NWHB) - 1u,
+		SWHB = FQMAX <= 1023u ? 16u : 18u, SWHMASK = (1u << SWHB) - 1u };
 	static_assert((static_cast<uint64_t>(FQMAX)*0xFFFFFFFFull) >> (32u+NWHB) == 0,"high part of a node weight: fqmax table words");
-	static_assert((64ull*static_cast<uint64_t>(FQMAX)*0xFFFFFFFFull) >> 48 == 0,"high part of a stretch weight: 64 nodes, 16 bits");
-	static_assert(16u + NWHB <= 32u,"reverse record: both high parts in its third word");
+	static_assert((64ull*static_cast<uint64_t>(FQMAX)*0xFFFFFFFFull) >> (32u+SWHB) == 0,"high part of a stretch weight: 64 nodes");
+	static_assert(SWHB + NWHB <= 32u,"reverse record: both high parts in its third word");
+	static_assert(SWHB == 16u || FastLds<CT>::wides,"a stretch weight of more than 48 bits needs the 32 byte forward record");
+	static_assert(CT::maxs <= 1024 || (FastLds<CT>::fqmax == 4095u && FastLds<CT>::icap == 8u*CT::precap && FastLds<CT>::xwides),"more than 1024 strings: the widths of FastLds<CT>::xwides");
 	static_assert(FastLds<CT>::wides || 16u + 2u*NWHB <= 32u,"forward record: three high parts in its fourth word, or the 32 byte record");
 	struct G8 { G4 a, b; };      // the 32 byte forward record of more than 256 strings: w, w1 | wl, unused (two 16 byte loads)
 	// One record per feasible (stretch, position) entry.  Forward: whole stretch (w), its first node at the start position
@@ -1942,7 +2011,7 @@ struct FastEngine
 		if constexpr ( GW )
 		{
 			G4 const v = reinterpret_cast<G4 const *>(gslab + FastLds<CT>::g_wR)[i];
-			r.w = v.x | (static_cast<uint64_t>(v.z & 0xFFFFu)<<32); r.w1 = v.y | (static_cast<uint64_t>((v.z>>16)&NWHMASK)<<32);
+			r.w = v.x | (static_cast<uint64_t>(v.z & SWHMASK)<<32); r.w1 = v.y | (static_cast<uint64_t>((v.z>>SWHB)&NWHMASK)<<32);
 		}
 		else
 		{
@@ -1977,7 +2046,7 @@ struct FastEngine
 		if constexpr ( GW )
 		{
 			G4 v; v.x = static_cast<uint32_t>(rsum); v.y = static_cast<uint32_t>(r1);
-			v.z = (static_cast<uint32_t>(rsum>>32)&0xFFFFu) | ((static_cast<uint32_t>(r1>>32)&NWHMASK)<<16); v.w = 0;
+			v.z = (static_cast<uint32_t>(rsum>>32)&SWHMASK) | ((static_cast<uint32_t>(r1>>32)&NWHMASK)<<SWHB); v.w = 0;
 			reinterpret_cast<G4 *>(gslab + FastLds<CT>::g_wR)[o] = v;
 		}
 		else

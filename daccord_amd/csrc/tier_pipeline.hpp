@@ -10,6 +10,7 @@
  *   shallow and deep  tier 5 on the second stream (k_window_long), in front of the generic engine there
  *   every batch       the LAST stage, once, behind the slots and in front of the generic engine: tier 13 (shallow, deep) / tier 14 (wide)
  *   shallow and deep  the VERY DEEP stage, behind the last stage, only in a batch with a window of more than 250 strings: tier 15
+ *   shallow and deep  the DEEPEST stage, behind the very deep stage, only in a batch with a window of more than 1000 strings: tier 16
  *
  * (TIER_CHAIN below: one row per stage, one column per batch shape.)
  *
@@ -30,7 +31,17 @@
  * on to the generic engine.  Its slab is allocated and its kernel launched only in a batch whose deepest window has more than 250 strings
  * (resolveTiers: maxstrings), so every other batch runs the launches it ran before the stage existed; a wide batch has no such tier.
  * DACC_VDEEP_TIER=0 removes it.  DACC_VDEEP_AS_SLOT2=1 (tests) makes tier 15 the main tier of the third slot of shallow and deep batches, with
- * tier 12 still in front of it, and switches ID_VDEEP off; together with DACC_LAST_AS_SLOT2=1 it is an error (TierSwitches::conflict).
+ * tier 12 still in front of it, and switches ID_VDEEP off.
+ *
+ * The DEEPEST stage (ID_XDEEP, ROLE_LAST as well) runs tier 16 -- windows of 1001 ... 2000 strings, and those of 251 ... 1000 that overflowed a table
+ * of tier 15; it passes the windows of at most 250 strings on untouched -- over the list the very deep stage handed on (without it: the last stage's
+ * or the last enabled slot's list) and hands on to the generic engine.  Its slab is allocated and its kernel launched only in a batch whose deepest
+ * window has more than XDEEP_MINS = 1000 strings, so every other batch runs the launches it ran before the stage existed.  DACC_XDEEP_TIER=0 removes
+ * it.  DACC_XDEEP_AS_SLOT2=1 (tests) makes tier 16 the main tier of the third slot of shallow and deep batches, with tier 12 still in front of it,
+ * and switches ID_XDEEP off.
+ *
+ * More than one of DACC_LAST_AS_SLOT2=1, DACC_VDEEP_AS_SLOT2=1 and DACC_XDEEP_AS_SLOT2=1 is an error (TierSwitches::conflict): each names the third
+ * slot's main tier.
  */
 #ifndef DACC_TIER_PIPELINE_HPP
 #define DACC_TIER_PIPELINE_HPP
@@ -55,7 +66,7 @@ enum : uint32_t { T0INST_DEFAULT = 576, T7INST_DEFAULT = 704 };      // a window
                                                // arguments of the pre-pass (DACC_T0INST / DACC_T7INST override them for sweeps)
 
 // The tiers.  KERNEL: those with a kernel of their own (k_window_fast<N>, window_kernels.hpp); tier 5 runs inside k_window_long.
-#define DACC_KERNEL_TIERS(X) X(0) X(1) X(2) X(3) X(4) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
+#define DACC_KERNEL_TIERS(X) X(0) X(1) X(2) X(3) X(4) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
 #define DACC_ALL_TIERS(X) DACC_KERNEL_TIERS(X) X(5)
 
 // From a run-time tier number to its compile-time capacities: f is called with a TierTag<N>, whose `type` is FastTier<N>
@@ -81,6 +92,7 @@ enum : uint32_t
 	GATE_PREV_SLOT = 16,  // needs the main tier of the slot in front as well (the dense tiers need slots 1 and 2)
 	GATE_DEEP = 128,      // DACC_DEEP_TIER=0 switches it off (windows of more than 96 strings run in the generic engine, as before the deep-window tier)
 	GATE_LAST = 256,      // DACC_LAST_TIER=0 or DACC_LAST_AS_SLOT2=1 switches it off; needs a slot that ran
+	GATE_XDEEP = 1024,    // DACC_XDEEP_TIER=0 or DACC_XDEEP_AS_SLOT2=1 switches it off; needs a slot that ran and a window of more than XDEEP_MINS strings in the batch
 	GATE_VDEEP = 512,     // DACC_VDEEP_TIER=0 or DACC_VDEEP_AS_SLOT2=1 switches it off; needs a slot that ran and a window of more than VDEEP_MINS strings in the batch
 	STAGE_PREPASS = 32,   // (no gate) fed by the size-class pre-pass instead of the list in front of it
 	STAGE_ADAPTIVE = 64   // (no gate) switches itself off for the rest of a context when it hands on too much (DACC_T7_ADAPT)
@@ -92,12 +104,15 @@ enum : uint32_t { WORK_SLOT0 = 0, WORK_SLOT1 = 8, WORK_SLOT2 = 16, WORK_DENSE = 
 	WORK_DEEP_COUNT = 72,      // two words: windows of more than FastTier<12>::mins strings the deep-window tier read / handed on (for dacc_timing)
 	WORK_LAST = 80, WORK_VDEEP = 88,
 	WORK_VDEEP_COUNT = 96,     // two words: windows of more than VDEEP_MINS strings the very deep stage read / handed on (for dacc_timing)
-	WORK_WORDS = 104 };
+	WORK_XDEEP = 104,
+	WORK_XDEEP_COUNT = 112,    // two words: windows of more than VDEEP_MINS strings the deepest stage read / handed on (for dacc_timing)
+	WORK_WORDS = 120 };
 
 // The stages, in the order they run; their place in this table is their place in BatchPlan::stageCaps, TierPipeline and dacc_ctx::st.
-enum TierId { ID_T0, ID_T7, ID_SLOT0, ID_SLOT1, ID_DENSE, ID_DEEP, ID_SLOT2, ID_LAST, ID_VDEEP, ID_LONG, TIER_NSTAGES };
+enum TierId { ID_T0, ID_T7, ID_SLOT0, ID_SLOT1, ID_DENSE, ID_DEEP, ID_SLOT2, ID_LAST, ID_VDEEP, ID_XDEEP, ID_LONG, TIER_NSTAGES };
 enum { TIER_NSLOTS = 3, TIER_NONE = 255, TIER_SHALLOW_FIRST = 1 };      // (the first slot's main tier of shallow batches: a batch whose windows mostly overflow its strings / instances is deep)
 enum : uint32_t { VDEEP_MINS = 250 };      // the very deep stage takes the windows with more strings than this (= FastTier<15>::mins = FastTier<13>::maxs, fast_window.hpp)
+enum : uint32_t { XDEEP_MINS = 1000 };     // the deepest stage is resolved for a batch with a window of more strings than this (= FastTier<15>::maxs); its tier takes what has more than VDEEP_MINS
 struct TierStage { uint8_t tier[3] /* in a shallow, deep, wide batch */, slot, role; int8_t tiersbit /* bit of DACC_TIERS */; uint32_t flags, work; };
 static TierStage const TIER_CHAIN[TIER_NSTAGES] = {
 	{ { 0, TIER_NONE, TIER_NONE }, 0, ROLE_FRONT, 3, STAGE_PREPASS, WORK_T0 },
@@ -109,6 +124,7 @@ static TierStage const TIER_CHAIN[TIER_NSTAGES] = {
 	{ { 3, 3, 9 }, 2, ROLE_MAIN, 2, GATE_TABFIT, WORK_SLOT2 },
 	{ { 13, 13, 14 }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_LAST, WORK_LAST },
 	{ { 15, 15, TIER_NONE }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_VDEEP, WORK_VDEEP },
+	{ { 16, 16, TIER_NONE }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_XDEEP, WORK_XDEEP },
 	// (tier 5 holds no wide window: a wide batch's second stream is the generic engine alone, at its own occupancy instead of a CU's LDS per wavefront)
 	{ { 5, 5, TIER_NONE }, 0, ROLE_LONG, 2, GATE_TABFIT, 0 } };
 static TierId const TIER_MAIN[TIER_NSLOTS] = { ID_SLOT0, ID_SLOT1, ID_SLOT2 };
@@ -119,10 +135,12 @@ static inline bool stageRuns(TierStage const & st, bool const deep, bool const w
 static inline bool lastAsSlot2() { char const * const e = getenv("DACC_LAST_AS_SLOT2"); return e && e[0] == '1'; }
 // DACC_VDEEP_AS_SLOT2=1: the third slot's main tier of shallow and deep batches is the very deep stage's tier (a wide batch keeps tier 9)
 static inline bool vdeepAsSlot2() { char const * const e = getenv("DACC_VDEEP_AS_SLOT2"); return e && e[0] == '1'; }
+// DACC_XDEEP_AS_SLOT2=1: the same with the deepest stage's tier
+static inline bool xdeepAsSlot2() { char const * const e = getenv("DACC_XDEEP_AS_SLOT2"); return e && e[0] == '1'; }
 static inline uint32_t stageTier(TierStage const & st, bool const deep, bool const wide)
 {
 	bool const slot2 = &st == &TIER_CHAIN[ID_SLOT2];
-	TierStage const & t = (slot2 && lastAsSlot2()) ? TIER_CHAIN[ID_LAST] : ((slot2 && !wide && vdeepAsSlot2()) ? TIER_CHAIN[ID_VDEEP] : st);
+	TierStage const & t = (slot2 && lastAsSlot2()) ? TIER_CHAIN[ID_LAST] : ((slot2 && !wide && vdeepAsSlot2()) ? TIER_CHAIN[ID_VDEEP] : ((slot2 && !wide && xdeepAsSlot2()) ? TIER_CHAIN[ID_XDEEP] : st));
 	return (wide && t.tier[2] != TIER_NONE) ? t.tier[2] : (t.tier[deep] != TIER_NONE ? t.tier[deep] : t.tier[0]);
 }
 
@@ -138,7 +156,9 @@ struct TierSwitches
 	bool last_as_slot2;       // DACC_LAST_AS_SLOT2=1: tier 13 / 14 as the third slot's main tier, no last stage
 	bool vdeeptier;           // DACC_VDEEP_TIER=0: no very deep stage (windows of more than 250 strings run in the generic engine, as before that stage)
 	bool vdeep_as_slot2;      // DACC_VDEEP_AS_SLOT2=1: tier 15 as the third slot's main tier of shallow and deep batches, no very deep stage
-	bool conflict() const { return last_as_slot2 && vdeep_as_slot2; }      // both want the third slot: dacc_create refuses
+	bool xdeeptier;           // DACC_XDEEP_TIER=0: no deepest stage (windows of more than 1000 strings run in the generic engine, as before that stage)
+	bool xdeep_as_slot2;      // DACC_XDEEP_AS_SLOT2=1: tier 16 as the third slot's main tier of shallow and deep batches, no deepest stage
+	bool conflict() const { return static_cast<int>(last_as_slot2) + static_cast<int>(vdeep_as_slot2) + static_cast<int>(xdeep_as_slot2) > 1; }      // more than one wants the third slot: dacc_create refuses
 	bool long128;             // DACC_LONG128=0: windows with a string of 65 ... 128 bases run in tier 5 on the second stream (rounds 3-5)
 	bool hand;                // DACC_HAND=0: no hand-over buffer, every hand-over restarts from the strings
 	uint32_t t0inst, t7inst;  // DACC_T0INST / DACC_T7INST: size-class thresholds (k-mer instances) of tiers 0 and 7
@@ -151,7 +171,7 @@ static inline TierSwitches readTierSwitches()
 	TierSwitches S;
 	{ char const * const e = getenv("DACC_NOFAST"); S.nofast = e && e[0] == '1'; }
 	S.tiers = num("DACC_TIERS",31);
-	S.widetier = !off("DACC_WIDE_TIER"); S.dense = !off("DACC_DENSE_TIER"); S.deepwin = !off("DACC_DEEP_TIER"); S.lasttier = !off("DACC_LAST_TIER"); S.last_as_slot2 = lastAsSlot2(); S.vdeeptier = !off("DACC_VDEEP_TIER"); S.vdeep_as_slot2 = vdeepAsSlot2(); S.long128 = !off("DACC_LONG128"); S.hand = !off("DACC_HAND");
+	S.widetier = !off("DACC_WIDE_TIER"); S.dense = !off("DACC_DENSE_TIER"); S.deepwin = !off("DACC_DEEP_TIER"); S.lasttier = !off("DACC_LAST_TIER"); S.last_as_slot2 = lastAsSlot2(); S.vdeeptier = !off("DACC_VDEEP_TIER"); S.vdeep_as_slot2 = vdeepAsSlot2(); S.xdeeptier = !off("DACC_XDEEP_TIER"); S.xdeep_as_slot2 = xdeepAsSlot2(); S.long128 = !off("DACC_LONG128"); S.hand = !off("DACC_HAND");
 	S.t0inst = num("DACC_T0INST",T0INST_DEFAULT); S.t7inst = num("DACC_T7INST",T7INST_DEFAULT);
 	S.lds_t1 = num("DACC_LDS_T1",0); S.lds_t0 = num("DACC_LDS_T0",0);
 	return S;
@@ -167,7 +187,7 @@ static inline uint32_t tierGrid(uint32_t const ldsbytes, uint64_t const nwindows
 }
 
 // Launch geometry of a device-memory tier (FastCaps::gmem): no LDS and 512 registers, so up to four workgroups per CU would fit; what bounds the
-// grid is the slab, gbytes per workgroup (tier 13: 1 059 840 B, tier 14: 1 125 632 B, tier 15: see DESIGN 3.2), kept to TIER_GMEM_SLAB = 256 MiB per context:
+// grid is the slab, gbytes per workgroup (tier 13: 1 059 840 B, tier 14: 1 125 632 B, tiers 15 and 16: see DESIGN 3.2), kept to TIER_GMEM_SLAB = 256 MiB per context:
 // 256 MiB / 1 059 840 B = 253 -> 248 workgroups (a multiple of 8, one share per XCD), 232 for tier 14 -- about one per CU, whose working sets
 // (1 MB each) then share the L2 of their XCD with no more than 31 others.  The stage sees a few windows per batch, hundreds on high-error data;
 // a small batch gets a workgroup per window and a slab to match.
@@ -196,8 +216,8 @@ struct TierPipeline
 
 // fastpath: the caller's own conditions (not switched off, a model table that fits 32 bit fixed point).  capsOf(id): the plan's capacities
 // of a stage (BatchPlan::stageCaps); the measurement switches DACC_LDS_T1 / DACC_LDS_T0 raise the LDS sizes in them.
-// maxstrings: strings of the deepest window of the batch (BatchPlan::maxstrings); the very deep stage is resolved only for a batch that has a
-// window for it -- a caller that walks the slots only (the emulation harness) leaves it out and sees no such stage.
+// maxstrings: strings of the deepest window of the batch (BatchPlan::maxstrings); the very deep stage and the deepest stage are resolved only for a batch that has a
+// window for them -- a caller that walks the slots only (the emulation harness) leaves it out and sees no such stage.
 template<typename C>
 static inline TierPipeline resolveTiers(TierSwitches const & S, bool const fastpath, bool const deep, bool const wide, uint32_t const nrows, uint32_t const nsup, uint32_t const w, C && capsOf,
 	uint32_t const maxstrings = 0)
@@ -215,13 +235,15 @@ static inline TierPipeline resolveTiers(TierSwitches const & S, bool const fastp
 			&& (!(st.flags & GATE_TABFIT) || static_cast<uint64_t>(nrows+1)*(nsup+1) <= F.tabcap)
 			&& (!(st.flags & GATE_T7_ABOVE_T0) || S.t7inst > S.t0inst) && (!(st.flags & GATE_DENSE) || S.dense) && (!(st.flags & GATE_DEEP) || S.deepwin)
 			&& (!(st.flags & GATE_LAST) || (S.lasttier && !S.last_as_slot2))
-			&& (!(st.flags & GATE_VDEEP) || (S.vdeeptier && !S.vdeep_as_slot2 && maxstrings > VDEEP_MINS));
+			&& (!(st.flags & GATE_VDEEP) || (S.vdeeptier && !S.vdeep_as_slot2 && maxstrings > VDEEP_MINS))
+			&& (!(st.flags & GATE_XDEEP) || (S.xdeeptier && !S.xdeep_as_slot2 && maxstrings > XDEEP_MINS));
 	};
 	{ FastCaps & F = capsOf(ID_SLOT0); if ( S.lds_t1 > F.ldsbytes && S.lds_t1 <= TIER_LDS_CU ) F.ldsbytes = S.lds_t1; }
 	{ FastCaps & F = capsOf(ID_T0); if ( S.lds_t0 > F.ldsbytes && S.lds_t0 <= TIER_LDS_CU ) F.ldsbytes = S.lds_t0; }
 	for ( uint32_t i = 0; i < TIER_NSTAGES; ++i ) { R.tier[i] = stageTier(TIER_CHAIN[i],deep,wide); if ( TIER_CHAIN[i].role != ROLE_FRONT ) R.ok[i] = gated(i); }
 	R.ok[ID_LAST] = R.ok[ID_LAST] && R.anytier();      // it reads what a slot handed on: no slot, no last stage (generic-only configurations stay generic-only)
 	R.ok[ID_VDEEP] = R.ok[ID_VDEEP] && R.anytier();
+	R.ok[ID_XDEEP] = R.ok[ID_XDEEP] && R.anytier();
 	// the front tiers, in chain order (a front tier stands before the main tier of its slot)
 	for ( uint32_t i = 0; i < TIER_NSTAGES; ++i )
 	{

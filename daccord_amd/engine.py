@@ -145,7 +145,7 @@ class Engine:
         self._chk(self.L.dacc_rerun_resident(self.h))
 
     def timing(self):
-        """The timing record of the last run; the fields behind the first TIMING_SIZE_V1 bytes (deep_ms, deep_windows, deep_out, last_ms, last_windows, last_out, vdeep_ms, vdeep_windows, vdeep_out, emit_ms) stay zero
+        """The timing record of the last run; the fields behind the first TIMING_SIZE_V1 bytes (deep_ms, deep_windows, deep_out, last_ms, last_windows, last_out, vdeep_ms, vdeep_windows, vdeep_out, xdeep_ms, xdeep_windows, emit_ms) stay zero
         with a library that has no dacc_last_timing2."""
         t = DaccTiming()
         if hasattr(self.L, "dacc_last_timing2"):

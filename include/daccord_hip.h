@@ -191,23 +191,27 @@ typedef struct dacc_timing {
 	float tier10_ms;         /* round 6, the dense-graph tier of shallow batches: k_window_fast<10> (2 wavefronts per CU) between tier 6 and tier 3, the part of tier_ms[2] in front of k_window_fast<3>; 0 if it did not run */
 	uint32_t tier10_out;     /* windows tier 10 handed on to tier 3 (it ran tier_out[1] windows) */
 	uint32_t tier10_ran;     /* 1: tier 10 ran in this pass (tier_out[1] went to it, not to tier 3) */
-	uint32_t pad2_;
+	uint32_t xdeep_out;      /* the deepest stage (below): windows of more than 250 strings it handed on to k_window (more than 2000 strings, a k-mer seen more than 4095 times, a table
+	                            beyond its capacities).  It took the place of a pad word (always 0 before): the record keeps its size */
 	/* ---- everything above: DACC_TIMING_SIZE_V1 bytes, what dacc_last_timing fills ---- */
 	float deep_ms;           /* the deep-window tier: k_window_fast<12> (1 wavefront per CU; windows of 97 ... 250 strings) in front of k_window_fast<3>, a part of tier_ms[2]; 0 if it did not run */
 	uint32_t deep_windows;   /* windows of more than 96 strings that finished in tier 12 */
 	uint32_t deep_out;       /* windows of more than 96 strings tier 12 handed on (more than 250 strings, a k-mer seen more than 255 times, a graph or pool beyond its capacities): they end in the generic engine */
-	uint32_t pad3_;
+	float xdeep_ms;          /* the deepest stage: k_window_fast<16> (layout in device memory, windows of 1001 ... 2000 strings and what <15> overflowed on), behind the very deep stage and
+	                            in front of k_window; launched only in a shallow or deep batch whose deepest window has more than 1000 strings; not a part of tier_ms[].  0 if it did not run
+	                            (no such window, a wide batch, DACC_XDEEP_TIER=0, DACC_XDEEP_AS_SLOT2=1, no slot ran, no memory for its slab).  In the place of a pad word, like xdeep_out */
 	/* the last stage: k_window_fast<13> (wide batches: <14>), the tier whose layout lives in device memory, behind the slots and in front of k_window; not a part of tier_ms[] */
 	float last_ms;           /* its kernel; 0 if it did not run (DACC_LAST_TIER=0, DACC_LAST_AS_SLOT2=1, no slot ran, no memory for its slab) */
 	uint32_t last_windows;   /* windows that finished in it */
 	uint32_t last_out;       /* windows it handed on (more than 250 strings, w = 128, a string of more than 128 bases, a table beyond its capacities): what k_window ran --
 	                            where the very deep stage ran, what that stage read (k_window then ran last_out - vdeep_windows) */
-	uint32_t pad4_;
+	uint32_t xdeep_windows;  /* windows of more than 250 strings that finished in the deepest stage (in the place of a pad word) */
 	/* the very deep stage: k_window_fast<15> (layout in device memory, windows of 251 ... 1000 strings), behind the last stage and in front of k_window; launched only in a
 	   shallow or deep batch whose deepest window has more than 250 strings; not a part of tier_ms[] */
 	float vdeep_ms;          /* its kernel; 0 if it did not run (no window of more than 250 strings in the batch, a wide batch, DACC_VDEEP_TIER=0, DACC_VDEEP_AS_SLOT2=1, no slot ran, no memory for its slab) */
 	uint32_t vdeep_windows;  /* windows of more than 250 strings that finished in it */
-	uint32_t vdeep_out;      /* windows of more than 250 strings it handed on to k_window (more than 1000 strings, a k-mer seen more than 1023 times, a table beyond its capacities) */
+	uint32_t vdeep_out;      /* windows of more than 250 strings it handed on (more than 1000 strings, a k-mer seen more than 1023 times, a table beyond its capacities): what k_window ran --
+	                            where the deepest stage ran, what that stage read (vdeep_out = xdeep_windows + xdeep_out; k_window then ran xdeep_out of them) */
 	float emit_ms;           /* k_emit: the consensus -> A alignment of the tiers' windows (w <= 64), one lane per window, behind all window kernels and in front of the
 	                            vote; a part of vote_ms, not of window_ms.  It took the place of a pad word (always 0 before): the record keeps its size */
 } dacc_timing;
