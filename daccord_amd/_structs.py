@@ -48,6 +48,13 @@ class DaccTiming(C.Structure):
                 ("emit_ms", C.c_float)]
 
 
+class DaccTimingLong(C.Structure):
+    """dacc_timing as it is since the long string stage: DaccTiming (176 bytes, unchanged) and the 16 bytes appended behind emit_ms"""
+    _fields_ = DaccTiming._fields_ + [
+        # the long string stage (k_window_fast<17>: strings of 129 ... 255 bases, second stream of a wide batch, in front of the generic engine there)
+        ("longstr_ms", C.c_float), ("longstr_windows", C.c_uint32), ("longstr_out", C.c_uint32), ("pad2_", C.c_uint32)]
+
+
 TIMING_SIZE_V1 = 128
 
 

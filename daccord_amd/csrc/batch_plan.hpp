@@ -65,7 +65,7 @@ struct BatchPlan
 	FastCaps ftier0, ftier7;  // front tiers of the first slot (size classes of shallow batches)
 	FastCaps ftierD;          // front tier of the last slot (dense graphs: tier 10, deep batches 11)
 	FastCaps ftierX;          // second front tier of the last slot (deep windows, 97 ... 250 strings: tier 12)
-	FastCaps ftierL;          // tier 5: windows with a string of 65..128 bases (second stream, before the generic engine)
+	FastCaps ftierL;          // the second stream's tier, in front of the generic engine there: tier 5 (shallow and deep batches: a string of 65..128 bases, inside k_window_long) / tier 17 (wide batches: a string of 129..255 bases, a kernel of its own)
 	FastCaps ftierZ;          // the last stage, behind the slots and in front of the generic engine (layout in device memory: tier 13, wide batches 14)
 	FastCaps ftierV;          // the very deep stage behind it (windows of 251 ... 1000 strings, layout in device memory: tier 15)
 	FastCaps ftierW;          // the deepest stage behind that (windows of 1001 ... 2000 strings and what tier 15 overflowed on, layout in device memory: tier 16)

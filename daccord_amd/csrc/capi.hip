@@ -403,12 +403,13 @@ struct dacc_ctx
 	DevBuf<uint8_t> d_wrec; DevBuf<WindowOut> d_wout; DevBuf<uint8_t> d_arena;
 	DevBuf<uint8_t> d_has, d_oc, d_outsym, d_pilebad; DevBuf<uint16_t> d_ld0; DevBuf<uint32_t> d_ocs, d_nfrag, d_err;
 	DevBuf<VoteFragment> d_frags; DevBuf<uint64_t> d_fragbase; DevBuf<uint64_t> d_prof;
-	DevBuf<uint64_t> d_vst; DevBuf<uint32_t> d_tab32; DevBuf<uint8_t> d_gslab, d_lastslab /* the last stage's own slab (layout included) */, d_vdeepslab /* the very deep stage's, allocated by the first batch with a window of more than 250 strings */, d_xdeepslab /* the deepest stage's, allocated by the first batch with a window of more than 1000 strings */; DevBuf<uint32_t> d_retry[TIER_NSLOTS], d_work, d_gearly, d_pregen, d_pregen2, d_pregenlist; DevBuf<uint8_t> d_arena2; DevBuf<uint64_t> d_trslab; DevBuf<uint32_t> d_small; DevBuf<uint64_t> d_hand; DevBuf<uint32_t> d_handctr; uint32_t handcap; uint64_t handwant, nruns; bool nohand, oom; bool tier7_adapt_off; int env_t7adapt; int env_trdyn;
+	DevBuf<uint64_t> d_vst; DevBuf<uint32_t> d_tab32; DevBuf<uint8_t> d_gslab, d_lastslab /* the last stage's own slab (layout included) */, d_vdeepslab /* the very deep stage's, allocated by the first batch with a window of more than 250 strings */, d_xdeepslab /* the deepest stage's, allocated by the first batch with a window of more than 1000 strings */, d_longslab /* the long string stage's (wide batches, second stream), allocated by the first pass whose second stream has a window */; DevBuf<uint32_t> d_longhand[2]; /* what that stage hands on to k_window_long, one list per list of the second stream */ DevBuf<uint32_t> d_retry[TIER_NSLOTS], d_work, d_gearly, d_pregen, d_pregen2, d_pregenlist; DevBuf<uint8_t> d_arena2; DevBuf<uint64_t> d_trslab; DevBuf<uint32_t> d_small; DevBuf<uint64_t> d_hand; DevBuf<uint32_t> d_handctr; uint32_t handcap; uint64_t handwant, nruns; bool nohand, oom; bool tier7_adapt_off; int env_t7adapt; int env_trdyn;
 	// the LDS tiers (tier_pipeline.hpp): their switches, the resolved chain of the current batch (capacities: BP.stageCaps), by TierId and the launch state of its stages.
 	// A main tier hands on through d_retry[slot] and is done at evslot[slot]; `handon` and `done` are those of the front tiers.
 	TierSwitches sw; TierPipeline TP;
 	struct Stage { bool ran; uint32_t grid; DevBuf<uint32_t> handon; hipEvent_t done; uint32_t const * in; /* the list it read in the last pass */ } st[TIER_NSTAGES];
 	uint32_t nlong[2];      // windows on the two lists of the second stream in the current pass (pre-scan, first tier's generic-only windows)
+	bool longran[2]; hipEvent_t evLong[4];      // the long string stage (tier 17): did it run over list i in the current pass, and the events around its two launches on the second stream
 	uint32_t retry_grid, early_grid; int sched;
 	uint32_t tr_grid, tr_lds, tr_words, tr_lanes, trace_bytes, win_grid;
 	int env_sched, env_dbgretry;     // debugging knobs, read once in dacc_create
@@ -467,14 +468,14 @@ int dacc_create(dacc_ctx ** out, dacc_params const * p)
 	if ( hipSetDevice(p->device) != hipSuccess ) return DACC_ENODEV;
 	dacc_ctx * c = new (std::nothrow) dacc_ctx;
 	if ( !c ) return DACC_ENOMEM;
-	c->par = *p; c->device = p->device; c->haveprofile = c->havedb = c->havebatch = false; c->est_cor = 0; c->nlong[0] = c->nlong[1] = 0; c->handcap = 0; c->handwant = 0; c->nruns = 0; c->nohand = false; c->oom = false;
+	c->par = *p; c->device = p->device; c->haveprofile = c->havedb = c->havebatch = false; c->est_cor = 0; c->nlong[0] = c->nlong[1] = 0; c->longran[0] = c->longran[1] = false; c->handcap = 0; c->handwant = 0; c->nruns = 0; c->nohand = false; c->oom = false;
 	std::memset(&c->timing,0,sizeof(c->timing));
 	// launch geometry of the LDS tiers: set by every batch that uses them; a generic-only batch (DACC_NOFAST, w >= 64, a model table no
 	// tier holds) reads retry_grid in its scratch retry and must not find an indeterminate value there
 	c->retry_grid = c->early_grid = c->win_grid = 0; c->tier7_adapt_off = false; c->sched = 0;
 	c->tr_grid = c->tr_lds = c->tr_words = c->tr_lanes = c->trace_bytes = 0;
 	{
-		c->sw = readTierSwitches();      // DACC_NOFAST, DACC_TIERS, DACC_WIDE_TIER, DACC_DENSE_TIER, DACC_DEEP_TIER, DACC_LAST_TIER, DACC_LAST_AS_SLOT2, DACC_VDEEP_TIER, DACC_VDEEP_AS_SLOT2, DACC_XDEEP_TIER, DACC_XDEEP_AS_SLOT2, DACC_LONG128, DACC_HAND, DACC_T0INST, DACC_T7INST, DACC_LDS_T1, DACC_LDS_T0
+		c->sw = readTierSwitches();      // DACC_NOFAST, DACC_TIERS, DACC_WIDE_TIER, DACC_DENSE_TIER, DACC_DEEP_TIER, DACC_LAST_TIER, DACC_LAST_AS_SLOT2, DACC_VDEEP_TIER, DACC_VDEEP_AS_SLOT2, DACC_XDEEP_TIER, DACC_XDEEP_AS_SLOT2, DACC_LONGSTR_TIER, DACC_LONG128, DACC_HAND, DACC_T0INST, DACC_T7INST, DACC_LDS_T1, DACC_LDS_T0
 		char const * sc = getenv("DACC_SCHED"); c->env_sched = sc ? atoi(sc) : 1;      // bit 0: LDS tiers pull work from a counter, bit 1: generic engine too
 		{ char const * td = getenv("DACC_TRACE_DYN"); c->env_trdyn = !(td && td[0] == '0'); }      // 0: k_trace walks its blocks with a fixed stride (rounds 1-5)
 		char const * ta = getenv("DACC_T7_ADAPT"); c->env_t7adapt = !(ta && ta[0] == '0');      // 0: tier 7 stays on whatever it hands on
@@ -485,6 +486,7 @@ int dacc_create(dacc_ctx ** out, dacc_params const * p)
 	hipEventCreateWithFlags(&c->evFirstTier,hipEventDisableTiming); hipEventCreateWithFlags(&c->evEarlyGeneric,hipEventDisableTiming); hipEventCreateWithFlags(&c->evPrescan,hipEventDisableTiming);
 	for ( int i = 0; i < 6; ++i ) hipEventCreate(&c->ev[i]);
 	for ( int i = 0; i < 2; ++i ) hipEventCreate(&c->evEmit[i]);
+	for ( int i = 0; i < 4; ++i ) hipEventCreate(&c->evLong[i]);
 	for ( int i = 0; i < TIER_NSLOTS; ++i ) hipEventCreate(&c->evslot[i]);
 	for ( int i = 0; i < TIER_NSTAGES; ++i ) { hipEventCreate(&c->st[i].done); c->st[i].ran = false; c->st[i].grid = 0; c->st[i].in = 0; }
 	*out = c;
@@ -500,9 +502,10 @@ void dacc_destroy(dacc_ctx * c)
 	c->d_bps.release(); c->d_boff.release(); c->d_rlen.release();
 	c->d_piles.release(); c->d_ovl.release(); c->d_ovl_pile.release(); c->d_trace.release(); c->d_blk_ovl.release(); c->d_blk_b0.release(); c->d_wt_b.release(); c->d_wt_e.release();
 	c->d_wrec.release(); c->d_wout.release(); c->d_arena.release();
-	c->h_outsym.release(); c->d_pilebad.release(); c->d_has.release(); c->d_oc.release(); c->d_outsym.release(); c->d_ld0.release(); c->d_ocs.release(); c->d_nfrag.release(); c->d_err.release(); c->d_frags.release(); c->d_fragbase.release(); c->d_prof.release(); c->d_vst.release(); c->d_tab32.release(); c->d_gslab.release(); c->d_lastslab.release(); c->d_vdeepslab.release(); c->d_xdeepslab.release(); for ( int i = 0; i < 3; ++i ) c->d_retry[i].release(); c->d_work.release(); c->d_gearly.release(); c->d_pregen.release(); c->d_pregen2.release(); c->d_pregenlist.release(); c->d_arena2.release(); c->d_trslab.release(); c->d_hand.release(); c->d_handctr.release();
+	c->h_outsym.release(); c->d_pilebad.release(); c->d_has.release(); c->d_oc.release(); c->d_outsym.release(); c->d_ld0.release(); c->d_ocs.release(); c->d_nfrag.release(); c->d_err.release(); c->d_frags.release(); c->d_fragbase.release(); c->d_prof.release(); c->d_vst.release(); c->d_tab32.release(); c->d_gslab.release(); c->d_lastslab.release(); c->d_vdeepslab.release(); c->d_xdeepslab.release(); c->d_longslab.release(); c->d_longhand[0].release(); c->d_longhand[1].release(); for ( int i = 0; i < 3; ++i ) c->d_retry[i].release(); c->d_work.release(); c->d_gearly.release(); c->d_pregen.release(); c->d_pregen2.release(); c->d_pregenlist.release(); c->d_arena2.release(); c->d_trslab.release(); c->d_hand.release(); c->d_handctr.release();
 	for ( int i = 0; i < 6; ++i ) hipEventDestroy(c->ev[i]);
 	for ( int i = 0; i < 2; ++i ) hipEventDestroy(c->evEmit[i]);
+	for ( int i = 0; i < 4; ++i ) hipEventDestroy(c->evLong[i]);
 	hipStreamDestroy(c->stream); hipStreamDestroy(c->stream2); hipEventDestroy(c->evFirstTier); hipEventDestroy(c->evEarlyGeneric); hipEventDestroy(c->evPrescan); for ( int i = 0; i < TIER_NSLOTS; ++i ) hipEventDestroy(c->evslot[i]);
 	c->d_small.release(); for ( int i = 0; i < TIER_NSTAGES; ++i ) { hipEventDestroy(c->st[i].done); c->st[i].handon.release(); }
 	delete c;
@@ -642,7 +645,11 @@ static int runDevice(dacc_ctx * c)
 #if defined(DACC_LEDGER)
 			FL.ledger = 0;
 #endif
-			if ( !TP.ok[ID_LONG] ) FL.F.ldsbytes = 0;
+			// (k_window_long runs tier 5 in its own LDS; a wide batch's ID_LONG is tier 17, a kernel of its own in front of it -- k_window_long then is the generic
+			// engine alone and never sees that tier's capacities)
+			bool const long5 = TP.ok[ID_LONG] && TP.tier[ID_LONG] == 5;
+			if ( TP.tier[ID_LONG] != 5 ) FL.F = tierCaps(5,c->H.nrows,c->H.nsup);
+			if ( !long5 ) FL.F.ldsbytes = 0;
 			// a launch the device refuses (the LDS of a whole CU) falls back to the generic engine alone, for good
 			// (round 5) The length of a list is fetched before its launch and the grid follows it: an empty list -- the rule at the default
 			// window -- is not launched at all, a list of three windows asks for three CUs' worth of LDS instead of 256.  Rounds 1-4 queued
@@ -652,29 +659,54 @@ static int runDevice(dacc_ctx * c)
 			// list, and only after every tier and the generic kernel have been queued on the main stream: round 5 synchronised the main
 			// stream in the middle of the chain, which kept the host -- and a second context's batches on the same device -- out of the
 			// queue until the first tier had retired.
-			auto const launchLong = [&](uint32_t const * const lst, uint32_t & nlist, hipEvent_t const filled) -> int
+			auto const launchLong = [&](uint32_t const * const lst, uint32_t & nlist, hipEvent_t const filled, uint32_t const which) -> int
 			{
 				nlist = 0;
 				HIPCHK(hipStreamWaitEvent(c->stream2,filled,0));
 				HIPCHK(hipMemcpyAsync(&nlist,lst,sizeof(uint32_t),hipMemcpyDeviceToHost,c->stream2));
 				HIPCHK(hipStreamSynchronize(c->stream2));
 				if ( !nlist ) return DACC_OK;
+				uint32_t const * glist = lst;      // what the generic engine of this stream reads
+				if ( TP.ok[ID_LONG] && TP.tier[ID_LONG] != 5 )
+				{
+					// the long string stage of a wide batch (tier 17: strings of up to 255 bases, layout in device memory): a kernel of its own over the list, no
+					// LDS, a slab of grid x gbytes and a hand-on list, both allocated here, where the list is known not to be empty (the second stream is idle: the
+					// copy above has been waited for).  Optional like the last stage's slab: without memory for it the batch runs without the stage
+					FastCaps const & F = BP.stageCaps(ID_LONG);
+					uint32_t const grid = tierGridGmem(F.gbytes,nlist);
+					hipError_t e = c->d_longhand[which].ensure(BP.nwindows+2);
+					if ( e == hipSuccess ) e = c->d_longslab.ensure(static_cast<size_t>(grid)*F.gbytes + 256);
+					if ( e == hipErrorOutOfMemory ) { (void)hipGetLastError(); c->d_longslab.release(); TP.ok[ID_LONG] = false; }
+					else
+					{
+						HIPCHK(e);
+						FastBatch FS = FL; FS.F = F; FS.W.pregen = 0; FS.retry = c->d_longhand[which].p; FS.gearly = 0; FS.gslab = c->d_longslab.p; FS.gstride = F.gbytes;
+						uint32_t * const wk = (c->sched&1) ? c->d_work.p + TIER_CHAIN[ID_LONG].work + 8u*which : static_cast<uint32_t *>(0);
+						HIPCHK(hipMemsetAsync(FS.retry,0,sizeof(uint32_t),c->stream2));
+						if ( wk ) HIPCHK(hipMemsetAsync(wk,0,8*sizeof(uint32_t),c->stream2));
+						HIPCHK(hipEventRecord(c->evLong[2*which],c->stream2));
+						hipLaunchKernelGGL(fastKernel(TP.tier[ID_LONG]),dim3(grid),dim3(64),0,c->stream2,FS,lst,wk);
+						HIPCHK(hipEventRecord(c->evLong[2*which+1],c->stream2));
+						c->longran[which] = true;
+						glist = FS.retry;      // (its length is read on the device: workgroups beyond it leave at once)
+					}
+				}
 				uint32_t const grid = nlist < c->early_grid ? nlist : c->early_grid;
 				(void)hipGetLastError();
-				hipLaunchKernelGGL(k_window_long,dim3(grid),dim3(64),FL.F.ldsbytes,c->stream2,FL,c->d_err.p,lst);
+				hipLaunchKernelGGL(k_window_long,dim3(grid),dim3(64),FL.F.ldsbytes,c->stream2,FL,c->d_err.p,glist);
 				if ( FL.F.ldsbytes && hipGetLastError() != hipSuccess )
 				{
 					TP.ok[ID_LONG] = false; FL.F.ldsbytes = 0;
-					hipLaunchKernelGGL(k_window_long,dim3(grid),dim3(64),0,c->stream2,FL,c->d_err.p,lst);
+					hipLaunchKernelGGL(k_window_long,dim3(grid),dim3(64),0,c->stream2,FL,c->d_err.p,glist);
 				}
 				return DACC_OK;
 			};
-			c->nlong[0] = c->nlong[1] = 0;
+			c->nlong[0] = c->nlong[1] = 0; c->longran[0] = c->longran[1] = false;
 			WB.pregen = c->d_pregen.p;
 			HIPCHK(hipMemsetAsync(c->d_gearly.p,0,sizeof(uint32_t),s));
 			HIPCHK(hipMemsetAsync(c->d_handctr.p,0,sizeof(uint32_t),s));
 			bool early = false;
-			HIPCHK(hipMemsetAsync(c->d_work.p,0,WORK_WORDS*sizeof(uint32_t),s));
+			HIPCHK(hipMemsetAsync(c->d_work.p,0,WORK_LONGSTR*sizeof(uint32_t),s));      // (the long string stage's counters are the second stream's: cleared there, in front of its launch)
 			// the chain (tier_pipeline.hpp): every slot takes the windows the previous one handed over (list = 0: all windows)
 			auto const work = [&](uint32_t const off) { return (c->sched&1) ? c->d_work.p+off : static_cast<uint32_t *>(0); };
 			uint32_t const * list = 0; int lastslot = -1;
@@ -793,8 +825,8 @@ static int runDevice(dacc_ctx * c)
 			hipLaunchKernelGGL(k_window,dim3(c->retry_grid),dim3(64),0,s,WB,c->d_err.p,list,(c->sched&2) ? c->d_work.p+WORK_GENERIC : static_cast<uint32_t *>(0));
 			// the second stream: the pre-scan's list (a string of more than 64 bases) as soon as the pre-scan is done, the first tier's
 			// generic-only windows behind the first tier; the main stream's queue is full by now
-			{ int const rc = launchLong(static_cast<uint32_t const *>(c->d_pregenlist.p),c->nlong[0],c->evPrescan); if ( rc ) return rc; }
-			if ( early ) { int const rc = launchLong(static_cast<uint32_t const *>(c->d_gearly.p),c->nlong[1],c->evFirstTier); if ( rc ) return rc; }
+			{ int const rc = launchLong(static_cast<uint32_t const *>(c->d_pregenlist.p),c->nlong[0],c->evPrescan,0); if ( rc ) return rc; }
+			if ( early ) { int const rc = launchLong(static_cast<uint32_t const *>(c->d_gearly.p),c->nlong[1],c->evFirstTier,1); if ( rc ) return rc; }
 			// everything the second stream ran (pre-scan list, first tier's generic-only windows) must be done before the vote
 			HIPCHK(hipEventRecord(c->evEarlyGeneric,c->stream2));
 			HIPCHK(hipStreamWaitEvent(s,c->evEarlyGeneric,0));
@@ -944,6 +976,17 @@ static int runDevice(dacc_ctx * c)
 		HIPCHK(hipStreamSynchronize(s));
 		c->timing.deep_out = cnt[1]; c->timing.deep_windows = cnt[0] > cnt[1] ? cnt[0] - cnt[1] : 0u;
 	}
+	// the long string stage (wide batches, second stream): what it read is what the second stream read (long_windows), what it handed on is what k_window_long ran
+	c->timing.longstr_ms = 0; c->timing.longstr_windows = 0; c->timing.longstr_out = 0; c->timing.pad2_ = 0;
+	if ( !(TP.usefast && BP.nwindows && TP.anytier()) ) c->longran[0] = c->longran[1] = false;
+	for ( int i = 0; i < 2; ++i )
+		if ( c->longran[i] )
+		{
+			uint32_t nout = 0; float lms = 0;
+			HIPCHK(hipMemcpy(&nout,c->d_longhand[i].p,sizeof(uint32_t),hipMemcpyDeviceToHost));
+			hipEventElapsedTime(&lms,c->evLong[2*i],c->evLong[2*i+1]);
+			c->timing.longstr_ms += lms; c->timing.longstr_out += nout; c->timing.longstr_windows += c->nlong[i] > nout ? c->nlong[i] - nout : 0u;
+		}
 	c->pile_status = BP.pile_status; c->pile_errors = BP.pile_errors;
 	if ( herr[0] && BP.piles.size() )
 	{
@@ -1117,7 +1160,7 @@ static int dacc_submit_piles_body(dacc_ctx * c, dacc_pile const * piles, uint64_
 			if ( c->d_hand.cap < static_cast<size_t>(cap)*TP.handwords ) c->handcap = static_cast<uint32_t>(c->d_hand.cap / TP.handwords);     // what an earlier batch left
 			else c->handcap = static_cast<uint32_t>(cap);
 		}
-		if ( TP.ok[ID_LONG] && BP.ftierL.ldsbytes > 64*1024 ) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_window_long),hipFuncAttributeMaxDynamicSharedMemorySize,BP.ftierL.ldsbytes));
+		if ( TP.ok[ID_LONG] && TP.tier[ID_LONG] == 5 && BP.ftierL.ldsbytes > 64*1024 ) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_window_long),hipFuncAttributeMaxDynamicSharedMemorySize,BP.ftierL.ldsbytes));
 		c->retry_grid = boundByArena(wg < 512 ? wg : 512,BP.caps.bytes,8);
 		c->win_grid = c->retry_grid;
 		// generic engine on the second stream (windows with a string of more than 64 bases): a wavefront per window as far
@@ -1170,9 +1213,9 @@ void dacc_release(dacc_ctx * c) { if ( c ) { c->frags.clear(); c->bases.clear();
 // dacc_last_timing: the record as it was when the call got its signature (everything in front of deep_ms), so that a caller compiled against
 // that header is not overrun; dacc_last_timing2 copies as much of today's record as the caller says it has room for
 static_assert(offsetof(dacc_timing,deep_ms) == DACC_TIMING_SIZE_V1,"dacc_last_timing fills the record in front of deep_ms");
-static_assert(offsetof(dacc_timing,vdeep_ms) == 160 && sizeof(dacc_timing) == 176,"the very deep stage's fields are appended behind last_*");
+static_assert(offsetof(dacc_timing,vdeep_ms) == 160 && offsetof(dacc_timing,longstr_ms) == DACC_TIMING_SIZE_V2 && DACC_TIMING_SIZE_V2 == 176 && sizeof(dacc_timing) == 192,"the very deep stage's fields are appended behind last_*, the long string stage's 16 bytes behind emit_ms");
 static_assert(offsetof(dacc_timing,xdeep_ms) == 140 && offsetof(dacc_timing,xdeep_windows) == 156 && offsetof(dacc_timing,xdeep_out) == 124,"the deepest stage's fields take the pad words: the record keeps its size");
-static_assert(offsetof(dacc_timing,emit_ms) == 172,"emit_ms is the last word of the record, where the very deep stage's pad word was");
+static_assert(offsetof(dacc_timing,emit_ms) == 172,"emit_ms is the last word of the first 176 bytes, where the very deep stage's pad word was");
 int dacc_last_timing(dacc_ctx * c, dacc_timing * t)
 {
 	if ( !c || !t ) return DACC_EINVAL;
@@ -1182,7 +1225,10 @@ int dacc_last_timing(dacc_ctx * c, dacc_timing * t)
 int dacc_last_timing2(dacc_ctx * c, dacc_timing * t, size_t size)
 {
 	if ( !c || !t ) return DACC_EINVAL;
-	std::memcpy(static_cast<void *>(t),&c->timing,size < sizeof(dacc_timing) ? size : sizeof(dacc_timing));
+	// the long string stage's 16 bytes behind emit_ms go only to a caller that has room for all of them: a caller built with the 176 byte record that
+	// passes a larger size (its record inside a larger buffer) gets the 176 bytes it knows, as before the record grew
+	size_t const n = size >= sizeof(dacc_timing) ? sizeof(dacc_timing) : (size < DACC_TIMING_SIZE_V2 ? size : static_cast<size_t>(DACC_TIMING_SIZE_V2));
+	std::memcpy(static_cast<void *>(t),&c->timing,n);
 	return DACC_OK;
 }
 

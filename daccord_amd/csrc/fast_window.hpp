@@ -30,7 +30,7 @@
  *  - stretches are looked up by first / last node through small index arrays, the weights of a feasible (stretch,
  *    position) entry carry the weights of its end nodes, candidates are kept as stretch sequences and decoded once.
  *
- * The same code is instantiated for seventeen capacity tiers (FastTier<N> below; the layout FastLds<CT> is a compile time constant,
+ * The same code is instantiated for eighteen capacity tiers (FastTier<N> below; the layout FastLds<CT> is a compile time constant,
  * so every LDS access has an immediate offset).  Which of them a batch runs, in which order and behind which switches, is
  * written down once, in tier_pipeline.hpp.
  *
@@ -52,6 +52,7 @@
  *     14  last stage, wide batches (layout in device memory)          gw      16 / 16 bit       no LDS
  *     15  very deep stage, shallow and deep: 251 ... 1000 strings     gw      16 / 16 bit       no LDS
  *     16  deepest stage, shallow and deep: 1001 ... 2000 strings      gw      16 / 16 bit       no LDS
+ *     17  second stream, wide batches: strings of 129 ... 255 bases   gw      16 / 16 bit       no LDS
  *
  * processWindowFast returns
  * FW_NEXT when a window overflows a tier (flags say what overflowed: 1 instances, 2 nodes, 8 candidates, 16 walk,
@@ -59,7 +60,7 @@
  * 0x20000 popped paths, 0x40000 score intervals), 1024 introsort's depth limit reached in the replayed std::sort (the tiers
  * stop there; the generic engine finishes such a range with libstdc++'s heapsort fallback), 2048 base length, 4096 candidate
  * length / sequence, 8192 gap filling) and FW_GENERIC for shapes the tier does not support (a window wider than it holds, a string
- * longer than its string stride lstr: 64 or 128 bases); those go to tier 5 / the generic engine (dbg_window.hpp).
+ * longer than its string stride lstr: 64 or 128 bases, tier 17: longer than 255); those go to tier 5 / tier 17 / the generic engine (dbg_window.hpp).
  */
 #ifndef DACC_FAST_WINDOW_HPP
 #define DACC_FAST_WINDOW_HPP
@@ -225,6 +226,19 @@ static_assert(FastTier<15>::mins == VDEEP_MINS && FastTier<13>::maxs == VDEEP_MI
 // whole scratch (lscrids = 4096 ids), which holds every path of the pool (rccap = 4096), so it never sends a window on by itself.
 template<> struct FastTier<16> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 4000, gw = 1, wcapg = 65536, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 8000, rpstcap = 768, lstr = 128, maxs = 2000, precap = 16384, ncap = 8190, scap = 4096, lcap = 16384, wcap = 65536, rccap = 4096, fcap = 1024, siqcap = 512, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 4096, wide = 0, mins = 250, gmem = 1 }; };
 static_assert(FastTier<16>::mins == VDEEP_MINS && FastTier<15>::maxs == XDEEP_MINS,"the deepest stage takes what the very deep stage hands on with more than 250 strings");
+// tier 17: the LONG STRING stage of wide batches, on the second stream in front of the generic engine there (tier_pipeline.hpp: ID_LONG): the windows the
+// pre-scan set aside because a B string has more than 128 bases.  Tier 14 with a string stride of 256: FOUR 64 bit words per pattern mask (FastLds<CT>::pw),
+// strings of up to 255 bases -- the lengths and positions of a string are bytes (slen, ipos, irpos, canderr) --, a longer one is FFAIL(4) = FW_GENERIC and
+// goes on to the generic engine.  Tables, pools and the wide fields (two words per position mask, 128 symbol consensus, base lengths up to 191) are tier
+// 14's: what a long string can make longer than those hold -- a forward base length, a candidate, a consensus -- is refused by the checks that refuse it in
+// tier 14 (extendPath: over(2048), buildSeq: over(4096), FFAIL(9)) and the window goes on, nothing wraps (DESIGN 3.5 lists the audit).
+// oneslab: the whole working set of a workgroup is ONE buffer whose first byte is the layout's (L.base); the weights, the spill image and the instance
+// image follow the layout (FastLds<CT>::g_base) instead of preceding it, so a caller that has one buffer of FastCaps::ldsbytes for a stage and no slab
+// (the emulation's ROLE_LONG stage) runs the tier as it is.  Tiers 13 ... 16 keep their addressing.
+template<> struct FastTier<17> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 1000, gw = 1, wcapg = 16384, rch = 16, fch = 16, fnw = 8, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 256, maxs = 250, precap = 16384, ncap = 6144, scap = 1024, lcap = 8192, wcap = 16384, rccap = 4096, fcap = 4096, siqcap = 512, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 4096, wide = 1, mins = 0, gmem = 1, oneslab = 1 }; };
+// (only tier 17 names the enumerator: for every other tier FastOneSlab<CT>::value is 0)
+template<typename CT, typename = void> struct FastOneSlab { enum : uint32_t { value = 0 }; };
+template<typename CT> struct FastOneSlab<CT,decltype(void(CT::oneslab))> { enum : uint32_t { value = (CT::oneslab != 0) ? 1u : 0u }; };
 
 HDEV constexpr uint32_t fcpow2(uint32_t v) { uint32_t p = 1; while ( p < v ) p <<= 1; return p; }
 HDEV constexpr uint32_t fcmax(uint32_t a, uint32_t b) { return a > b ? a : b; }
@@ -255,8 +269,9 @@ struct FastLds<CT,false>
 	static_assert(sizeof(typename CT::id_t) > 1 || (CT::fcap <= 256 && CT::rccap <= 256),"pool slots are recorded as id_t (pout)");
 	static_assert(CT::blcap <= 128 && (CT::blcap & 7) == 0,"base length buckets: two 64 bit occupancy words, cleared 8 at a time");
 	// ---- live during the whole window ----
-	static_assert(CT::lstr == 64 || CT::lstr == 128,"string stride: one or two 64 bit words per pattern mask");
+	static_assert(CT::lstr == 64 || CT::lstr == 128 || CT::lstr == 256,"string stride: one, two or four 64 bit words per pattern mask");
 	static constexpr uint32_t pw = CT::lstr/64;      // words per pattern mask
+	static constexpr uint32_t maxlen = CT::lstr < 256u ? static_cast<uint32_t>(CT::lstr) : 255u;      // longest string the layout holds
 	typedef uint8_t sid_t;      // stretch ids are 8 bits in the legacy layout
 	static_assert(sizeof(typename CT::sid_t) == 1,"16 bit stretch ids need the gw layout");
 	FLD(str,uint8_t,CT::maxs*CT::lstr,0)
@@ -457,8 +472,10 @@ struct FastLds<CT,true>
 	// sort at the start of a window is checked against it)
 	static_assert(sizeof(typename CT::id_t) > 1 || (CT::fcap <= 256 && CT::rccap <= 256),"pool slots are recorded as id_t (pout)");
 	static_assert(CT::blcap <= 128 && (CT::blcap & 7) == 0,"base length buckets: two 64 bit occupancy words, cleared 8 at a time");
-	static_assert(CT::lstr == 64 || CT::lstr == 128,"the gw layout holds strings of up to 64 bases in one word per pattern mask, of up to 128 in two (round 6)");
+	static_assert(CT::lstr == 64 || CT::lstr == 128 || CT::lstr == 256,"the gw layout holds strings of up to 64 bases in one word per pattern mask, of up to 128 in two (round 6), of up to 255 in four (tier 17)");
 	static constexpr uint32_t pw = CT::lstr/64;
+	static constexpr uint32_t maxlen = CT::lstr < 256u ? static_cast<uint32_t>(CT::lstr) : 255u;      // longest string the layout holds: its length is a byte
+	static constexpr bool oneslab = FastOneSlab<CT>::value != 0;      // FastTier<17>: layout and slab in one buffer, the layout first
 	typedef typename CT::sid_t sid_t;      // stretch ids: 8 bits (at most 250 stretches) or 16 bits
 	// more than 256 strings (tier 15): 16 bit node frequencies capped at fqmax, 32 bit first-instance offsets, a 32 byte forward weight record
 	static constexpr bool wides = CT::maxs > 256;
@@ -475,6 +492,7 @@ struct FastLds<CT,true>
 	static_assert(icap <= (sizeof(nps_t) == 2 ? 65535u : 0xFFFFFFFFu),"nps[nn] = npre <= icap must fit a first-instance offset");
 	// ---- P ----
 	FLD(slen,uint8_t,CT::maxs,0)
+	static_assert(maxlen <= 255u,"slen: a string's length is a byte");
 	static constexpr uint32_t supcap = CT::wide ? static_cast<uint32_t>(FSUPCAPW) : static_cast<uint32_t>(FSUPCAP);
 	FLD(suplo8,uint8_t,supcap,e_slen)
 	FLD(suphi8,uint8_t,supcap,e_suplo8)
@@ -501,6 +519,7 @@ struct FastLds<CT,true>
 	FLD(peq,uint64_t,CT::maxs*4*pw,sbase)
 	FLD(ipos,uint8_t,icap,e_peq)
 	FLD(irpos,uint8_t,icap,e_ipos)
+	static_assert(supcap <= 255u && maxlen <= 255u,"ipos / irpos: the position of a k-mer in its string, from either end, is stored as min(position,nsup) <= supcap in a byte");
 	FLD(nps,nps_t,CT::ncap+1,e_irpos)
 	FLD(nfreq,nfreq_t,CT::ncap,e_nps)
 	FLD(succ0,uint16_t,CT::ncap,e_nfreq)
@@ -589,6 +608,7 @@ struct FastLds<CT,true>
 	FLD(acc,FCC,16,e_ch)
 	FLD(accerr,uint32_t,16,e_acc)
 	FLD(canderr,uint8_t,16*CT::maxs,e_accerr)
+	static_assert(fcmax(maxlen,CT::consrow) <= 255u,"canderr: the error of a candidate against one string is at most max(string,candidate), a byte");
 	FLD(consL,uint8_t,16*CT::consrow,e_canderr)
 	static constexpr uint32_t lscrbytes = static_cast<uint32_t>(CT::lscrids)*static_cast<uint32_t>(sizeof(typename CT::id_t));
 	FLD(lscr,uint8_t,lscrbytes,e_cseq)
@@ -623,10 +643,14 @@ struct FastLds<CT,true>
 	HDEV LDSQ uint8_t * xreach() const { return reinterpret_cast<LDSQ uint8_t *>(base + xbase); }
 	// (more than 256 strings: the instances as they are generated, before they are split into the four sorted ranges of `pre`; behind both overlays)
 	FLD(pregen,uint64_t,(wides ? icap : 0u),((fcmax(uA,uB) + 15u) & ~15u))
-	static constexpr uint32_t uend = wides ? e_pregen : fcmax(uA,uB);
 	// scratch behind the build overlay (gap filling): small in this layout, a window that needs more goes to the next tier
-	FLD(gfbuf,uint64_t,(uB > uA ? (uB-uA)/8 : 0u),uA)
-	static constexpr uint32_t gfcap = uB > uA ? (uB-uA)/8 : 0u;
+	// (one-slab tier: nothing comes behind it but the generic engine, and the windows of noisy sequence that carry its long strings reach filter frequency 0
+	// more often than others -- a region of its own behind both overlays, 16384 records and as many candidates; where the build overlay is the longer
+	// one, as in tiers 14 and 17, the shared scratch has no room at all)
+	static constexpr uint32_t gfown = (oneslab && !wides) ? 32768u : 0u;
+	FLD(gfbuf,uint64_t,(gfown ? gfown : (uB > uA ? (uB-uA)/8 : 0u)),(gfown ? ((fcmax(uA,uB) + 15u) & ~15u) : uA))
+	static constexpr uint32_t gfcap = gfown ? gfown : (uB > uA ? (uB-uA)/8 : 0u);
+	static constexpr uint32_t uend = wides ? e_pregen : (gfown ? e_gfbuf : fcmax(uA,uB));
 	static constexpr uint32_t tabcap = 0x7FFFFFFFu;      // no LDS copy of the model table
 	HDEV static uint32_t bytes(uint32_t const, uint32_t const) { return (uend + 15u) & ~15u; }
 	// the global slab of a workgroup: forward weights, reverse weights (16 bytes per entry), spill of S; the walk slots of
@@ -641,6 +665,10 @@ struct FastLds<CT,true>
 	static constexpr uint32_t xnslot = g_spill / 128u;
 	// device-memory tiers (CT::gmem): this layout itself sits behind the instance image, g_total bytes per workgroup in all
 	static constexpr uint32_t g_layout = g_bytes, g_total = CT::gmem ? g_bytes + ((((uend + 15u) & ~15u) + 255u) & ~255u) : g_bytes;
+	// one-slab tiers (FastTier<17>::oneslab): the layout comes FIRST -- base is the first byte of the workgroup's buffer -- and the g_* part follows it at g_base
+	// (processWindowFast: E.gslab = base + g_base); the buffer has the same g_total bytes
+	static constexpr uint32_t g_base = oneslab ? ((((uend + 15u) & ~15u) + 255u) & ~255u) : 0u;
+	static_assert(!oneslab || CT::gmem != 0,"a one-slab tier is a device-memory tier");
 };
 #undef FLD
 
@@ -654,6 +682,7 @@ HDEV FastCaps fastCapsOf(uint32_t const nrows, uint32_t const nsup)
 	C.ldsbytes = FastLds<CT>::bytes(nrows,nsup);
 	C.tabcap = FastLds<CT>::tabcap;
 	if constexpr ( CT::gw != 0 ) C.gbytes = FastLds<CT>::g_total; else C.gbytes = 0;
+	if constexpr ( FastOneSlab<CT>::value != 0 ) C.ldsbytes = C.gbytes;      // one buffer: layout, then weights, spill image, instance image
 	C.gmem = CT::gmem;
 	static_assert(CT::gmem == 0 || CT::gw != 0,"a layout in device memory is the gw layout");
 	return C;
@@ -1015,6 +1044,18 @@ struct FastEngine
 					{
 						uint64_t const e1 = PEQ[1], e2 = PEQ[2], e3 = PEQ[3];
 						lo = static_cast<uint32_t>((e1|e3) >> i) & km; hi = static_cast<uint32_t>((e2|e3) >> i) & km;
+					}
+					else if constexpr ( PW > 2 )
+					{
+						// (PW words per mask, tier 17: strings of up to 255 bases.  The 16 bits from position i on come from word i >> 6 and, where the run
+						// straddles a boundary, from the word behind it; i + k <= 255, so a run that straddles has such a word)
+						uint32_t const wq = i >> 6, sh = i & 63u;
+						bool const two = sh > 48u && wq+1 < PW;
+						uint64_t const l0 = PEQ[1*PW+wq] | PEQ[3*PW+wq], h0 = PEQ[2*PW+wq] | PEQ[3*PW+wq];
+						uint64_t const l1 = two ? (PEQ[1*PW+wq+1] | PEQ[3*PW+wq+1]) : 0ull, h1 = two ? (PEQ[2*PW+wq+1] | PEQ[3*PW+wq+1]) : 0ull;
+						uint64_t const sl = (l0 >> sh) | (sh ? (l1 << (64u-sh)) : 0ull);
+						uint64_t const sx = (h0 >> sh) | (sh ? (h1 << (64u-sh)) : 0ull);
+						lo = static_cast<uint32_t>(sl) & km; hi = static_cast<uint32_t>(sx) & km;
 					}
 					else
 					{
@@ -3270,6 +3311,8 @@ struct FastEngine
 	{
 		uint32_t const m = L.slen()[j];
 		if ( m == 0 ) return n;
+		if constexpr ( FastLds<CT>::pw > 2 ) return myersDistanceN(j,text,n,m);
+		else {
 		if ( FastLds<CT>::pw == 2 ) return myersDistance2(j,text,n,m);
 		LDSQ uint64_t const * PEQ = L.peq() + 4*j;
 		uint64_t const e0 = PEQ[0], e1 = PEQ[1], e2 = PEQ[2], e3 = PEQ[3];
@@ -3298,6 +3341,7 @@ struct FastEngine
 			w = wn;
 		}
 		return score;
+		}
 	}
 	// the same for strings of up to 128 bases (tier 5): two words per pattern mask, block-wise Myers (the horizontal deltas
 	// of the top row of word 0 are the carries into word 1), the score follows bit m-1
@@ -3341,6 +3385,53 @@ struct FastEngine
 					Pv1 = Mh1 | ~(Xv1 | Ph1);
 					Mv1 = Ph1 & Xv1;
 				}
+			}
+			w = wn;
+		}
+		return score;
+	}
+	// the same for strings of up to 255 bases (tier 17): PW words per pattern mask, block-wise Myers over the nb = ceil(m/64) words the string has (the
+	// words above its last one do no work), the horizontal deltas of the top row of a word are the carries into the next one, the score follows bit
+	// (m-1) & 63 of word (m-1) >> 6.  The masks of a symbol are picked by mask arithmetic (as k_trace_wide does), not by an indexed select: the 16 mask
+	// words and the 8 state words stay in registers
+	DEV uint32_t myersDistanceN(uint32_t const j, LDSQ uint8_t const * text, uint32_t const n, uint32_t const m) const
+	{
+		enum { PW = FastLds<CT>::pw };
+		LDSQ uint64_t const * PEQ = L.peq() + 4*PW*j;
+		uint64_t E0[PW], E1[PW], E2[PW], E3[PW], Pv[PW], Mv[PW];
+		#pragma unroll
+		for ( uint32_t b = 0; b < PW; ++b ) { E0[b] = PEQ[b]; E1[b] = PEQ[PW+b]; E2[b] = PEQ[2*PW+b]; E3[b] = PEQ[3*PW+b]; Pv[b] = ~0ull; Mv[b] = 0; }
+		LDSQ uint64_t const * T8 = reinterpret_cast<LDSQ uint64_t const *>(text);
+		uint32_t const lastw = (m-1) >> 6;
+		uint64_t const top = 1ull << ((m-1) & 63u);
+		uint32_t score = m;
+		uint64_t w = n ? T8[0] : 0ull;
+		for ( uint32_t c0 = 0; c0 < n; c0 += 8 )
+		{
+			uint64_t const wn = (c0+8 < n) ? T8[(c0>>3)+1] : 0ull;
+			uint32_t const cnt = (n-c0 < 8) ? (n-c0) : 8u;
+			for ( uint32_t u = 0; u < cnt; ++u )
+			{
+				uint32_t const ch = static_cast<uint32_t>(w >> (8*u)) & 3u;
+				uint64_t const s0 = ch == 0 ? ~0ull : 0ull, s1 = ch == 1 ? ~0ull : 0ull, s2 = ch == 2 ? ~0ull : 0ull, s3 = ch == 3 ? ~0ull : 0ull;
+				uint64_t phc = 1ull, mhc = 0ull;      // the delta entering row 0: +1 (the first row of the matrix is 0, 1, 2, ...: a global distance)
+				#pragma unroll
+				for ( uint32_t b = 0; b < PW; ++b )
+					if ( b <= lastw )
+					{
+						uint64_t const Eq = (E0[b] & s0) | (E1[b] & s1) | (E2[b] & s2) | (E3[b] & s3);
+						uint64_t const Eqc = Eq | mhc;
+						uint64_t const Xv = Eq | Mv[b];
+						uint64_t const Xh = (((Eqc & Pv[b]) + Pv[b]) ^ Pv[b]) | Eqc;
+						uint64_t Ph = Mv[b] | ~(Xh | Pv[b]);
+						uint64_t Mh = Pv[b] & Xh;
+						if ( b == lastw ) { if ( Ph & top ) ++score; else if ( Mh & top ) --score; }
+						uint64_t const pho = Ph>>63, mho = Mh>>63;
+						Ph = (Ph<<1) | phc; Mh = (Mh<<1) | mhc;
+						Pv[b] = Mh | ~(Xv | Ph);
+						Mv[b] = Ph & Xv;
+						phc = pho; mhc = mho;
+					}
 			}
 			w = wn;
 		}
@@ -4092,7 +4183,7 @@ struct FastEngine
 		{
 		uint32_t const m = P.w;
 		enum { PW = FastLds<CT>::pw };
-		static_assert(PW == 2,"the A window of a wide tier has two words per pattern mask");
+		static_assert(PW >= 2,"the A window of a wide tier (string 0, stride PW) has at least two words per pattern mask: w <= 127 uses words 0 and 1");
 		LDSQ uint64_t const * PEQ = L.peq();      // string 0 = the A window: word q of symbol c at PW*c + q
 		uint64_t const mask1 = (m == 128) ? ~0ull : ((1ull<<(m-64))-1);
 		uint64_t Pv0 = ~0ull, Mv0 = 0, Pv1 = mask1, Mv1 = 0; uint32_t score = m;
@@ -4245,6 +4336,8 @@ DEV int processWindowFast(FastBatch const & FB, uint64_t const widx, LDSQ uint8_
 #else
 		E.gslab = FB.gslab + static_cast<uint64_t>(blockIdx.x)*FB.gstride;
 #endif
+		// (one-slab tier: the weights, the spill image and the instance image follow the layout in the buffer the caller passed as `lds`)
+		if constexpr ( FastOneSlab<CT>::value != 0 ) E.gslab = (uint8_t *)(lds) + FastLds<CT>::g_base;
 	}
 	E.lane = wv_lane(); E.flags = 0; E.prof = B.prof;
 #if defined(DACC_LEDGER)
@@ -4338,7 +4431,7 @@ DEV int processWindowFast(FastBatch const & FB, uint64_t const widx, LDSQ uint8_
 				bs = B.wt_b[row]; len = B.wt_e[row]-bs;
 				off = B.boff[o.bread]; rl = B.rlen[o.bread]; inv = o.flags & 1;
 			}
-			if ( len > CT::lstr ) { toolong = 1; len = 0; }
+			if ( len > FastLds<CT>::maxlen ) { toolong = 1; len = 0; }
 			L.slen()[j] = len;
 			L.mfirst()[j] = bs | (static_cast<uint64_t>(rl)<<32);
 			L.mlast()[j] = off | (static_cast<uint64_t>(inv ? 1 : 0)<<63);
@@ -4360,7 +4453,7 @@ DEV int processWindowFast(FastBatch const & FB, uint64_t const widx, LDSQ uint8_
 				if constexpr ( CT::gw != 0 )
 				{
 					// pattern masks by ballot: bit p of word c of string j <=> symbol c at position p (positions behind the string: no bit)
-					// (words 4*PW*j + PW*symbol + word: PW = 2 holds strings of up to 128 bases, the second round of p fills word 1)
+					// (words 4*PW*j + PW*symbol + word: PW = 2 holds strings of up to 128 bases, the second round of p fills word 1; PW = 4: four rounds, up to 255)
 					enum { PW = FastLds<CT>::pw };
 					uint32_t const sh0 = p - static_cast<uint32_t>(lane);      // (a 64-lane wavefront: 0 or 64; the 1-lane test build walks p)
 					uint32_t const wq = sh0 >> 6, sh = sh0 & 63u;

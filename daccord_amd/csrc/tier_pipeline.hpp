@@ -8,6 +8,7 @@
  *   deep batches      slot 0: 4               slot 1: 2     slot 2: 11 -> 12 -> 3
  *   wide batches                              slot 1: 8     slot 2: 9
  *   shallow and deep  tier 5 on the second stream (k_window_long), in front of the generic engine there
+ *   wide batches      the LONG STRING stage on the second stream: tier 17 (strings of 129 ... 255 bases, layout in device memory), in front of the generic engine there
  *   every batch       the LAST stage, once, behind the slots and in front of the generic engine: tier 13 (shallow, deep) / tier 14 (wide)
  *   shallow and deep  the VERY DEEP stage, behind the last stage, only in a batch with a window of more than 250 strings: tier 15
  *   shallow and deep  the DEEPEST stage, behind the very deep stage, only in a batch with a window of more than 1000 strings: tier 16
@@ -40,6 +41,12 @@
  * it.  DACC_XDEEP_AS_SLOT2=1 (tests) makes tier 16 the main tier of the third slot of shallow and deep batches, with tier 12 still in front of it,
  * and switches ID_XDEEP off.
  *
+ * The LONG STRING stage (ID_LONG in a wide batch, ROLE_LONG) runs tier 17 -- tier 14 with four words per pattern mask, strings of up to 255 bases -- over the
+ * two lists of the second stream (the pre-scan's: a B string of more than 128 bases; the first tier's generic-only windows) with a kernel of its own,
+ * k_window_fast<17>, in front of k_window_long, which then runs the generic engine alone over what the tier handed on (a string of more than 255 bases,
+ * a table that overflowed).  Its slab is allocated and its kernel launched only for a list that is not empty.  DACC_LONGSTR_TIER=0 removes it: a wide
+ * batch's second stream is then the generic engine alone, as before the stage.  Shallow and deep batches keep tier 5 inside k_window_long.
+ *
  * More than one of DACC_LAST_AS_SLOT2=1, DACC_VDEEP_AS_SLOT2=1 and DACC_XDEEP_AS_SLOT2=1 is an error (TierSwitches::conflict): each names the third
  * slot's main tier.
  */
@@ -66,7 +73,7 @@ enum : uint32_t { T0INST_DEFAULT = 576, T7INST_DEFAULT = 704 };      // a window
                                                // arguments of the pre-pass (DACC_T0INST / DACC_T7INST override them for sweeps)
 
 // The tiers.  KERNEL: those with a kernel of their own (k_window_fast<N>, window_kernels.hpp); tier 5 runs inside k_window_long.
-#define DACC_KERNEL_TIERS(X) X(0) X(1) X(2) X(3) X(4) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
+#define DACC_KERNEL_TIERS(X) X(0) X(1) X(2) X(3) X(4) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17)
 #define DACC_ALL_TIERS(X) DACC_KERNEL_TIERS(X) X(5)
 
 // From a run-time tier number to its compile-time capacities: f is called with a TierTag<N>, whose `type` is FastTier<N>
@@ -80,7 +87,7 @@ template<typename F> static inline auto withTier(uint32_t const tier, F && f) ->
 	std::abort();
 }
 
-enum TierRole { ROLE_FRONT, ROLE_MAIN, ROLE_LONG, ROLE_LAST };      // front tier of a slot, the slot's main tier, tier 5 on the second stream, the device-memory tier behind the slots
+enum TierRole { ROLE_FRONT, ROLE_MAIN, ROLE_LONG, ROLE_LAST };      // front tier of a slot, the slot's main tier, tier 5 / tier 17 on the second stream, the device-memory tier behind the slots
 // What switches a stage off, beside its bit of DACC_TIERS, its LDS size (at most the 160 KiB of a CU) and a batch shape it has no tier
 // for (TIER_NONE: "not in a wide batch", "not in a deep batch").  A front tier also needs the main tier of its slot.
 enum : uint32_t
@@ -93,6 +100,7 @@ enum : uint32_t
 	GATE_DEEP = 128,      // DACC_DEEP_TIER=0 switches it off (windows of more than 96 strings run in the generic engine, as before the deep-window tier)
 	GATE_LAST = 256,      // DACC_LAST_TIER=0 or DACC_LAST_AS_SLOT2=1 switches it off; needs a slot that ran
 	GATE_XDEEP = 1024,    // DACC_XDEEP_TIER=0 or DACC_XDEEP_AS_SLOT2=1 switches it off; needs a slot that ran and a window of more than XDEEP_MINS strings in the batch
+	GATE_LONGSTR = 2048,  // DACC_LONGSTR_TIER=0 switches it off in a wide batch (the second stream of a wide batch is then the generic engine alone); no gate in the other shapes
 	GATE_VDEEP = 512,     // DACC_VDEEP_TIER=0 or DACC_VDEEP_AS_SLOT2=1 switches it off; needs a slot that ran and a window of more than VDEEP_MINS strings in the batch
 	STAGE_PREPASS = 32,   // (no gate) fed by the size-class pre-pass instead of the list in front of it
 	STAGE_ADAPTIVE = 64   // (no gate) switches itself off for the rest of a context when it hands on too much (DACC_T7_ADAPT)
@@ -106,7 +114,8 @@ enum : uint32_t { WORK_SLOT0 = 0, WORK_SLOT1 = 8, WORK_SLOT2 = 16, WORK_DENSE = 
 	WORK_VDEEP_COUNT = 96,     // two words: windows of more than VDEEP_MINS strings the very deep stage read / handed on (for dacc_timing)
 	WORK_XDEEP = 104,
 	WORK_XDEEP_COUNT = 112,    // two words: windows of more than VDEEP_MINS strings the deepest stage read / handed on (for dacc_timing)
-	WORK_WORDS = 120 };
+	WORK_LONGSTR = 120,        // the long string stage's launch over the pre-scan list, WORK_LONGSTR + 8: its launch over the first tier's generic-only list
+	WORK_WORDS = 136 };
 
 // The stages, in the order they run; their place in this table is their place in BatchPlan::stageCaps, TierPipeline and dacc_ctx::st.
 enum TierId { ID_T0, ID_T7, ID_SLOT0, ID_SLOT1, ID_DENSE, ID_DEEP, ID_SLOT2, ID_LAST, ID_VDEEP, ID_XDEEP, ID_LONG, TIER_NSTAGES };
@@ -125,8 +134,9 @@ static TierStage const TIER_CHAIN[TIER_NSTAGES] = {
 	{ { 13, 13, 14 }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_LAST, WORK_LAST },
 	{ { 15, 15, TIER_NONE }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_VDEEP, WORK_VDEEP },
 	{ { 16, 16, TIER_NONE }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_XDEEP, WORK_XDEEP },
-	// (tier 5 holds no wide window: a wide batch's second stream is the generic engine alone, at its own occupancy instead of a CU's LDS per wavefront)
-	{ { 5, 5, TIER_NONE }, 0, ROLE_LONG, 2, GATE_TABFIT, 0 } };
+	// (tier 5 holds no wide window and no string of more than 128 bases: a wide batch's second stream runs tier 17, a kernel of its own over a slab in device
+	// memory, and the generic engine behind it)
+	{ { 5, 5, 17 }, 0, ROLE_LONG, 2, GATE_TABFIT|GATE_LONGSTR, WORK_LONGSTR } };
 static TierId const TIER_MAIN[TIER_NSLOTS] = { ID_SLOT0, ID_SLOT1, ID_SLOT2 };
 // does the stage run in a batch of this shape, and the tier whose capacities the plan holds for it (a stage that does not run keeps
 // those of the nearest shape: the first slot of a wide batch has tier 1's or tier 4's)
@@ -158,6 +168,7 @@ struct TierSwitches
 	bool vdeep_as_slot2;      // DACC_VDEEP_AS_SLOT2=1: tier 15 as the third slot's main tier of shallow and deep batches, no very deep stage
 	bool xdeeptier;           // DACC_XDEEP_TIER=0: no deepest stage (windows of more than 1000 strings run in the generic engine, as before that stage)
 	bool xdeep_as_slot2;      // DACC_XDEEP_AS_SLOT2=1: tier 16 as the third slot's main tier of shallow and deep batches, no deepest stage
+	bool longstr;             // DACC_LONGSTR_TIER=0: no long string stage (tier 17) on the second stream of a wide batch, the generic engine alone as before that stage
 	bool conflict() const { return static_cast<int>(last_as_slot2) + static_cast<int>(vdeep_as_slot2) + static_cast<int>(xdeep_as_slot2) > 1; }      // more than one wants the third slot: dacc_create refuses
 	bool long128;             // DACC_LONG128=0: windows with a string of 65 ... 128 bases run in tier 5 on the second stream (rounds 3-5)
 	bool hand;                // DACC_HAND=0: no hand-over buffer, every hand-over restarts from the strings
@@ -171,7 +182,7 @@ static inline TierSwitches readTierSwitches()
 	TierSwitches S;
 	{ char const * const e = getenv("DACC_NOFAST"); S.nofast = e && e[0] == '1'; }
 	S.tiers = num("DACC_TIERS",31);
-	S.widetier = !off("DACC_WIDE_TIER"); S.dense = !off("DACC_DENSE_TIER"); S.deepwin = !off("DACC_DEEP_TIER"); S.lasttier = !off("DACC_LAST_TIER"); S.last_as_slot2 = lastAsSlot2(); S.vdeeptier = !off("DACC_VDEEP_TIER"); S.vdeep_as_slot2 = vdeepAsSlot2(); S.xdeeptier = !off("DACC_XDEEP_TIER"); S.xdeep_as_slot2 = xdeepAsSlot2(); S.long128 = !off("DACC_LONG128"); S.hand = !off("DACC_HAND");
+	S.widetier = !off("DACC_WIDE_TIER"); S.dense = !off("DACC_DENSE_TIER"); S.deepwin = !off("DACC_DEEP_TIER"); S.lasttier = !off("DACC_LAST_TIER"); S.last_as_slot2 = lastAsSlot2(); S.vdeeptier = !off("DACC_VDEEP_TIER"); S.vdeep_as_slot2 = vdeepAsSlot2(); S.xdeeptier = !off("DACC_XDEEP_TIER"); S.xdeep_as_slot2 = xdeepAsSlot2(); S.longstr = !off("DACC_LONGSTR_TIER"); S.long128 = !off("DACC_LONG128"); S.hand = !off("DACC_HAND");
 	S.t0inst = num("DACC_T0INST",T0INST_DEFAULT); S.t7inst = num("DACC_T7INST",T7INST_DEFAULT);
 	S.lds_t1 = num("DACC_LDS_T1",0); S.lds_t0 = num("DACC_LDS_T0",0);
 	return S;
@@ -236,7 +247,8 @@ static inline TierPipeline resolveTiers(TierSwitches const & S, bool const fastp
 			&& (!(st.flags & GATE_T7_ABOVE_T0) || S.t7inst > S.t0inst) && (!(st.flags & GATE_DENSE) || S.dense) && (!(st.flags & GATE_DEEP) || S.deepwin)
 			&& (!(st.flags & GATE_LAST) || (S.lasttier && !S.last_as_slot2))
 			&& (!(st.flags & GATE_VDEEP) || (S.vdeeptier && !S.vdeep_as_slot2 && maxstrings > VDEEP_MINS))
-			&& (!(st.flags & GATE_XDEEP) || (S.xdeeptier && !S.xdeep_as_slot2 && maxstrings > XDEEP_MINS));
+			&& (!(st.flags & GATE_XDEEP) || (S.xdeeptier && !S.xdeep_as_slot2 && maxstrings > XDEEP_MINS))
+			&& (!(st.flags & GATE_LONGSTR) || !wide || S.longstr);
 	};
 	{ FastCaps & F = capsOf(ID_SLOT0); if ( S.lds_t1 > F.ldsbytes && S.lds_t1 <= TIER_LDS_CU ) F.ldsbytes = S.lds_t1; }
 	{ FastCaps & F = capsOf(ID_T0); if ( S.lds_t0 > F.ldsbytes && S.lds_t0 <= TIER_LDS_CU ) F.ldsbytes = S.lds_t0; }

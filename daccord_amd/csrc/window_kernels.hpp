@@ -1,5 +1,5 @@
 /*
- * The window kernels of libdaccord_hip.so, one translation unit each (k_fast_<tier>.hip for the fifteen tiers of DACC_KERNEL_TIERS,
+ * The window kernels of libdaccord_hip.so, one translation unit each (k_fast_<tier>.hip for the tiers of DACC_KERNEL_TIERS,
  * tier_pipeline.hpp -- the table of the tiers is at the head of fast_window.hpp --, and k_generic.hip, which also holds tier 5): they are
  * 150-260 KB of gfx950 code apiece and took 25 minutes to compile one after the other inside capi.hip; as separate objects they compile
  * side by side (daccord_amd/build.py).  This header holds what the units share: the work distribution, the kernel template of the LDS tiers (defined
@@ -64,7 +64,8 @@ __global__ void __launch_bounds__(64) DACC_WPE(TIER) k_window_fast(FastBatch FB,
 #if defined(DACC_LAYOUT_IN_GLOBAL)
 	// device-memory tier: the layout sits in this workgroup's slab, behind the weights, the spill image and the instance image; no LDS at all
 	static_assert(CT::gmem != 0,"only the device-memory tiers are compiled with the layout in global memory");
-	LDSQ uint8_t * lds = (LDSQ uint8_t *)(FB.gslab + static_cast<uint64_t>(blockIdx.x)*FB.gstride + FastLds<CT>::g_layout);
+	// (a one-slab tier, FastTier<17>: the layout is the first thing in the slab and everything else follows it)
+	LDSQ uint8_t * lds = (LDSQ uint8_t *)(FB.gslab + static_cast<uint64_t>(blockIdx.x)*FB.gstride + (FastOneSlab<CT>::value ? 0u : FastLds<CT>::g_layout));
 #else
 	static_assert(CT::gmem == 0,"a device-memory tier needs DACC_LAYOUT_IN_GLOBAL in its unit");
 	extern __shared__ __attribute__((aligned(16))) uint8_t lds_generic[];

@@ -214,11 +214,24 @@ typedef struct dacc_timing {
 	                            where the deepest stage ran, what that stage read (vdeep_out = xdeep_windows + xdeep_out; k_window then ran xdeep_out of them) */
 	float emit_ms;           /* k_emit: the consensus -> A alignment of the tiers' windows (w <= 64), one lane per window, behind all window kernels and in front of the
 	                            vote; a part of vote_ms, not of window_ms.  It took the place of a pad word (always 0 before): the record keeps its size */
+	/* ---- everything above: 176 bytes, the record before the long string stage ---- */
+	/* the long string stage: k_window_fast<17> (layout in device memory, four words per pattern mask: strings of up to 255 bases) on the second stream of a wide batch
+	   (w = 64 ... 127), over the windows with a B string of more than 128 bases, in front of the generic engine of that stream; runs concurrently with the slots, so not a part
+	   of tier_ms[] */
+	float longstr_ms;        /* its launches (one per list of the second stream that is not empty); 0 if it did not run (not a wide batch, no such window, DACC_LONGSTR_TIER=0,
+	                            no memory for its slab) */
+	uint32_t longstr_windows;/* windows that finished in it */
+	uint32_t longstr_out;    /* windows it handed on to the generic engine of the second stream (a string of more than 255 bases, a table beyond its capacities);
+	                            where it ran, longstr_windows + longstr_out == long_windows */
+	uint32_t pad2_;
 } dacc_timing;
 #define DACC_TIMING_SIZE_V1 128
+#define DACC_TIMING_SIZE_V2 176   /* the record in front of longstr_ms */
 /* dacc_last_timing fills the first DACC_TIMING_SIZE_V1 bytes only (the record as it was when the call was introduced: a caller built against
  * an older header is never overrun).  dacc_last_timing2 copies min(size, sizeof(dacc_timing)) bytes: pass sizeof(dacc_timing) of the header
- * the caller was compiled with; fields the library does not know stay as the caller set them. */
+ * the caller was compiled with; fields the library does not know stay as the caller set them.  The 16 bytes behind emit_ms (the long string
+ * stage) are copied only when size covers all of them: a size between DACC_TIMING_SIZE_V2 and sizeof(dacc_timing) copies DACC_TIMING_SIZE_V2
+ * bytes, so that a caller of the 176 byte record who passes the size of a larger buffer of its own gets what it got before. */
 int  dacc_last_timing(dacc_ctx *ctx, dacc_timing *t);
 int  dacc_last_timing2(dacc_ctx *ctx, dacc_timing *t, size_t size);
 
