@@ -60,16 +60,9 @@ struct BatchPlan
 	std::vector<int32_t> pile_status;         // per submitted pile: DACC_OK or why it was dropped
 	std::vector<std::string> pile_errors;     // first messages of dropped piles
 	ArenaCaps caps;
-	// LDS fast path: capacities of the stages of the tier chain (tier_pipeline.hpp), by name and by TierId
-	FastCaps ftier[TIER_NSLOTS];   // main tier of every slot
-	FastCaps ftier0, ftier7;  // front tiers of the first slot (size classes of shallow batches)
-	FastCaps ftierD;          // front tier of the last slot (dense graphs: tier 10, deep batches 11)
-	FastCaps ftierX;          // second front tier of the last slot (deep windows, 97 ... 250 strings: tier 12)
-	FastCaps ftierL;          // the second stream's tier, in front of the generic engine there: tier 5 (shallow and deep batches: a string of 65..128 bases, inside k_window_long) / tier 17 (wide batches: a string of 129..255 bases, a kernel of its own)
-	FastCaps ftierZ;          // the last stage, behind the slots and in front of the generic engine (layout in device memory: tier 13, wide batches 14)
-	FastCaps ftierV;          // the very deep stage behind it (windows of 251 ... 1000 strings, layout in device memory: tier 15)
-	FastCaps ftierW;          // the deepest stage behind that (windows of 1001 ... 2000 strings and what tier 15 overflowed on, layout in device memory: tier 16)
-	FastCaps & stageCaps(uint32_t const id) { FastCaps * const F[TIER_NSTAGES] = { &ftier0,&ftier7,&ftier[0],&ftier[1],&ftierD,&ftierX,&ftier[2],&ftierZ,&ftierV,&ftierW,&ftierL }; return *F[id]; }
+	// LDS fast path: capacities of the stages of the tier chain (tier_pipeline.hpp), by TierId
+	FastCaps stage[TIER_NSTAGES];
+	FastCaps & stageCaps(uint32_t const id) { return stage[id]; }
 	// strings of the deepest window of the batch: the A window and its active overlaps (maxdepth), capped by -d like the kernels' mao
 	uint32_t maxstrings(dacc_params const & par) const { uint64_t const nb = par.maxalign > 0 ? static_cast<uint64_t>(par.maxalign-1) : 0; return 1u + static_cast<uint32_t>(std::min<uint64_t>(maxdepth,nb)); }
 	uint64_t ndeepwin;        // windows with more strings / k-mer instances than the first tier of shallow batches holds

@@ -403,11 +403,12 @@ struct dacc_ctx
 	DevBuf<uint8_t> d_wrec; DevBuf<WindowOut> d_wout; DevBuf<uint8_t> d_arena;
 	DevBuf<uint8_t> d_has, d_oc, d_outsym, d_pilebad; DevBuf<uint16_t> d_ld0; DevBuf<uint32_t> d_ocs, d_nfrag, d_err;
 	DevBuf<VoteFragment> d_frags; DevBuf<uint64_t> d_fragbase; DevBuf<uint64_t> d_prof;
-	DevBuf<uint64_t> d_vst; DevBuf<uint32_t> d_tab32; DevBuf<uint8_t> d_gslab, d_lastslab /* the last stage's own slab (layout included) */, d_vdeepslab /* the very deep stage's, allocated by the first batch with a window of more than 250 strings */, d_xdeepslab /* the deepest stage's, allocated by the first batch with a window of more than 1000 strings */, d_longslab /* the long string stage's (wide batches, second stream), allocated by the first pass whose second stream has a window */; DevBuf<uint32_t> d_longhand[2]; /* what that stage hands on to k_window_long, one list per list of the second stream */ DevBuf<uint32_t> d_retry[TIER_NSLOTS], d_work, d_gearly, d_pregen, d_pregen2, d_pregenlist; DevBuf<uint8_t> d_arena2; DevBuf<uint64_t> d_trslab; DevBuf<uint32_t> d_small; DevBuf<uint64_t> d_hand; DevBuf<uint32_t> d_handctr; uint32_t handcap; uint64_t handwant, nruns; bool nohand, oom; bool tier7_adapt_off; int env_t7adapt; int env_trdyn;
+	DevBuf<uint64_t> d_vst; DevBuf<uint32_t> d_tab32; DevBuf<uint8_t> d_gslab, d_longslab /* the long string stage's (wide batches, second stream), allocated by the first pass whose second stream has a window */; DevBuf<uint32_t> d_longhand[2]; /* what that stage hands on to k_window_long, one list per list of the second stream */ DevBuf<uint32_t> d_retry[TIER_NSLOTS], d_work, d_gearly, d_pregen, d_pregen2, d_pregenlist; DevBuf<uint8_t> d_arena2; DevBuf<uint64_t> d_trslab; DevBuf<uint32_t> d_small; DevBuf<uint64_t> d_hand; DevBuf<uint32_t> d_handctr; uint32_t handcap; uint64_t handwant, nruns; bool nohand, oom; bool tier7_adapt_off; int env_t7adapt; int env_trdyn;
 	// the LDS tiers (tier_pipeline.hpp): their switches, the resolved chain of the current batch (capacities: BP.stageCaps), by TierId and the launch state of its stages.
-	// A main tier hands on through d_retry[slot] and is done at evslot[slot]; `handon` and `done` are those of the front tiers.
+	// A main tier hands on through d_retry[slot] and is done at evslot[slot]; `handon` and `done` are those of the front tiers and of the trailing stages.
+	// `slab`: a trailing stage's own slab (layout included; the kernels' grids differ), allocated by the first batch the stage is resolved for.
 	TierSwitches sw; TierPipeline TP;
-	struct Stage { bool ran; uint32_t grid; DevBuf<uint32_t> handon; hipEvent_t done; uint32_t const * in; /* the list it read in the last pass */ } st[TIER_NSTAGES];
+	struct Stage { bool ran; uint32_t grid; DevBuf<uint32_t> handon; DevBuf<uint8_t> slab; hipEvent_t done; uint32_t const * in; /* the list it read in the last pass */ } st[TIER_NSTAGES];
 	uint32_t nlong[2];      // windows on the two lists of the second stream in the current pass (pre-scan, first tier's generic-only windows)
 	bool longran[2]; hipEvent_t evLong[4];      // the long string stage (tier 17): did it run over list i in the current pass, and the events around its two launches on the second stream
 	uint32_t retry_grid, early_grid; int sched;
@@ -460,7 +461,7 @@ int dacc_create(dacc_ctx ** out, dacc_params const * p)
 	if ( p->klow < 3 || p->khigh > 16 || p->klow > p->khigh || !p->w || !p->a || p->w > DACC_WMAX || p->minfilterfreq < 0 ||
 	     p->maxfilterfreq < p->minfilterfreq || p->tspace <= 0 || p->tspace > 512 )      // (tspace: 1..512, what the planner and the trace kernels hold)
 		return DACC_EINVAL;
-	// DACC_LAST_AS_SLOT2=1, DACC_VDEEP_AS_SLOT2=1 and DACC_XDEEP_AS_SLOT2=1 each name the third slot's main tier: more than one is refused before anything is set up
+	// the DACC_*_AS_SLOT2=1 switches of the trailing stages each name the third slot's main tier: more than one is refused before anything is set up
 	if ( readTierSwitches().conflict() ) return DACC_EINVAL;
 	int ndev = 0;
 	if ( hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || p->device < 0 || p->device >= ndev )
@@ -475,7 +476,7 @@ int dacc_create(dacc_ctx ** out, dacc_params const * p)
 	c->retry_grid = c->early_grid = c->win_grid = 0; c->tier7_adapt_off = false; c->sched = 0;
 	c->tr_grid = c->tr_lds = c->tr_words = c->tr_lanes = c->trace_bytes = 0;
 	{
-		c->sw = readTierSwitches();      // DACC_NOFAST, DACC_TIERS, DACC_WIDE_TIER, DACC_DENSE_TIER, DACC_DEEP_TIER, DACC_LAST_TIER, DACC_LAST_AS_SLOT2, DACC_VDEEP_TIER, DACC_VDEEP_AS_SLOT2, DACC_XDEEP_TIER, DACC_XDEEP_AS_SLOT2, DACC_LONGSTR_TIER, DACC_LONG128, DACC_HAND, DACC_T0INST, DACC_T7INST, DACC_LDS_T1, DACC_LDS_T0
+		c->sw = readTierSwitches();      // DACC_NOFAST, DACC_TIERS, DACC_WIDE_TIER, DACC_DENSE_TIER, DACC_DEEP_TIER, the trailing stages' DACC_*_TIER and DACC_*_AS_SLOT2, DACC_LONGSTR_TIER, DACC_LONG128, DACC_HAND, DACC_T0INST, DACC_T7INST, DACC_LDS_T1, DACC_LDS_T0
 		char const * sc = getenv("DACC_SCHED"); c->env_sched = sc ? atoi(sc) : 1;      // bit 0: LDS tiers pull work from a counter, bit 1: generic engine too
 		{ char const * td = getenv("DACC_TRACE_DYN"); c->env_trdyn = !(td && td[0] == '0'); }      // 0: k_trace walks its blocks with a fixed stride (rounds 1-5)
 		char const * ta = getenv("DACC_T7_ADAPT"); c->env_t7adapt = !(ta && ta[0] == '0');      // 0: tier 7 stays on whatever it hands on
@@ -502,12 +503,12 @@ void dacc_destroy(dacc_ctx * c)
 	c->d_bps.release(); c->d_boff.release(); c->d_rlen.release();
 	c->d_piles.release(); c->d_ovl.release(); c->d_ovl_pile.release(); c->d_trace.release(); c->d_blk_ovl.release(); c->d_blk_b0.release(); c->d_wt_b.release(); c->d_wt_e.release();
 	c->d_wrec.release(); c->d_wout.release(); c->d_arena.release();
-	c->h_outsym.release(); c->d_pilebad.release(); c->d_has.release(); c->d_oc.release(); c->d_outsym.release(); c->d_ld0.release(); c->d_ocs.release(); c->d_nfrag.release(); c->d_err.release(); c->d_frags.release(); c->d_fragbase.release(); c->d_prof.release(); c->d_vst.release(); c->d_tab32.release(); c->d_gslab.release(); c->d_lastslab.release(); c->d_vdeepslab.release(); c->d_xdeepslab.release(); c->d_longslab.release(); c->d_longhand[0].release(); c->d_longhand[1].release(); for ( int i = 0; i < 3; ++i ) c->d_retry[i].release(); c->d_work.release(); c->d_gearly.release(); c->d_pregen.release(); c->d_pregen2.release(); c->d_pregenlist.release(); c->d_arena2.release(); c->d_trslab.release(); c->d_hand.release(); c->d_handctr.release();
+	c->h_outsym.release(); c->d_pilebad.release(); c->d_has.release(); c->d_oc.release(); c->d_outsym.release(); c->d_ld0.release(); c->d_ocs.release(); c->d_nfrag.release(); c->d_err.release(); c->d_frags.release(); c->d_fragbase.release(); c->d_prof.release(); c->d_vst.release(); c->d_tab32.release(); c->d_gslab.release(); c->d_longslab.release(); c->d_longhand[0].release(); c->d_longhand[1].release(); for ( int i = 0; i < 3; ++i ) c->d_retry[i].release(); c->d_work.release(); c->d_gearly.release(); c->d_pregen.release(); c->d_pregen2.release(); c->d_pregenlist.release(); c->d_arena2.release(); c->d_trslab.release(); c->d_hand.release(); c->d_handctr.release();
 	for ( int i = 0; i < 6; ++i ) hipEventDestroy(c->ev[i]);
 	for ( int i = 0; i < 2; ++i ) hipEventDestroy(c->evEmit[i]);
 	for ( int i = 0; i < 4; ++i ) hipEventDestroy(c->evLong[i]);
 	hipStreamDestroy(c->stream); hipStreamDestroy(c->stream2); hipEventDestroy(c->evFirstTier); hipEventDestroy(c->evEarlyGeneric); hipEventDestroy(c->evPrescan); for ( int i = 0; i < TIER_NSLOTS; ++i ) hipEventDestroy(c->evslot[i]);
-	c->d_small.release(); for ( int i = 0; i < TIER_NSTAGES; ++i ) { hipEventDestroy(c->st[i].done); c->st[i].handon.release(); }
+	c->d_small.release(); for ( int i = 0; i < TIER_NSTAGES; ++i ) { hipEventDestroy(c->st[i].done); c->st[i].handon.release(); c->st[i].slab.release(); }
 	delete c;
 }
 
@@ -572,6 +573,18 @@ static int dacc_load_db_body(dacc_ctx * c, uint8_t const * bps, uint64_t bps_byt
 	c->havedb = true;
 	return DACC_OK;
 }
+
+// dacc_timing's counters of the stages that pass on untouched what is not theirs, in chain order.  `deeper`: the stage's own share are the windows of more than
+// `mins` strings on the list it read (windows + out) and on the list it handed on (out), counted by k_count_deeper into two words of d_work from the final
+// window records (behind the scratch retries of the generic engine); else everything on its list is its own: the difference of the two list lengths -- what the
+// last stage handed on is what k_window ran, or what the very deep stage read.  The deepest stage counts with the very deep stage's threshold: what it read with
+// more than VDEEP_MINS strings is vdeep_out where that stage ran.  `ms`: a trailing stage's kernel time (the deep-window tier's has a start event of its own)
+struct StageCounters { TierId id; float dacc_timing::* ms; uint32_t dacc_timing::* windows, dacc_timing::* out; bool deeper; uint32_t mins, countwords; };
+static StageCounters const STAGE_COUNTERS[] = {
+	{ ID_DEEP, nullptr, &dacc_timing::deep_windows, &dacc_timing::deep_out, true, FastTier<12>::mins, WORK_DEEP_COUNT },
+	{ ID_LAST, &dacc_timing::last_ms, &dacc_timing::last_windows, &dacc_timing::last_out, false, 0, 0 },
+	{ ID_VDEEP, &dacc_timing::vdeep_ms, &dacc_timing::vdeep_windows, &dacc_timing::vdeep_out, true, VDEEP_MINS, WORK_VDEEP_COUNT },
+	{ ID_XDEEP, &dacc_timing::xdeep_ms, &dacc_timing::xdeep_windows, &dacc_timing::xdeep_out, true, VDEEP_MINS, WORK_XDEEP_COUNT } };
 
 static int runDevice(dacc_ctx * c)
 {
@@ -641,7 +654,7 @@ static int runDevice(dacc_ctx * c)
 					TP.slot1_long ? c->d_retry[0].p : static_cast<uint32_t *>(0),c->d_wout.p);
 			}
 			HIPCHK(hipEventRecord(c->evPrescan,s));
-			FastBatch FL; FL.W = WB; FL.W.arena = c->d_arena2.p; FL.W.prof = 0; FL.W.pregen = 0; FL.F = BP.ftierL; FL.dpsq_vst = c->d_vst.p; FL.retry = 0; FL.gearly = 0; FL.gslab = 0; FL.gstride = 0; FL.tab32 = c->d_tab32.p; FL.hand = 0; FL.handctr = 0; FL.handcap = 0; FL.handwords = 0;
+			FastBatch FL; FL.W = WB; FL.W.arena = c->d_arena2.p; FL.W.prof = 0; FL.W.pregen = 0; FL.F = BP.stageCaps(ID_LONG); FL.dpsq_vst = c->d_vst.p; FL.retry = 0; FL.gearly = 0; FL.gslab = 0; FL.gstride = 0; FL.tab32 = c->d_tab32.p; FL.hand = 0; FL.handctr = 0; FL.handcap = 0; FL.handwords = 0;
 #if defined(DACC_LEDGER)
 			FL.ledger = 0;
 #endif
@@ -710,7 +723,7 @@ static int runDevice(dacc_ctx * c)
 			// the chain (tier_pipeline.hpp): every slot takes the windows the previous one handed over (list = 0: all windows)
 			auto const work = [&](uint32_t const off) { return (c->sched&1) ? c->d_work.p+off : static_cast<uint32_t *>(0); };
 			uint32_t const * list = 0; int lastslot = -1;
-			FastBatch FZ;      // the last stage's batch record: that of the last slot that ran, with its own capacities, list and slab
+			FastBatch FZ;      // the trailing stages' batch record: that of the last slot that ran, with their own capacities, list and slab
 			for ( uint32_t slot = 0; slot < TIER_NSLOTS; ++slot )
 			{
 				if ( TP.slotok(slot) )
@@ -773,44 +786,21 @@ static int runDevice(dacc_ctx * c)
 				hipEventRecord(c->evslot[slot],s);
 			}
 			uint32_t const * const slotlist = list;      // what the last enabled slot handed on (dacc_debug_retry, tier_out)
-			if ( TP.ok[ID_LAST] && list && lastslot >= 0 )
-			{
-				// the last stage (tier 13, wide batches 14: layout in device memory) takes that list and hands on to the generic engine.  It skips the windows
-				// the second stream has, like every slot behind the first, and feeds no early list (the early kernel has read its list)
-				dacc_ctx::Stage & S = c->st[ID_LAST];
-				FZ.F = BP.stageCaps(ID_LAST); FZ.retry = S.handon.p; FZ.gearly = 0; FZ.gslab = c->d_lastslab.p; FZ.gstride = FZ.F.gbytes;
-				FZ.W.pregen = (TP.late_long || TP.widetier) ? c->d_pregen2.p : c->d_pregen.p;
-				HIPCHK(hipMemsetAsync(S.handon.p,0,sizeof(uint32_t),s));
-				hipLaunchKernelGGL(fastKernel(TP.tier[ID_LAST]),dim3(S.grid),dim3(64),0,s,FZ,list,work(TIER_CHAIN[ID_LAST].work));
-				HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = list;
-				list = S.handon.p;
-			}
-			if ( TP.ok[ID_VDEEP] && list && lastslot >= 0 )
-			{
-				// the very deep stage (tier 15: windows of 251 ... 1000 strings, layout in device memory; resolved only for a batch that has such a window)
-				// takes what the last stage handed on -- the last slot's list where that stage did not run --, passes the windows of at most 250 strings
-				// on as they came and hands on to the generic engine.  Same bit map of skipped windows as the last stage, no early list
-				dacc_ctx::Stage & S = c->st[ID_VDEEP];
-				FZ.F = BP.stageCaps(ID_VDEEP); FZ.retry = S.handon.p; FZ.gearly = 0; FZ.gslab = c->d_vdeepslab.p; FZ.gstride = FZ.F.gbytes;
-				FZ.W.pregen = (TP.late_long || TP.widetier) ? c->d_pregen2.p : c->d_pregen.p;
-				HIPCHK(hipMemsetAsync(S.handon.p,0,sizeof(uint32_t),s));
-				hipLaunchKernelGGL(fastKernel(TP.tier[ID_VDEEP]),dim3(S.grid),dim3(64),0,s,FZ,list,work(TIER_CHAIN[ID_VDEEP].work));
-				HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = list;
-				list = S.handon.p;
-			}
-			if ( TP.ok[ID_XDEEP] && list && lastslot >= 0 )
-			{
-				// the deepest stage (tier 16: windows of 1001 ... 2000 strings and what tier 15 overflowed on, layout in device memory; resolved only for a
-				// batch with a window of more than 1000 strings) takes what the very deep stage handed on -- the last stage's or the last slot's list where
-				// the stages in front did not run --, passes the windows of at most 250 strings on as they came and hands on to the generic engine
-				dacc_ctx::Stage & S = c->st[ID_XDEEP];
-				FZ.F = BP.stageCaps(ID_XDEEP); FZ.retry = S.handon.p; FZ.gearly = 0; FZ.gslab = c->d_xdeepslab.p; FZ.gstride = FZ.F.gbytes;
-				FZ.W.pregen = (TP.late_long || TP.widetier) ? c->d_pregen2.p : c->d_pregen.p;
-				HIPCHK(hipMemsetAsync(S.handon.p,0,sizeof(uint32_t),s));
-				hipLaunchKernelGGL(fastKernel(TP.tier[ID_XDEEP]),dim3(S.grid),dim3(64),0,s,FZ,list,work(TIER_CHAIN[ID_XDEEP].work));
-				HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = list;
-				list = S.handon.p;
-			}
+			// the trailing stages (tier_pipeline.hpp: layout in device memory), in chain order: each takes the list the stage or slot in front of it that ran
+			// handed on and hands on to the next, the last to the generic engine; one that does not run (switched off, no window deep enough in the batch)
+			// leaves the list as it is.  They skip the windows the second stream has, like every slot behind the first, and feed no early list (the early
+			// kernel has read its list)
+			for ( uint32_t i = 0; i < TIER_NSTAGES; ++i )
+				if ( TIER_CHAIN[i].role == ROLE_LAST && TP.ok[i] && list && lastslot >= 0 )
+				{
+					dacc_ctx::Stage & S = c->st[i];
+					FZ.F = BP.stageCaps(i); FZ.retry = S.handon.p; FZ.gearly = 0; FZ.gslab = S.slab.p; FZ.gstride = FZ.F.gbytes;
+					FZ.W.pregen = (TP.late_long || TP.widetier) ? c->d_pregen2.p : c->d_pregen.p;
+					HIPCHK(hipMemsetAsync(S.handon.p,0,sizeof(uint32_t),s));
+					hipLaunchKernelGGL(fastKernel(TP.tier[i]),dim3(S.grid),dim3(64),0,s,FZ,list,work(TIER_CHAIN[i].work));
+					HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = list;
+					list = S.handon.p;
+				}
 			if ( c->env_dbgretry && slotlist )
 			{
 				uint32_t const * const list = slotlist;
@@ -933,48 +923,25 @@ static int runDevice(dacc_ctx * c)
 		mark("k_window (scratch retry)");
 		int const rc = voteAndFetch(); if ( rc ) return rc;
 	}
-	// the deep-window tier passes the windows of at most FastTier<12>::mins strings on untouched: its own share are the windows with more strings
-	// on the list it read (deep_windows + deep_out) and on the list it handed on (deep_out), counted from the final window records (behind the scratch retries of the generic engine)
-	c->timing.deep_windows = 0; c->timing.deep_out = 0;
-	// the last stage: what it read is what the last slot handed on, what it handed on is what k_window ran -- or, in a batch with a window of more
-	// than 250 strings, what the very deep stage read
-	c->timing.last_windows = 0; c->timing.last_out = 0;
-	if ( dacc_ctx::Stage const * const fZ = ranOf(ID_LAST) )
+	// the counters of the deep-window tier and of the trailing stages (STAGE_COUNTERS), zero for a stage that did not run.  A trailing stage's time runs from
+	// the nearest trailing stage in front of it that ran, else from the last slot
+	hipEvent_t from = c->evslot[TIER_NSLOTS-1];
+	for ( StageCounters const & K : STAGE_COUNTERS )
 	{
-		uint32_t nin = 0, nout = 0;
-		HIPCHK(hipMemcpy(&nin,fZ->in,sizeof(uint32_t),hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&nout,fZ->handon.p,sizeof(uint32_t),hipMemcpyDeviceToHost));
-		c->timing.last_out = nout; c->timing.last_windows = nin > nout ? nin - nout : 0u;
-	}
-	// the very deep stage passes the windows of at most VDEEP_MINS strings on untouched, like the deep-window tier: its own share is counted the same way
-	c->timing.vdeep_windows = 0; c->timing.vdeep_out = 0;
-	if ( dacc_ctx::Stage const * const fV = ranOf(ID_VDEEP) )
-	{
-		HIPCHK(hipMemsetAsync(c->d_work.p+WORK_VDEEP_COUNT,0,2*sizeof(uint32_t),s));
-		hipLaunchKernelGGL(k_count_deeper,dim3(64),dim3(256),0,s,fV->in,static_cast<uint32_t const *>(fV->handon.p),c->d_wout.p,static_cast<uint32_t>(VDEEP_MINS),c->d_work.p+WORK_VDEEP_COUNT);
-		uint32_t cnt[2] = {0,0};
-		HIPCHK(hipMemcpyAsync(cnt,c->d_work.p+WORK_VDEEP_COUNT,sizeof(cnt),hipMemcpyDeviceToHost,s));
-		HIPCHK(hipStreamSynchronize(s));
-		c->timing.vdeep_out = cnt[1]; c->timing.vdeep_windows = cnt[0] > cnt[1] ? cnt[0] - cnt[1] : 0u;
-	}
-	// the deepest stage, counted the same way with the same threshold: what it read with more than VDEEP_MINS strings is vdeep_out where the very deep stage ran
-	c->timing.xdeep_windows = 0; c->timing.xdeep_out = 0;
-	if ( dacc_ctx::Stage const * const fW = ranOf(ID_XDEEP) )
-	{
-		HIPCHK(hipMemsetAsync(c->d_work.p+WORK_XDEEP_COUNT,0,2*sizeof(uint32_t),s));
-		hipLaunchKernelGGL(k_count_deeper,dim3(64),dim3(256),0,s,fW->in,static_cast<uint32_t const *>(fW->handon.p),c->d_wout.p,static_cast<uint32_t>(VDEEP_MINS),c->d_work.p+WORK_XDEEP_COUNT);
-		uint32_t cnt[2] = {0,0};
-		HIPCHK(hipMemcpyAsync(cnt,c->d_work.p+WORK_XDEEP_COUNT,sizeof(cnt),hipMemcpyDeviceToHost,s));
-		HIPCHK(hipStreamSynchronize(s));
-		c->timing.xdeep_out = cnt[1]; c->timing.xdeep_windows = cnt[0] > cnt[1] ? cnt[0] - cnt[1] : 0u;
-	}
-	if ( fX && fX->in )
-	{
-		HIPCHK(hipMemsetAsync(c->d_work.p+WORK_DEEP_COUNT,0,2*sizeof(uint32_t),s));
-		hipLaunchKernelGGL(k_count_deeper,dim3(64),dim3(256),0,s,fX->in,static_cast<uint32_t const *>(fX->handon.p),c->d_wout.p,static_cast<uint32_t>(FastTier<12>::mins),c->d_work.p+WORK_DEEP_COUNT);
-		uint32_t cnt[2] = {0,0};
-		HIPCHK(hipMemcpyAsync(cnt,c->d_work.p+WORK_DEEP_COUNT,sizeof(cnt),hipMemcpyDeviceToHost,s));
-		HIPCHK(hipStreamSynchronize(s));
-		c->timing.deep_out = cnt[1]; c->timing.deep_windows = cnt[0] > cnt[1] ? cnt[0] - cnt[1] : 0u;
+		dacc_ctx::Stage const & S = c->st[K.id];
+		c->timing.*K.windows = 0; c->timing.*K.out = 0; if ( K.ms ) c->timing.*K.ms = 0;
+		if ( !S.ran || !S.in ) continue;
+		uint32_t cnt[2] = {0,0};      // what it read, what it handed on
+		if ( K.deeper )
+		{
+			HIPCHK(hipMemsetAsync(c->d_work.p+K.countwords,0,2*sizeof(uint32_t),s));
+			hipLaunchKernelGGL(k_count_deeper,dim3(64),dim3(256),0,s,S.in,static_cast<uint32_t const *>(S.handon.p),c->d_wout.p,K.mins,c->d_work.p+K.countwords);
+			HIPCHK(hipMemcpyAsync(cnt,c->d_work.p+K.countwords,sizeof(cnt),hipMemcpyDeviceToHost,s));
+			HIPCHK(hipStreamSynchronize(s));
+		}
+		else { HIPCHK(hipMemcpy(&cnt[0],S.in,sizeof(uint32_t),hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&cnt[1],S.handon.p,sizeof(uint32_t),hipMemcpyDeviceToHost)); }
+		c->timing.*K.out = cnt[1]; c->timing.*K.windows = cnt[0] > cnt[1] ? cnt[0] - cnt[1] : 0u;
+		if ( K.ms ) { float sms = 0; hipEventElapsedTime(&sms,from,S.done); c->timing.*K.ms = sms; from = S.done; }
 	}
 	// the long string stage (wide batches, second stream): what it read is what the second stream read (long_windows), what it handed on is what k_window_long ran
 	c->timing.longstr_ms = 0; c->timing.longstr_windows = 0; c->timing.longstr_out = 0; c->timing.pad2_ = 0;
@@ -1025,10 +992,7 @@ static int runDevice(dacc_ctx * c)
 	if ( f0 ) { hipEventElapsedTime(&ms,c->ev[1],f0->done); c->timing.tier0_ms = ms; }
 	if ( f7 ) { hipEventElapsedTime(&ms,f0->done,f7->done); c->timing.tier7_ms = ms; }
 	if ( fD ) { hipEventElapsedTime(&ms,c->evslot[1],fD->done); c->timing.tier10_ms = ms; }
-	c->timing.deep_ms = 0; c->timing.last_ms = 0; c->timing.vdeep_ms = 0; c->timing.xdeep_ms = 0;
-	if ( dacc_ctx::Stage const * const fZ = ranOf(ID_LAST) ) { hipEventElapsedTime(&ms,c->evslot[TIER_NSLOTS-1],fZ->done); c->timing.last_ms = ms; }
-	if ( dacc_ctx::Stage const * const fV = ranOf(ID_VDEEP) ) { dacc_ctx::Stage const * const fZ = ranOf(ID_LAST); hipEventElapsedTime(&ms,fZ ? fZ->done : c->evslot[TIER_NSLOTS-1],fV->done); c->timing.vdeep_ms = ms; }
-	if ( dacc_ctx::Stage const * const fW = ranOf(ID_XDEEP) ) { dacc_ctx::Stage const * const fV = ranOf(ID_VDEEP), * const fZ = ranOf(ID_LAST); hipEventElapsedTime(&ms,fV ? fV->done : (fZ ? fZ->done : c->evslot[TIER_NSLOTS-1]),fW->done); c->timing.xdeep_ms = ms; }
+	c->timing.deep_ms = 0;
 	if ( fX ) { hipEventElapsedTime(&ms,fD ? fD->done : c->evslot[1],fX->done); c->timing.deep_ms = ms; }
 	hipEventElapsedTime(&ms,c->ev[2],c->ev[3]); c->timing.vote_ms = ms;
 	hipEventElapsedTime(&ms,c->evEmit[0],c->evEmit[1]); c->timing.emit_ms = ms;      // (of the last vote of the batch; a part of vote_ms)
@@ -1128,10 +1092,9 @@ static int dacc_submit_piles_body(dacc_ctx * c, dacc_pile const * piles, uint64_
 			if ( !TP.ok[i] || TIER_CHAIN[i].role == ROLE_LONG ) continue;
 			if ( TIER_CHAIN[i].role == ROLE_LAST )
 			{
-				// the last stage: its own hand-on list (what k_window reads) and its own slab, grid x gbytes <= TIER_GMEM_SLAB.  Both are optional like the
-				// hand-over buffer: a device that cannot spare them runs the batch without the stage, on the route it had before
-				// (the very deep stage, resolved only in a batch with a window of more than 250 strings, has a slab of its own: the two kernels' grids differ)
-				DevBuf<uint8_t> & slab = i == ID_XDEEP ? c->d_xdeepslab : (i == ID_VDEEP ? c->d_vdeepslab : c->d_lastslab);
+				// a trailing stage: its own hand-on list (what the next one or k_window reads) and its own slab, grid x gbytes <= TIER_GMEM_SLAB.  Both are optional
+				// like the hand-over buffer: a device that cannot spare them runs the batch without the stage, on the route it had before
+				DevBuf<uint8_t> & slab = c->st[i].slab;
 				hipError_t e = c->st[i].handon.ensure(BP.nwindows+2);
 				if ( e == hipSuccess ) e = slab.ensure(static_cast<size_t>(c->st[i].grid)*F.gbytes + 256);
 				if ( e == hipErrorOutOfMemory ) { (void)hipGetLastError(); slab.release(); c->TP.ok[i] = false; }
@@ -1160,7 +1123,7 @@ static int dacc_submit_piles_body(dacc_ctx * c, dacc_pile const * piles, uint64_
 			if ( c->d_hand.cap < static_cast<size_t>(cap)*TP.handwords ) c->handcap = static_cast<uint32_t>(c->d_hand.cap / TP.handwords);     // what an earlier batch left
 			else c->handcap = static_cast<uint32_t>(cap);
 		}
-		if ( TP.ok[ID_LONG] && TP.tier[ID_LONG] == 5 && BP.ftierL.ldsbytes > 64*1024 ) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_window_long),hipFuncAttributeMaxDynamicSharedMemorySize,BP.ftierL.ldsbytes));
+		if ( TP.ok[ID_LONG] && TP.tier[ID_LONG] == 5 && BP.stageCaps(ID_LONG).ldsbytes > 64*1024 ) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_window_long),hipFuncAttributeMaxDynamicSharedMemorySize,BP.stageCaps(ID_LONG).ldsbytes));
 		c->retry_grid = boundByArena(wg < 512 ? wg : 512,BP.caps.bytes,8);
 		c->win_grid = c->retry_grid;
 		// generic engine on the second stream (windows with a string of more than 64 bases): a wavefront per window as far

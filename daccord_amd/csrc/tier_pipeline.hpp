@@ -9,9 +9,8 @@
  *   wide batches                              slot 1: 8     slot 2: 9
  *   shallow and deep  tier 5 on the second stream (k_window_long), in front of the generic engine there
  *   wide batches      the LONG STRING stage on the second stream: tier 17 (strings of 129 ... 255 bases, layout in device memory), in front of the generic engine there
- *   every batch       the LAST stage, once, behind the slots and in front of the generic engine: tier 13 (shallow, deep) / tier 14 (wide)
- *   shallow and deep  the VERY DEEP stage, behind the last stage, only in a batch with a window of more than 250 strings: tier 15
- *   shallow and deep  the DEEPEST stage, behind the very deep stage, only in a batch with a window of more than 1000 strings: tier 16
+ *   every batch       the TRAILING stages, each once, behind the slots and in front of the generic engine: tier 13 (shallow, deep) / tier 14 (wide), then in
+ *                     shallow and deep batches tier 15 and tier 16, each only in a batch with a window deep enough for it
  *
  * (TIER_CHAIN below: one row per stage, one column per batch shape.)
  *
@@ -20,35 +19,30 @@
  * with more wavefronts per CU: each hands on to the next stage of its slot.  Tiers 0 and 7 are fed by the size-class pre-pass
  * (k_classify), tiers 10 / 11 by the list of the slot in front, tier 12 (windows of 97 ... 250 strings; it passes the others on) by what they hand on.
  *
- * The LAST stage (ID_LAST, ROLE_LAST) is no slot: its tiers keep the layout FastLds<CT> in a slab of device memory per workgroup instead of
- * LDS (FastCaps::gmem), with tables no CU's LDS could hold.  It reads the list the last enabled slot handed on and hands on to the generic
- * engine (k_window), which recomputes both enumerations for every (first, last) k-mer pair and is two to three orders of magnitude slower per
- * window.  DACC_LAST_TIER=0 removes it; it does not run when no slot runs.  DACC_LAST_AS_SLOT2=1 (tests, A/B timing) makes the last stage's
- * tier the main tier of the third slot instead (13 for 3, 14 for 9) and switches ID_LAST off: the planner, the launches and the emulation
- * harness then run the device-memory tiers as an ordinary slot.
+ * A TRAILING stage (ROLE_LAST) is no slot: its tier keeps the layout FastLds<CT> in a slab of device memory per workgroup instead of LDS (FastCaps::gmem),
+ * with tables no CU's LDS could hold.  It reads the list the nearest stage in front of it that ran handed on -- a trailing stage, else the last enabled
+ * slot -- and hands on to the next one, the last to the generic engine (k_window), which recomputes both enumerations for every (first, last) k-mer
+ * pair and is two to three orders of magnitude slower per window.  It does not run when no slot runs.  Its row of TIER_CHAIN names its two switches and
+ * its threshold: DACC_*_TIER=0 removes it (the chain as it was before the stage); its slab is allocated and its kernel launched only in a batch whose
+ * deepest window has more strings than the threshold (resolveTiers: maxstrings), so every other batch runs the launches it ran before the stage existed;
+ * DACC_*_AS_SLOT2=1 (tests, A/B timing) makes its tier the main tier of the third slot instead, with the slot's front tiers still in front of it, and
+ * switches the stage off: the planner, the launches and the emulation harness then run the device-memory tier as an ordinary slot.  Each of these names
+ * the third slot's main tier, so more than one of them is an error (TierSwitches::conflict).
  *
- * The VERY DEEP stage (ID_VDEEP, ROLE_LAST as well) runs tier 15 -- windows of 251 ... 1000 strings, which every other tier refuses at its string
- * count; it passes the others on untouched -- over the list the last stage handed on (without a last stage: the last enabled slot's list) and hands
- * on to the generic engine.  Its slab is allocated and its kernel launched only in a batch whose deepest window has more than 250 strings
- * (resolveTiers: maxstrings), so every other batch runs the launches it ran before the stage existed; a wide batch has no such tier.
- * DACC_VDEEP_TIER=0 removes it.  DACC_VDEEP_AS_SLOT2=1 (tests) makes tier 15 the main tier of the third slot of shallow and deep batches, with
- * tier 12 still in front of it, and switches ID_VDEEP off.
- *
- * The DEEPEST stage (ID_XDEEP, ROLE_LAST as well) runs tier 16 -- windows of 1001 ... 2000 strings, and those of 251 ... 1000 that overflowed a table
- * of tier 15; it passes the windows of at most 250 strings on untouched -- over the list the very deep stage handed on (without it: the last stage's
- * or the last enabled slot's list) and hands on to the generic engine.  Its slab is allocated and its kernel launched only in a batch whose deepest
- * window has more than XDEEP_MINS = 1000 strings, so every other batch runs the launches it ran before the stage existed.  DACC_XDEEP_TIER=0 removes
- * it.  DACC_XDEEP_AS_SLOT2=1 (tests) makes tier 16 the main tier of the third slot of shallow and deep batches, with tier 12 still in front of it,
- * and switches ID_XDEEP off.
+ *   stage      tier                        its windows                                        =0 removes it     =1: the third slot's main tier            threshold
+ *   ID_LAST    13 (shallow, deep) / 14     what overflowed a table of the slots, up to 250    DACC_LAST_TIER    DACC_LAST_AS_SLOT2 (13 for 3, 14 for 9)   0: every batch
+ *              (wide)                      strings
+ *   ID_VDEEP   15 (shallow, deep)          251 ... 1000 strings, which every tier in front    DACC_VDEEP_TIER   DACC_VDEEP_AS_SLOT2 (a wide batch keeps   VDEEP_MINS = 250
+ *                                          refuses at its string count; others passed on                        tier 9)
+ *   ID_XDEEP   16 (shallow, deep)          1001 ... 2000 strings, and those of 251 ... 1000   DACC_XDEEP_TIER   DACC_XDEEP_AS_SLOT2 (a wide batch keeps   XDEEP_MINS = 1000
+ *                                          that overflowed a table of tier 15; those of at                      tier 9)
+ *                                          most 250 passed on
  *
  * The LONG STRING stage (ID_LONG in a wide batch, ROLE_LONG) runs tier 17 -- tier 14 with four words per pattern mask, strings of up to 255 bases -- over the
  * two lists of the second stream (the pre-scan's: a B string of more than 128 bases; the first tier's generic-only windows) with a kernel of its own,
  * k_window_fast<17>, in front of k_window_long, which then runs the generic engine alone over what the tier handed on (a string of more than 255 bases,
  * a table that overflowed).  Its slab is allocated and its kernel launched only for a list that is not empty.  DACC_LONGSTR_TIER=0 removes it: a wide
  * batch's second stream is then the generic engine alone, as before the stage.  Shallow and deep batches keep tier 5 inside k_window_long.
- *
- * More than one of DACC_LAST_AS_SLOT2=1, DACC_VDEEP_AS_SLOT2=1 and DACC_XDEEP_AS_SLOT2=1 is an error (TierSwitches::conflict): each names the third
- * slot's main tier.
  */
 #ifndef DACC_TIER_PIPELINE_HPP
 #define DACC_TIER_PIPELINE_HPP
@@ -98,10 +92,8 @@ enum : uint32_t
 	GATE_DENSE = 8,       // DACC_DENSE_TIER=0 switches it off
 	GATE_PREV_SLOT = 16,  // needs the main tier of the slot in front as well (the dense tiers need slots 1 and 2)
 	GATE_DEEP = 128,      // DACC_DEEP_TIER=0 switches it off (windows of more than 96 strings run in the generic engine, as before the deep-window tier)
-	GATE_LAST = 256,      // DACC_LAST_TIER=0 or DACC_LAST_AS_SLOT2=1 switches it off; needs a slot that ran
-	GATE_XDEEP = 1024,    // DACC_XDEEP_TIER=0 or DACC_XDEEP_AS_SLOT2=1 switches it off; needs a slot that ran and a window of more than XDEEP_MINS strings in the batch
+	GATE_TRAILING = 256,  // a trailing stage: its row's DACC_*_TIER=0 or DACC_*_AS_SLOT2=1 switches it off; needs a slot that ran and a window of more strings than its row's minstrings in the batch
 	GATE_LONGSTR = 2048,  // DACC_LONGSTR_TIER=0 switches it off in a wide batch (the second stream of a wide batch is then the generic engine alone); no gate in the other shapes
-	GATE_VDEEP = 512,     // DACC_VDEEP_TIER=0 or DACC_VDEEP_AS_SLOT2=1 switches it off; needs a slot that ran and a window of more than VDEEP_MINS strings in the batch
 	STAGE_PREPASS = 32,   // (no gate) fed by the size-class pre-pass instead of the list in front of it
 	STAGE_ADAPTIVE = 64   // (no gate) switches itself off for the rest of a context when it hands on too much (DACC_T7_ADAPT)
 };
@@ -122,7 +114,15 @@ enum TierId { ID_T0, ID_T7, ID_SLOT0, ID_SLOT1, ID_DENSE, ID_DEEP, ID_SLOT2, ID_
 enum { TIER_NSLOTS = 3, TIER_NONE = 255, TIER_SHALLOW_FIRST = 1 };      // (the first slot's main tier of shallow batches: a batch whose windows mostly overflow its strings / instances is deep)
 enum : uint32_t { VDEEP_MINS = 250 };      // the very deep stage takes the windows with more strings than this (= FastTier<15>::mins = FastTier<13>::maxs, fast_window.hpp)
 enum : uint32_t { XDEEP_MINS = 1000 };     // the deepest stage is resolved for a batch with a window of more strings than this (= FastTier<15>::maxs); its tier takes what has more than VDEEP_MINS
-struct TierStage { uint8_t tier[3] /* in a shallow, deep, wide batch */, slot, role; int8_t tiersbit /* bit of DACC_TIERS */; uint32_t flags, work; };
+struct TierStage
+{
+	uint8_t tier[3] /* in a shallow, deep, wide batch */, slot, role; int8_t tiersbit /* bit of DACC_TIERS */; uint32_t flags, work;
+	// a trailing stage (ROLE_LAST) only
+	char const * offswitch = nullptr;      // DACC_*_TIER: 0 removes the stage
+	char const * slot2switch = nullptr;    // DACC_*_AS_SLOT2: 1 makes its tier the main tier of the third slot and switches the stage off
+	uint32_t minstrings = 0;               // resolved only for a batch whose deepest window has more strings than this (0: every batch)
+	bool slot2wide = false;                // does its AS_SLOT2 switch apply to a wide batch (else that keeps tier 9)
+};
 static TierStage const TIER_CHAIN[TIER_NSTAGES] = {
 	{ { 0, TIER_NONE, TIER_NONE }, 0, ROLE_FRONT, 3, STAGE_PREPASS, WORK_T0 },
 	{ { 7, TIER_NONE, TIER_NONE }, 0, ROLE_FRONT, 4, STAGE_PREPASS|STAGE_ADAPTIVE|GATE_PREV_FRONT|GATE_T7_ABOVE_T0, WORK_T7 },
@@ -131,9 +131,9 @@ static TierStage const TIER_CHAIN[TIER_NSTAGES] = {
 	{ { 10, 11, TIER_NONE }, 2, ROLE_FRONT, -1, GATE_TABFIT|GATE_DENSE|GATE_PREV_SLOT, WORK_DENSE },
 	{ { 12, 12, TIER_NONE }, 2, ROLE_FRONT, -1, GATE_TABFIT|GATE_DEEP|GATE_PREV_SLOT, WORK_DEEP },
 	{ { 3, 3, 9 }, 2, ROLE_MAIN, 2, GATE_TABFIT, WORK_SLOT2 },
-	{ { 13, 13, 14 }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_LAST, WORK_LAST },
-	{ { 15, 15, TIER_NONE }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_VDEEP, WORK_VDEEP },
-	{ { 16, 16, TIER_NONE }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_XDEEP, WORK_XDEEP },
+	{ { 13, 13, 14 }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_TRAILING, WORK_LAST, "DACC_LAST_TIER", "DACC_LAST_AS_SLOT2", 0, true },
+	{ { 15, 15, TIER_NONE }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_TRAILING, WORK_VDEEP, "DACC_VDEEP_TIER", "DACC_VDEEP_AS_SLOT2", VDEEP_MINS, false },
+	{ { 16, 16, TIER_NONE }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_TRAILING, WORK_XDEEP, "DACC_XDEEP_TIER", "DACC_XDEEP_AS_SLOT2", XDEEP_MINS, false },
 	// (tier 5 holds no wide window and no string of more than 128 bases: a wide batch's second stream runs tier 17, a kernel of its own over a slab in device
 	// memory, and the generic engine behind it)
 	{ { 5, 5, 17 }, 0, ROLE_LONG, 2, GATE_TABFIT|GATE_LONGSTR, WORK_LONGSTR } };
@@ -141,17 +141,13 @@ static TierId const TIER_MAIN[TIER_NSLOTS] = { ID_SLOT0, ID_SLOT1, ID_SLOT2 };
 // does the stage run in a batch of this shape, and the tier whose capacities the plan holds for it (a stage that does not run keeps
 // those of the nearest shape: the first slot of a wide batch has tier 1's or tier 4's)
 static inline bool stageRuns(TierStage const & st, bool const deep, bool const wide) { return st.tier[wide ? 2 : deep] != TIER_NONE; }
-// DACC_LAST_AS_SLOT2=1: the third slot's main tier is the last stage's tier (read by the planner and by resolveTiers alike, so once per call)
-static inline bool lastAsSlot2() { char const * const e = getenv("DACC_LAST_AS_SLOT2"); return e && e[0] == '1'; }
-// DACC_VDEEP_AS_SLOT2=1: the third slot's main tier of shallow and deep batches is the very deep stage's tier (a wide batch keeps tier 9)
-static inline bool vdeepAsSlot2() { char const * const e = getenv("DACC_VDEEP_AS_SLOT2"); return e && e[0] == '1'; }
-// DACC_XDEEP_AS_SLOT2=1: the same with the deepest stage's tier
-static inline bool xdeepAsSlot2() { char const * const e = getenv("DACC_XDEEP_AS_SLOT2"); return e && e[0] == '1'; }
+// DACC_*_AS_SLOT2=1 of a trailing stage's row: the third slot's main tier is that stage's tier (read by the planner and by resolveTiers alike, so once per call)
+static inline bool stageAsSlot2(TierStage const & st) { char const * const e = st.slot2switch ? getenv(st.slot2switch) : 0; return e && e[0] == '1'; }
 static inline uint32_t stageTier(TierStage const & st, bool const deep, bool const wide)
 {
-	bool const slot2 = &st == &TIER_CHAIN[ID_SLOT2];
-	TierStage const & t = (slot2 && lastAsSlot2()) ? TIER_CHAIN[ID_LAST] : ((slot2 && !wide && vdeepAsSlot2()) ? TIER_CHAIN[ID_VDEEP] : ((slot2 && !wide && xdeepAsSlot2()) ? TIER_CHAIN[ID_XDEEP] : st));
-	return (wide && t.tier[2] != TIER_NONE) ? t.tier[2] : (t.tier[deep] != TIER_NONE ? t.tier[deep] : t.tier[0]);
+	TierStage const * t = &st;
+	if ( &st == &TIER_CHAIN[ID_SLOT2] ) for ( TierStage const & r : TIER_CHAIN ) if ( stageAsSlot2(r) && (!wide || r.slot2wide) ) { t = &r; break; }
+	return (wide && t->tier[2] != TIER_NONE) ? t->tier[2] : (t->tier[deep] != TIER_NONE ? t->tier[deep] : t->tier[0]);
 }
 
 // the environment switches of the chain, read once per context
@@ -162,14 +158,10 @@ struct TierSwitches
 	bool widetier;            // DACC_WIDE_TIER=0: wide batches run in the generic engine only, as in rounds 4-5
 	bool dense;               // DACC_DENSE_TIER=0: the second slot hands on to tier 3 directly (before round 6's dense tiers)
 	bool deepwin;             // DACC_DEEP_TIER=0: no deep-window tier (tier 12) in front of tier 3
-	bool lasttier;            // DACC_LAST_TIER=0: no device-memory stage in front of the generic engine (the chain as it was before that stage)
-	bool last_as_slot2;       // DACC_LAST_AS_SLOT2=1: tier 13 / 14 as the third slot's main tier, no last stage
-	bool vdeeptier;           // DACC_VDEEP_TIER=0: no very deep stage (windows of more than 250 strings run in the generic engine, as before that stage)
-	bool vdeep_as_slot2;      // DACC_VDEEP_AS_SLOT2=1: tier 15 as the third slot's main tier of shallow and deep batches, no very deep stage
-	bool xdeeptier;           // DACC_XDEEP_TIER=0: no deepest stage (windows of more than 1000 strings run in the generic engine, as before that stage)
-	bool xdeep_as_slot2;      // DACC_XDEEP_AS_SLOT2=1: tier 16 as the third slot's main tier of shallow and deep batches, no deepest stage
+	bool off[TIER_NSTAGES];        // a trailing stage's DACC_*_TIER=0: the chain as it was before that stage (its windows run in what stands behind it)
+	bool as_slot2[TIER_NSTAGES];   // a trailing stage's DACC_*_AS_SLOT2=1: its tier as the third slot's main tier, no such stage
 	bool longstr;             // DACC_LONGSTR_TIER=0: no long string stage (tier 17) on the second stream of a wide batch, the generic engine alone as before that stage
-	bool conflict() const { return static_cast<int>(last_as_slot2) + static_cast<int>(vdeep_as_slot2) + static_cast<int>(xdeep_as_slot2) > 1; }      // more than one wants the third slot: dacc_create refuses
+	bool conflict() const { int n = 0; for ( bool const b : as_slot2 ) n += b; return n > 1; }      // more than one wants the third slot: dacc_create refuses
 	bool long128;             // DACC_LONG128=0: windows with a string of 65 ... 128 bases run in tier 5 on the second stream (rounds 3-5)
 	bool hand;                // DACC_HAND=0: no hand-over buffer, every hand-over restarts from the strings
 	uint32_t t0inst, t7inst;  // DACC_T0INST / DACC_T7INST: size-class thresholds (k-mer instances) of tiers 0 and 7
@@ -182,7 +174,8 @@ static inline TierSwitches readTierSwitches()
 	TierSwitches S;
 	{ char const * const e = getenv("DACC_NOFAST"); S.nofast = e && e[0] == '1'; }
 	S.tiers = num("DACC_TIERS",31);
-	S.widetier = !off("DACC_WIDE_TIER"); S.dense = !off("DACC_DENSE_TIER"); S.deepwin = !off("DACC_DEEP_TIER"); S.lasttier = !off("DACC_LAST_TIER"); S.last_as_slot2 = lastAsSlot2(); S.vdeeptier = !off("DACC_VDEEP_TIER"); S.vdeep_as_slot2 = vdeepAsSlot2(); S.xdeeptier = !off("DACC_XDEEP_TIER"); S.xdeep_as_slot2 = xdeepAsSlot2(); S.longstr = !off("DACC_LONGSTR_TIER"); S.long128 = !off("DACC_LONG128"); S.hand = !off("DACC_HAND");
+	S.widetier = !off("DACC_WIDE_TIER"); S.dense = !off("DACC_DENSE_TIER"); S.deepwin = !off("DACC_DEEP_TIER"); S.longstr = !off("DACC_LONGSTR_TIER"); S.long128 = !off("DACC_LONG128"); S.hand = !off("DACC_HAND");
+	for ( uint32_t i = 0; i < TIER_NSTAGES; ++i ) { TierStage const & st = TIER_CHAIN[i]; S.off[i] = st.offswitch && off(st.offswitch); S.as_slot2[i] = stageAsSlot2(st); }
 	S.t0inst = num("DACC_T0INST",T0INST_DEFAULT); S.t7inst = num("DACC_T7INST",T7INST_DEFAULT);
 	S.lds_t1 = num("DACC_LDS_T1",0); S.lds_t0 = num("DACC_LDS_T0",0);
 	return S;
@@ -227,8 +220,8 @@ struct TierPipeline
 
 // fastpath: the caller's own conditions (not switched off, a model table that fits 32 bit fixed point).  capsOf(id): the plan's capacities
 // of a stage (BatchPlan::stageCaps); the measurement switches DACC_LDS_T1 / DACC_LDS_T0 raise the LDS sizes in them.
-// maxstrings: strings of the deepest window of the batch (BatchPlan::maxstrings); the very deep stage and the deepest stage are resolved only for a batch that has a
-// window for them -- a caller that walks the slots only (the emulation harness) leaves it out and sees no such stage.
+// maxstrings: strings of the deepest window of the batch (BatchPlan::maxstrings); a trailing stage with a threshold (TierStage::minstrings) is resolved only for a batch that has a
+// window for it -- a caller that walks the slots only (the emulation harness) leaves it out and sees no such stage.
 template<typename C>
 static inline TierPipeline resolveTiers(TierSwitches const & S, bool const fastpath, bool const deep, bool const wide, uint32_t const nrows, uint32_t const nsup, uint32_t const w, C && capsOf,
 	uint32_t const maxstrings = 0)
@@ -245,17 +238,14 @@ static inline TierPipeline resolveTiers(TierSwitches const & S, bool const fastp
 		return R.usefast && stageRuns(st,deep,wide) && (F.gmem || F.ldsbytes <= TIER_LDS_CU) && (st.tiersbit < 0 || ((S.tiers >> st.tiersbit) & 1))
 			&& (!(st.flags & GATE_TABFIT) || static_cast<uint64_t>(nrows+1)*(nsup+1) <= F.tabcap)
 			&& (!(st.flags & GATE_T7_ABOVE_T0) || S.t7inst > S.t0inst) && (!(st.flags & GATE_DENSE) || S.dense) && (!(st.flags & GATE_DEEP) || S.deepwin)
-			&& (!(st.flags & GATE_LAST) || (S.lasttier && !S.last_as_slot2))
-			&& (!(st.flags & GATE_VDEEP) || (S.vdeeptier && !S.vdeep_as_slot2 && maxstrings > VDEEP_MINS))
-			&& (!(st.flags & GATE_XDEEP) || (S.xdeeptier && !S.xdeep_as_slot2 && maxstrings > XDEEP_MINS))
+			&& (!(st.flags & GATE_TRAILING) || (!S.off[i] && !S.as_slot2[i] && (!st.minstrings || maxstrings > st.minstrings)))
 			&& (!(st.flags & GATE_LONGSTR) || !wide || S.longstr);
 	};
 	{ FastCaps & F = capsOf(ID_SLOT0); if ( S.lds_t1 > F.ldsbytes && S.lds_t1 <= TIER_LDS_CU ) F.ldsbytes = S.lds_t1; }
 	{ FastCaps & F = capsOf(ID_T0); if ( S.lds_t0 > F.ldsbytes && S.lds_t0 <= TIER_LDS_CU ) F.ldsbytes = S.lds_t0; }
 	for ( uint32_t i = 0; i < TIER_NSTAGES; ++i ) { R.tier[i] = stageTier(TIER_CHAIN[i],deep,wide); if ( TIER_CHAIN[i].role != ROLE_FRONT ) R.ok[i] = gated(i); }
-	R.ok[ID_LAST] = R.ok[ID_LAST] && R.anytier();      // it reads what a slot handed on: no slot, no last stage (generic-only configurations stay generic-only)
-	R.ok[ID_VDEEP] = R.ok[ID_VDEEP] && R.anytier();
-	R.ok[ID_XDEEP] = R.ok[ID_XDEEP] && R.anytier();
+	// a trailing stage reads what a slot handed on: no slot, no such stage (generic-only configurations stay generic-only)
+	for ( uint32_t i = 0; i < TIER_NSTAGES; ++i ) if ( TIER_CHAIN[i].role == ROLE_LAST ) R.ok[i] = R.ok[i] && R.anytier();
 	// the front tiers, in chain order (a front tier stands before the main tier of its slot)
 	for ( uint32_t i = 0; i < TIER_NSTAGES; ++i )
 	{

@@ -65,6 +65,20 @@ def test_switch_off_sends_them_to_the_generic_engine(monkeypatch):
     E.close()
 
 
+def test_without_the_last_stage_it_reads_the_last_slots_list(monkeypatch):
+    """DACC_LAST_TIER=0: no trailing stage in front of it, so the stage takes what the third slot handed on; the same 131 windows finish in it"""
+    monkeypatch.setenv("DACC_LAST_TIER", "0")
+    wo, fo, bo = vc.oracle("M")
+    E, fx, bx = _device_run("M", 14)
+    wx = E.debug_windows(); t = E.timing()
+    _report("M, no last stage", t, len(wx))
+    assert windows_equal(wo, wx) == [] and frags_equal(fo, bo, fx, bx)
+    assert t.vdeep_windows == 131 and t.vdeep_out == 0
+    assert t.last_ms == 0.0 and (t.last_windows, t.last_out) == (0, 0)
+    assert t.vdeep_ms > 0
+    E.close()
+
+
 def test_shallow_batch_does_not_launch_the_stage():
     """the shape of __graft_entry__.smoke(): no window of more than 250 strings, so no slab and no launch"""
     d = SynthData(60000, 150, 3000, seed=2)

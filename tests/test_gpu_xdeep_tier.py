@@ -56,6 +56,22 @@ def test_exactly_1001_and_2000_strings_finish_in_the_stage(maxalign):
     E.close()
 
 
+def test_without_the_stages_in_front_it_reads_the_last_slots_list(monkeypatch):
+    """DACC_LAST_TIER=0 and DACC_VDEEP_TIER=0: no trailing stage in front of it, so the stage takes what the third slot handed on.  The 37 windows of exactly
+    1001 strings are those tiers 13 and 15 refuse at their string count in the default run: tier 16 sees no window it does not see there, and none of more
+    than 1000 strings reaches k_window"""
+    monkeypatch.setenv("DACC_LAST_TIER", "0"); monkeypatch.setenv("DACC_VDEEP_TIER", "0")
+    wo, fo, bo = xc.oracle("Q", maxalign=1001)
+    E, fx, bx = _device_run("Q", k=14, maxalign=1001)
+    wx = E.debug_windows(); t = E.timing()
+    _report("Q -d 1001, no last and no very deep stage", t, len(wx))
+    assert windows_equal(wo, wx) == [] and frags_equal(fo, bo, fx, bx)
+    assert t.xdeep_windows == 37 and t.xdeep_out == 0
+    assert t.last_ms == 0.0 and t.vdeep_ms == 0.0
+    assert t.xdeep_ms > 0
+    E.close()
+
+
 def test_what_the_very_deep_stage_refused_at_1000_strings_finishes():
     wo, fo, bo = xc.oracle("X"); xc.check("X", wo)
     E, fx, bx = _device_run("X", k=14)
