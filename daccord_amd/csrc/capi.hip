@@ -414,6 +414,7 @@ struct dacc_ctx
 	uint32_t retry_grid, early_grid; int sched;
 	uint32_t tr_grid, tr_lds, tr_words, tr_lanes, trace_bytes, win_grid;
 	int env_sched, env_dbgretry;     // debugging knobs, read once in dacc_create
+	uint32_t env_feasneed;           // DACC_FEAS_NEED=0: stretch feasibility of every (stretch, direction, position) instead of what the enumerations can read (A/B runs, tests)
 	std::vector<uint32_t> retry_flags;                      // DACC_DEBUG_RETRY: (window, flags) of what the last LDS tier handed on
 	std::vector<dacc_fragment> frags; std::string bases;
 	std::vector<int32_t> pile_status; std::vector<std::string> pile_errors; std::string pile_errors_joined;
@@ -481,6 +482,7 @@ int dacc_create(dacc_ctx ** out, dacc_params const * p)
 		{ char const * td = getenv("DACC_TRACE_DYN"); c->env_trdyn = !(td && td[0] == '0'); }      // 0: k_trace walks its blocks with a fixed stride (rounds 1-5)
 		char const * ta = getenv("DACC_T7_ADAPT"); c->env_t7adapt = !(ta && ta[0] == '0');      // 0: tier 7 stays on whatever it hands on
 		char const * dr = getenv("DACC_DEBUG_RETRY"); c->env_dbgretry = (dr && dr[0] == '1');
+		{ char const * fn = getenv("DACC_FEAS_NEED"); c->env_feasneed = (fn && fn[0] == '0') ? 0u : 1u; }
 	}
 	if ( hipStreamCreate(&c->stream) != hipSuccess ) { delete c; return DACC_EHIP; }
 	{ int lo = 0, hi = 0; hipDeviceGetStreamPriorityRange(&lo,&hi); if ( hipStreamCreateWithPriority(&c->stream2,hipStreamNonBlocking,hi) != hipSuccess ) { delete c; return DACC_EHIP; } }
@@ -654,7 +656,7 @@ static int runDevice(dacc_ctx * c)
 					TP.slot1_long ? c->d_retry[0].p : static_cast<uint32_t *>(0),c->d_wout.p);
 			}
 			HIPCHK(hipEventRecord(c->evPrescan,s));
-			FastBatch FL; FL.W = WB; FL.W.arena = c->d_arena2.p; FL.W.prof = 0; FL.W.pregen = 0; FL.F = BP.stageCaps(ID_LONG); FL.dpsq_vst = c->d_vst.p; FL.retry = 0; FL.gearly = 0; FL.gslab = 0; FL.gstride = 0; FL.tab32 = c->d_tab32.p; FL.hand = 0; FL.handctr = 0; FL.handcap = 0; FL.handwords = 0;
+			FastBatch FL; FL.W = WB; FL.W.arena = c->d_arena2.p; FL.W.prof = 0; FL.W.pregen = 0; FL.F = BP.stageCaps(ID_LONG); FL.dpsq_vst = c->d_vst.p; FL.retry = 0; FL.gearly = 0; FL.gslab = 0; FL.gstride = 0; FL.tab32 = c->d_tab32.p; FL.hand = 0; FL.handctr = 0; FL.handcap = 0; FL.handwords = 0; FL.feasneed = c->env_feasneed;
 #if defined(DACC_LEDGER)
 			FL.ledger = 0;
 #endif
@@ -735,7 +737,7 @@ static int runDevice(dacc_ctx * c)
 					if ( (slot > 0 && TP.late_long) || TP.widetier ) FB.W.pregen = c->d_pregen2.p;
 					FB.gslab = c->d_gslab.p; FB.gstride = FB.F.gbytes; FB.tab32 = c->d_tab32.p;
 					// (a wide batch has handcap == 0, dacc_submit_piles: its hand-overs go to the generic engine, which sorts for itself)
-					FB.hand = c->handcap ? c->d_hand.p : static_cast<uint64_t *>(0); FB.handctr = c->d_handctr.p; FB.handcap = c->handcap; FB.handwords = TP.handwords;
+					FB.hand = c->handcap ? c->d_hand.p : static_cast<uint64_t *>(0); FB.handctr = c->d_handctr.p; FB.handcap = c->handcap; FB.handwords = TP.handwords; FB.feasneed = c->env_feasneed;
 #if defined(DACC_LEDGER)
 					{ char const * lm = getenv("DACC_LEDGER_MASK"); FB.ledger = lm ? static_cast<uint32_t>(strtoul(lm,0,0)) : 0u; }      // (scripts/ledger.py)
 #endif

@@ -702,6 +702,7 @@ struct FastBatch
 	// list in a slot of this buffer (handwords 64 bit words per slot: header {npre, nlast}, instances, last k-mers); the tier that picks
 	// the window up loads them instead of generating and sorting them again.  hand == 0: every hand-over restarts from the strings.
 	uint64_t * hand; uint32_t * handctr; uint32_t handcap, handwords;
+	uint32_t feasneed;          // 0: stretch feasibility of every (stretch, direction, position), as before the filter (DACC_FEAS_NEED=0: A/B runs and tests)
 #if defined(DACC_LEDGER)
 	uint32_t ledger;            // instruction ledger build (scripts/ledger.py): bit p set = phase p of every window runs twice
 #endif
@@ -773,8 +774,8 @@ static inline void feasit_dump()
 	g_feasit.clear();
 }
 static inline bool feasit_on() { static int on = -1; if ( on < 0 ) on = getenv("DACC_EMUL_FEAS") ? 1 : 0; return on == 1; }      // single threaded design aid only
-#define FEAS_ITERS(t,len,n) { if ( feasit_on() ) { g_feasit.it.push_back(n); g_feasit.ln.push_back(len); } }
-#define FEAS_DUMP() { if ( feasit_on() ) feasit_dump(); }
+#define FEAS_ITERS(t,len,n) { if ( feasit_on() && !feascount ) { g_feasit.it.push_back(n); g_feasit.ln.push_back(len); } }
+#define FEAS_DUMP() { if ( feasit_on() && !feascount ) feasit_dump(); }
 // test aid (DACC_EMUL_FEASCASES=<file>): per traversal of computeStretchFeasLanes one line of counters that say which situations of the unit
 // order, of the task rounds (as 64 lanes would run them, whatever the emulation's width) and of the node pipeline it went through
 // (tests/test_feas_pipeline.py asserts that its cases reach each of them).  One window at a time: the emulation of one context is sequential.
@@ -821,10 +822,57 @@ struct FeasCases
 	}
 };
 static FeasCases g_feascases;
-#define FEAS_UNITS(W,nu) { if ( lane == 0 ) g_feascases.units(W,nu); }
-#define FEAS_NODE(j,len,pp,nrows,f) g_feascases.node(j,len,pp,nrows,f);
-#define FEAS_FAIL(j,len) g_feascases.fail(j,len);
-#define FEAS_CASES_DUMP() { if ( lane == 0 ) g_feascases.dump(int(CT::maxs),nwF,nwR); }
+#define FEAS_UNITS(W,nu) { if ( lane == 0 && !feascount ) g_feascases.units(W,nu); }
+#define FEAS_NODE(j,len,pp,nrows,f) { if ( !feascount ) g_feascases.node(j,len,pp,nrows,f); }
+#define FEAS_FAIL(j,len) { if ( !feascount ) g_feascases.fail(j,len); }
+#define FEAS_CASES_DUMP() { if ( lane == 0 && !feascount ) g_feascases.dump(int(CT::maxs),nwF,nwR); }
+// audit aid (DACC_EMUL_FEASNEED=<file>): which (stretch, direction, position) triples the filter of computeStretchFeasLanes left out of a
+// traversal, and how often the enumerations asked for one of them -- sfFind / csfFind at a left-out position, linkOk on a left-out reverse
+// unit.  The filter is exact iff that never happens (tests/test_feas_need.py asserts zero).  The file holds one line of running totals,
+// rewritten at every traversal and when the process ends: traversals, units with tasks and tasks without the filter, the same with it,
+// weight records written (forward, reverse), probes of left-out forward positions, of left-out reverse positions, links on left-out
+// reverse units; then the situations the traversals went through: first and last k-mer candidates strictly inside a stretch, middle
+// pieces, traversals with (lmax+1)/2 <= k, passes of the distance relaxation.  One window at a time, like the other aids.
+struct FeasNeedAudit
+{
+	enum { SCAP = 65536 };
+	uint64_t outF[SCAP][2], outR[SCAP][2];      // left-out start positions of stretch s, forward and reverse (128 bits each)
+	uint64_t ntrav, units0, tasks0, units1, tasks1, recF, recR, probeF, probeR, linkR, insF, insL, mids, hlek, passes;
+	FILE * f; bool tried;
+	bool on() { if ( !tried ) { tried = true; char const * fn = getenv("DACC_EMUL_FEASNEED"); if ( fn ) f = fopen(fn,"w"); } return f != 0; }
+	static void range(uint64_t * m, uint32_t const lo, uint32_t const hi) { for ( uint32_t p = lo; p < hi && p < 128u; ++p ) m[p>>6] |= 1ull << (p&63u); }
+	// unit (s,rev): start positions [lo0,hi0) without the filter, [lo1,hi1) with it
+	void unit(uint32_t const s, bool const rev, uint32_t const lo0, uint32_t const hi0, uint32_t const lo1, uint32_t const hi1)
+	{
+		if ( !on() || s >= SCAP ) return;
+		uint64_t * const m = rev ? outR[s] : outF[s];
+		m[0] = m[1] = 0; range(m,lo0,hi0);
+		uint64_t k[2] = {0,0}; range(k,lo1,hi1); m[0] &= ~k[0]; m[1] &= ~k[1];
+		if ( hi0 > lo0 ) { ++units0; tasks0 += hi0-lo0; }
+		if ( hi1 > lo1 ) { ++units1; tasks1 += hi1-lo1; }
+	}
+	static bool out(uint64_t const * m, uint32_t const p) { return p < 128u && ((m[p>>6] >> (p&63u)) & 1ull); }
+	void probe(uint32_t const s, bool const rev, uint32_t const p) { if ( f && s < SCAP && out(rev ? outR[s] : outF[s],p) ) ++(rev ? probeR : probeF); }
+	void link(uint32_t const a, uint32_t const b) { if ( f && a < SCAP && b < SCAP && ((outR[a][0]|outR[a][1]) || (outR[b][0]|outR[b][1])) ) ++linkR; }
+	void dump()
+	{
+		if ( !f ) return;
+		rewind(f);
+		fprintf(f,"%llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu\n",(unsigned long long)ntrav,(unsigned long long)units0,(unsigned long long)tasks0,(unsigned long long)units1,(unsigned long long)tasks1,
+			(unsigned long long)recF,(unsigned long long)recR,(unsigned long long)probeF,(unsigned long long)probeR,(unsigned long long)linkR,
+			(unsigned long long)insF,(unsigned long long)insL,(unsigned long long)mids,(unsigned long long)hlek,(unsigned long long)passes);
+		fflush(f);
+	}
+	~FeasNeedAudit() { dump(); }
+};
+static FeasNeedAudit g_feasneed;
+#define FEAS_NEED_UNIT(s,rev,lo0,hi0,lo1,hi1) { if ( !feascount ) g_feasneed.unit(s,rev,lo0,hi0,lo1,hi1); }
+#define FEAS_NEED_PROBE(s,rev,p) g_feasneed.probe(s,rev,p);
+#define FEAS_NEED_LINK(a,b) g_feasneed.link(a,b);
+#define FEAS_OVER() { if ( !feascount ) over(128); }
+#define FEAS_NEED_PASS() { if ( lane == 0 ) ++g_feasneed.passes; }
+#define FEAS_NEED_DUMP() { if ( lane == 0 && !feascount && g_feasneed.on() ) { FeasNeedAudit & A_ = g_feasneed; ++A_.ntrav; A_.recF += nwF; A_.recR += nwR; A_.mids += nmid; A_.hlek += (H <= static_cast<int64_t>(k)); \
+	for ( uint32_t c_ = 0; c_ < nF; ++c_ ) A_.insF += (L.fnode()[c_] != 0xFFFF && L.parF()[c_] != SNONE); for ( uint32_t c_ = 0; c_ < nL; ++c_ ) A_.insL += (L.lnode()[c_] != 0xFFFF && L.parL()[c_] != SNONE); A_.dump(); } }
 #else
 #define FEAS_ITERS(t,len,n)
 #define FEAS_DUMP()
@@ -832,6 +880,12 @@ static FeasCases g_feascases;
 #define FEAS_NODE(j,len,pp,nrows,f)
 #define FEAS_FAIL(j,len)
 #define FEAS_CASES_DUMP()
+#define FEAS_NEED_UNIT(s,rev,lo0,hi0,lo1,hi1)
+#define FEAS_NEED_PROBE(s,rev,p)
+#define FEAS_NEED_LINK(a,b)
+#define FEAS_NEED_DUMP()
+#define FEAS_NEED_PASS()
+#define FEAS_OVER() over(128);
 #define FSTAT_MX(i,x)
 #define FSTAT_ADD(i,x)
 #endif
@@ -858,7 +912,17 @@ struct FastEngine
 	uint32_t npre, nlast, nn, nmfirst, nmlast;
 	uint32_t n0, npool, nlinks, nwF, nwR;
 	uint32_t nF, nL;
+	uint32_t feasneed;           // FastBatch::feasneed
 
+#if defined(DACC_EMUL)
+	// emulation only: the filter's switch is read from the environment at every traversal (a test runs both settings in one process); feascount marks
+	// the count-only pass of computeStretchFeasLanes that gives the traversal trace (DACC_EMUL_TRAV) its unfiltered numbers of weight records
+	bool feascount, feasapplied; uint32_t nwFall, nwRall;
+	DEV bool feasNeedOn() const { char const * e = getenv("DACC_FEAS_NEED"); return !(e && e[0] == '0'); }
+#else
+	static constexpr bool feascount = false;
+	DEV bool feasNeedOn() const { return feasneed != 0; }
+#endif
 #if defined(DACC_EMUL)
 	// emulation only: DACC_EMUL_OVER=1 reports where a tier overflowed
 	DEV void over_(uint32_t b, int line) { flags |= b; static char const * ov = getenv("DACC_EMUL_OVER"); if ( ov ) fprintf(stderr,"[over] tier maxs=%d line %d bits 0x%x nn=%u n0=%u npool=%u nF=%u nL=%u nwF=%u nwR=%u rstop=%u\n",int(CT::maxs)*10000+int(CT::ncap),line,b,nn,n0,npool,nF,nL,nwF,nwR,rstop); }
@@ -1767,6 +1831,56 @@ struct FastEngine
 		return res;
 	}
 
+	// Shortest distances, in k-mer steps, from the first k-mer candidates to every node (dF) and from every node to the last k-mer
+	// candidates (dR), over the base stretches; FEASINF = none (or 255 steps and more: no path, position or start position gets there).
+	// A forward path that enters a stretch at position p has walked p steps from a first candidate, so p >= dF of the stretch's
+	// first node; a reverse path that enters one at p has walked p steps back from a last candidate, p >= dR of its last node.
+	// The enumerations extend a path only in the first half of the window (forwardEnumerateLane, reverseEnumerateLane: (lmax+1)/2),
+	// which bounds the positions they can ask computeStretchFeasLanes' records for.  Pieces are parts of base stretches: a walk over
+	// them is a walk over their parents.  A candidate strictly inside a stretch leads to that stretch's end (forward) / start (reverse).
+	// Same scratch as pairReachable, whose tables are dead; the two byte tables live until the unit set-up of computeStretchFeasLanes
+	// has read them (nothing between the two writes there: loadTab's copy lies elsewhere).  Lost updates of lanes that relax the same
+	// node in one step are made up for in the next: the loop ends when a whole pass changes nothing, at the one fixed point there is.
+	enum : uint32_t { FEASINF = 255u };
+	DEV void feasDistances()
+	{
+		LDSQ uint8_t * const dF = L.xreach();
+		LDSQ uint8_t * const dR = dF + CT::ncap;
+		for ( uint32_t z = lane; z < nn; z += WSZ ) { dF[z] = FEASINF; dR[z] = FEASINF; }
+		wv_sync();
+		for ( uint32_t c = lane; c < nF; c += WSZ ) { uint32_t const z = L.fnode()[c]; if ( z != 0xFFFF ) dF[z] = 0; }
+		for ( uint32_t c = lane; c < nL; c += WSZ ) { uint32_t const z = L.lnode()[c]; if ( z != 0xFFFF ) dR[z] = 0; }
+		wv_sync();
+		while ( true )
+		{
+			uint32_t changed = 0;
+			for ( uint32_t c = lane; c < nF; c += WSZ )
+			{
+				uint32_t const par = L.parF()[c];
+				if ( L.fnode()[c] == 0xFFFF || par == SNONE ) continue;
+				uint32_t const l = L.slast()[par], d = L.sslen()[par]-1u-L.posF()[c];
+				if ( d < dF[l] ) { dF[l] = d; changed = 1; }
+			}
+			for ( uint32_t c = lane; c < nL; c += WSZ )
+			{
+				uint32_t const par = L.parL()[c];
+				if ( L.lnode()[c] == 0xFFFF || par == SNONE ) continue;
+				uint32_t const f = L.sfirst()[par], d = L.posL()[c];
+				if ( d < dR[f] ) { dR[f] = d; changed = 1; }
+			}
+			for ( uint32_t s = lane; s < n0; s += WSZ )
+			{
+				uint32_t const f = L.sfirst()[s], l = L.slast()[s], step = L.sslen()[s]-1u;
+				uint32_t const a = dF[f] + step, b = dR[l] + step;      // (>= FEASINF: never below a table entry)
+				if ( a < dF[l] ) { dF[l] = a; changed = 1; }
+				if ( b < dR[f] ) { dR[f] = b; changed = 1; }
+			}
+			wv_sync();
+			FEAS_NEED_PASS()
+			if ( !wv_any(changed) ) break;
+		}
+	}
+
 	// copy of the model table in LDS, row stride nrows+1: the extra row is zero so that positions beyond the table can be
 	// clamped instead of branched on; one more all-zero position (nsup) for read positions behind the support
 	DEV void loadTab()
@@ -1802,11 +1916,26 @@ struct FastEngine
 		if constexpr ( GW ) return L.urec();
 		else { static_assert(2*CT::scap < 512,"unit ids are packed into 9 bits of a 16 bit record"); return reinterpret_cast<LDSQ uint16_t *>(L.ulo()); }
 	}
-	DEV void computeStretchFeasLanes(uint32_t const sfrom, uint32_t const sto)
+	// (need: only what the enumerations of this traversal can ask for -- feasDistances() has run.  A forward unit of a base stretch starts at
+	// position dF of its first node at the earliest and, like every forward unit, below H = (lmax+1)/2, the bound of the paths that are extended
+	// (the roots' extensions ask for position 0 whatever H is); a reverse unit of a base stretch is read when a path of base length dR + k < H
+	// reaches its last node, or as a root's extension (dR = 0), and then at ALL of its positions: linkOk takes the maximum over every
+	// common position of two masks, so reverse units are kept or dropped whole.  A unit that is not needed gets width 0 and leaves the
+	// order like a unit without a task; its mask stays empty.
+	// Which tier finishes a window must not depend on the filter: a traversal is handed on when its weight records overflow the tier (wcap, the
+	// task offsets), and that is decided by the records of ALL triples.  They are at most as many as the tasks: the set-up computes both widths
+	// of every unit, and where the unfiltered tasks of a direction exceed wcap (or all of them the task offsets) the traversal runs without the
+	// filter and overflows, or not, as it always did; below that bound neither form can overflow.)
+	DEV void computeStretchFeasLanes(uint32_t const sfrom, uint32_t const sto, int64_t const lmax, bool const need)
 	{
 		PROFX_T0
 		uint32_t const ns = sto-sfrom, nu = 2*ns;          // units: forward stretches, then reverse stretches
 		uint32_t const stride = nrows+1;
+		// (two uniform bounds, dF < max(H,1) and dR < max(H-k,1), compared in 32 bits cost the shallow tiers four more registers than this form)
+		int64_t const H = (lmax+1)/2;
+		int32_t const hcap = H < 1 ? 1 : (H < static_cast<int64_t>(nrows) ? static_cast<int32_t>(H) : static_cast<int32_t>(nrows));      // forward start positions: below max(H,1)
+		LDSQ uint8_t const * const dF = L.xreach();
+		LDSQ uint8_t const * const dR = dF + CT::ncap;
 		// The tasks of a round run in lock step for as long as the longest of them walks its stretch, so the units are
 		// processed in classes of decreasing stretch length (lock step iterations per traversal at config 2: 248 in pool
 		// order, 97 sorted by length, about 105 in these classes; 65 is the sum of the iterations over 64).  Any order of
@@ -1821,6 +1950,7 @@ struct FastEngine
 		// (legacy layout: 16 bit records over the bytes of ulo / uhi, at most 511 units; gw layout: 32 bit records)
 		auto const urec = unitRecords();
 		uint32_t ulo_r[NCHU], uw_r[NCHU], ucls_r[NCHU], upos_r[NCHU];
+		uint32_t allF = 0, allR = 0;          // this lane's tasks without the filter, by direction
 		#pragma unroll
 		for ( uint32_t cc = 0; cc < NCHU; ++cc )
 		{
@@ -1840,10 +1970,28 @@ struct FastEngine
 					lo = a > lo ? a : lo; hi = b < hi ? b : hi;
 				}
 				if ( hi < lo ) hi = lo;
-				w = static_cast<uint32_t>(hi-lo); lo_ = static_cast<uint32_t>(lo);
+				if ( need )
+				{
+					// (both forms of the unit in its two registers, the unfiltered one in bits 8 ...: widths and start positions are at most 128)
+					w = static_cast<uint32_t>(hi-lo) << 8; lo_ = static_cast<uint32_t>(lo) << 8;
+					if ( rev ) allR += static_cast<uint32_t>(hi-lo); else allF += static_cast<uint32_t>(hi-lo);
+					if ( !rev ) hi = hi < hcap ? hi : hcap;
+					if ( s < n0 )
+					{
+						int32_t const d = rev ? dR[L.slast()[s]] : dF[L.sfirst()[s]];
+						bool const wanted = rev ? (d == 0 || static_cast<int64_t>(d) + static_cast<int64_t>(k) < H) : true;      // (forward: hi <= hcap decides)
+						if ( !rev ) lo = d > lo ? d : lo;
+						if ( d == static_cast<int32_t>(FEASINF) || !wanted ) hi = 0;
+					}
+					if ( hi <= lo ) { lo = 0; hi = 0; }
+				}
+				w |= static_cast<uint32_t>(hi-lo); lo_ |= static_cast<uint32_t>(lo);
 				cls = len >= 49 ? 0u : len >= 33 ? 1u : len >= 25 ? 2u : len >= 17 ? 3u : len >= 13 ? 4u : len >= 9 ? 5u : len >= 7 ? 6u : len >= 5 ? 7u : len == 4 ? 8u : len == 3 ? 9u : len == 2 ? 10u : 11u;
+				if ( !feascount )
+				{
 				if ( rev ) { L.maskR()[s] = 0; L.woffR()[s] = 0; } else { L.maskF()[s] = 0; L.woffF()[s] = 0; }
 				if constexpr ( CT::wide != 0 ) { if ( rev ) L.maskRh()[s] = 0; else L.maskFh()[s] = 0; }
+				}
 			}
 			ulo_r[cc] = lo_; uw_r[cc] = w; ucls_r[cc] = cls; upos_r[cc] = 0;
 		}
@@ -1862,11 +2010,23 @@ struct FastEngine
 				}
 			}
 		}
+		// the filter stands where no direction's unfiltered tasks, hence records, can overflow the tier
+		bool filt = false;
+		if ( need ) { uint32_t const tF = wv_sum(allF), tR = wv_sum(allR); filt = tF <= CT::wcap && tR <= CT::wcap && static_cast<uint64_t>(tF) + tR <= TOFFMAX; }
+	#if defined(DACC_EMUL)
+		if ( !feascount ) feasapplied = filt;
+	#endif
 		#pragma unroll
 		for ( uint32_t cc = 0; cc < NCHU; ++cc )
 		{
 			uint32_t const u = cc*WSZ + lane;
-			if ( u < nu ) { urec[upos_r[cc]] = ulo_r[cc] | (u << 7); L.toff()[upos_r[cc]] = static_cast<toff_t>(uw_r[cc]); }
+			if ( u < nu )
+			{
+				uint32_t const usel = (need && !filt) ? 8u : 0u, umask = need ? 0xFFu : ~0u;
+				uint32_t const wsel = (uw_r[cc] >> usel) & umask, lsel = (ulo_r[cc] >> usel) & umask;
+				FEAS_NEED_UNIT(sfrom + (u >= ns ? u-ns : u),u >= ns,need ? (ulo_r[cc] >> 8) : lsel,need ? (ulo_r[cc] >> 8) + (uw_r[cc] >> 8) : lsel+wsel,lsel,lsel+wsel)
+				urec[upos_r[cc]] = lsel | (u << 7); L.toff()[upos_r[cc]] = static_cast<toff_t>(wsel);
+			}
 		}
 		wv_sync();
 		FEAS_UNITS(L.toff(),nu)
@@ -1886,7 +2046,7 @@ struct FastEngine
 			tbase += tot; ncu += ntot;
 		}
 		PROFX(18)
-		if ( tbase > TOFFMAX ) { over(128); return; }
+		if ( tbase > TOFFMAX ) { FEAS_OVER() return; }
 		if ( lane == 0 ) L.toff()[ncu] = static_cast<toff_t>(tbase);
 		wv_sync();
 		uint32_t const ntask = tbase;
@@ -1965,7 +2125,7 @@ struct FastEngine
 			uint64_t const revb = wv_ballot(act && rev);
 			uint64_t const mydir = rev ? revb : ~revb;
 			uint32_t const base = rev ? nwR : nwF;
-			if ( ok )
+			if ( ok && !feascount )
 			{
 				uint32_t const o = base + dacc_popc64(okb & mydir & ltmask);
 				if ( o < CT::wcap )
@@ -1973,7 +2133,7 @@ struct FastEngine
 					if ( rev ) putR(o,sum,f1); else putF(o,sum,f1,fl);
 				}
 			}
-			if ( act )
+			if ( act && !feascount )
 			{
 				// the first lane of a stretch in this round adds the round's bits to its mask; the lane with the stretch's first
 				// task sets the offset of its list
@@ -1999,11 +2159,12 @@ struct FastEngine
 				}
 			}
 			nwF += dacc_popc64(okb & ~revb); nwR += dacc_popc64(okb & revb);
-			if ( nwF > CT::wcap || nwR > CT::wcap ) { over(128); FEAS_DUMP() return; }
+			if ( nwF > CT::wcap || nwR > CT::wcap ) { FEAS_OVER() FEAS_DUMP() return; }
 		}
 		FEAS_DUMP()
 		wv_sync();
 		FEAS_CASES_DUMP()
+		FEAS_NEED_DUMP()
 	}
 	// weights of feasible (stretch, position) entry i.  A node weight is a sum of at most fqmax table words of < 2^32: 255 of them stay below 2^40
 	// (8 bit high part), 1023 below 2^42 (10 bits, the tier of more than 256 strings); a feasible stretch has at most nrows <= 64 nodes: < 2^46 / 2^48
@@ -2116,6 +2277,7 @@ struct FastEngine
 	}
 	DEV int32_t sfFind(uint32_t const s, uint32_t const p) const
 	{
+		FEAS_NEED_PROBE(s,false,p)
 		if constexpr ( CT::wide != 0 )
 		{
 			if ( p >= 128 ) return -1;
@@ -2130,6 +2292,7 @@ struct FastEngine
 	}
 	DEV int32_t csfFind(uint32_t const s, uint32_t const p) const
 	{
+		FEAS_NEED_PROBE(s,true,p)
 		if constexpr ( CT::wide != 0 )
 		{
 			if ( p >= 128 ) return -1;
@@ -2145,6 +2308,7 @@ struct FastEngine
 	// getReverseStretchLinkWeight(A=i,B=b) >= 0.1 (computeStretchLinks :3388-3480), evaluated on demand
 	DEV bool linkOk(uint32_t const i, uint32_t const b) const
 	{
+		FEAS_NEED_LINK(i,b)
 		uint32_t const shift = L.sslen()[b]-1;
 		if constexpr ( CT::wide != 0 )
 		{
@@ -3760,8 +3924,21 @@ struct FastEngine
 		PROF(*this,16)
 		loadTab();
 		PROF(*this,17)
-		LEDGER_REP(8) { nwF = 0; nwR = 0; computeStretchFeasLanes(0,npool); }
+		// (the distances are part of the phase: its second run in a ledger build finds their bytes overwritten)
+		LEDGER_REP(8) { nwF = 0; nwR = 0; bool const need = feasNeedOn(); if ( need ) feasDistances(); computeStretchFeasLanes(0,npool,lmax,need); }
 		flags = wv_or(flags); if ( flags ) return false;
+#if defined(DACC_EMUL)
+		// the traversal trace (DACC_EMUL_TRAV) describes the unfiltered computation, as it did before there was a filter: where the filtered
+		// pass stood, its numbers of weight records come from a second pass that only counts (its task lists are scratch the first pass is
+		// done with; it writes no mask, offset or record and cannot overflow: the bound of the set-up held)
+		nwFall = nwF; nwRall = nwR;
+		if ( ftrav_file() && feasapplied )
+		{
+			uint32_t const kF = nwF, kR = nwR;
+			feascount = true; nwF = 0; nwR = 0; computeStretchFeasLanes(0,npool,lmax,false); feascount = false;
+			nwFall = nwF; nwRall = nwR; nwF = kF; nwR = kR;
+		}
+#endif
 		{ SITE_T0 bool const sf0_ = sfresh, sd0_ = sdirty; LEDGER_REP(9) { sfresh = sf0_; sdirty = sd0_; spillS(); } SITE(24) }      // traverse: build-phase arrays to the slab
 		PROF(*this,9)
 
@@ -4087,7 +4264,7 @@ struct FastEngine
 		FSTAT_MX(0,mao); FSTAT_MX(1,npre); FSTAT_MX(2,nn); FSTAT_MX(3,n0); FSTAT_MX(4,npool); FSTAT_MX(5,nlinks); FSTAT_MX(6,nwF); FSTAT_MX(7,nwR);
 		FSTAT_MX(8,rstop); FSTAT_MX(9,nF); FSTAT_MX(10,nL); FSTAT_ADD(11,1); FSTAT_MX(12,nc); FSTAT_ADD(24,nc ? 0u : 1u);
 #if defined(DACC_EMUL)
-		if ( lane == 0 ) { FILE * f = ftrav_file(); if ( f ) { uint32_t nlv = 0; for ( uint32_t i = 0; i < nL; ++i ) nlv += L.lnode()[i] != 0xFFFF; fprintf(f,"%d %u %u %u %u %u %u %u %u %u %u %u %u\n",int(CT::maxs),mao,npre,nn,n0,npool,nF,nL,nlv,rstop,nwF,nwR,nc); fflush(f); } }
+		if ( lane == 0 ) { FILE * f = ftrav_file(); if ( f ) { uint32_t nlv = 0; for ( uint32_t i = 0; i < nL; ++i ) nlv += L.lnode()[i] != 0xFFFF; fprintf(f,"%d %u %u %u %u %u %u %u %u %u %u %u %u\n",int(CT::maxs),mao,npre,nn,n0,npool,nF,nL,nlv,rstop,nwFall,nwRall,nc); fflush(f); } }
 #endif
 		return nc != 0;
 	}
@@ -4339,7 +4516,10 @@ DEV int processWindowFast(FastBatch const & FB, uint64_t const widx, LDSQ uint8_
 		// (one-slab tier: the weights, the spill image and the instance image follow the layout in the buffer the caller passed as `lds`)
 		if constexpr ( FastOneSlab<CT>::value != 0 ) E.gslab = (uint8_t *)(lds) + FastLds<CT>::g_base;
 	}
-	E.lane = wv_lane(); E.flags = 0; E.prof = B.prof;
+	E.lane = wv_lane(); E.flags = 0; E.prof = B.prof; E.feasneed = FB.feasneed;
+#if defined(DACC_EMUL)
+	E.feascount = false; E.feasapplied = false; E.nwFall = E.nwRall = 0;
+#endif
 #if defined(DACC_LEDGER)
 	E.ledger = FB.ledger;
 #endif
