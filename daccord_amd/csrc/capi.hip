@@ -1,6 +1,6 @@
 /*
  * libdaccord_hip.so: C ABI (include/daccord_hip.h) + gfx950 kernels.
- * Host side: device buffers, batch planning, launches on one HIP stream, HIP-event timing.
+ * Host side: the context and what it owns on the device (context.hpp), batch planning, the device pass as a sequence of phases (runDevice), HIP-event timing.
  * There is no CPU fallback anywhere in this file: no device => DACC_ENODEV.
  */
 #include <hip/hip_runtime.h>
@@ -17,6 +17,7 @@
 #include "trace_kernel.hpp"
 #include "vote_kernel.hpp"
 #include "emit_record.hpp"
+#include "context.hpp"
 
 using namespace dacc;
 
@@ -340,88 +341,6 @@ __global__ void __launch_bounds__(256) k_vote(VoteBatch B)
 
 // ---------------------------------------------------------------- host
 
-namespace {
-
-template<typename T>
-struct DevBuf
-{
-	T * p; size_t cap;
-	DevBuf() : p(0), cap(0) {}
-	hipError_t ensure(size_t n)
-	{
-		if ( n <= cap ) return hipSuccess;
-		if ( p ) { hipFree(p); p = 0; cap = 0; }
-		hipError_t const e = hipMalloc(reinterpret_cast<void **>(&p),n*sizeof(T));
-		if ( e == hipSuccess ) cap = n;
-		return e;
-	}
-	void release() { if ( p ) hipFree(p); p = 0; cap = 0; }
-};
-
-// pinned host buffer (the symbol stream of a batch comes back at PCIe speed instead of through a pageable staging copy)
-template<typename T>
-struct HostBuf
-{
-	T * p; size_t cap; bool pinned;
-	HostBuf() : p(0), cap(0), pinned(false) {}
-	// pinned memory (the device-to-host copy of the symbol stream runs at link speed into it); where the process may not lock
-	// that much memory (memlock limit) a pageable buffer does the same job through the runtime's staging copy
-	hipError_t ensure(size_t n)
-	{
-		if ( n <= cap ) return hipSuccess;
-		release();
-		hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&p),n*sizeof(T),hipHostMallocDefault);
-		if ( e == hipSuccess ) { cap = n; pinned = true; return e; }
-		(void)hipGetLastError();
-		p = static_cast<T *>(std::malloc(n*sizeof(T)));
-		if ( !p ) return hipErrorOutOfMemory;
-		cap = n; pinned = false;
-		return hipSuccess;
-	}
-	void release() { if ( p ) { if ( pinned ) hipHostFree(p); else std::free(p); } p = 0; cap = 0; pinned = false; }
-};
-
-}
-
-struct dacc_ctx
-{
-	dacc_params par;
-	int device;
-	hipStream_t stream; hipStream_t stream2; hipEvent_t evFirstTier, evEarlyGeneric, evPrescan;   // stream2: generic engine for the windows no LDS tier can run, concurrent with tiers 2 and 3
-	hipEvent_t ev[6]; hipEvent_t evEmit[2]; hipEvent_t evslot[TIER_NSLOTS];      // evslot[t]: slot t of the tier chain is done
-	std::string err;
-	bool haveprofile, havedb, havebatch;
-	double est_cor;
-	HostTables H;
-	DevTables T; DevParams P;
-	DevBuf<double> d_dpnorm, d_dpsq; DevBuf<uint64_t> d_vs; DevBuf<uint16_t> d_first, d_size, d_suplo, d_suphi; DevBuf<uint32_t> d_klim;
-	DevBuf<uint8_t> d_bps; DevBuf<uint64_t> d_boff; DevBuf<uint32_t> d_rlen;
-	std::vector<uint32_t> h_rlen;
-	BatchPlan BP;
-	DevBuf<DevPile> d_piles; DevBuf<DevOvl> d_ovl; DevBuf<uint32_t> d_ovl_pile; DevBuf<uint8_t> d_trace;
-	DevBuf<uint32_t> d_blk_ovl, d_blk_b0, d_wt_b, d_wt_e;
-	DevBuf<uint8_t> d_wrec; DevBuf<WindowOut> d_wout; DevBuf<uint8_t> d_arena;
-	DevBuf<uint8_t> d_has, d_oc, d_outsym, d_pilebad; DevBuf<uint16_t> d_ld0; DevBuf<uint32_t> d_ocs, d_nfrag, d_err;
-	DevBuf<VoteFragment> d_frags; DevBuf<uint64_t> d_fragbase; DevBuf<uint64_t> d_prof;
-	DevBuf<uint64_t> d_vst; DevBuf<uint32_t> d_tab32; DevBuf<uint8_t> d_gslab, d_longslab /* the long string stage's (wide batches, second stream), allocated by the first pass whose second stream has a window */; DevBuf<uint32_t> d_longhand[2]; /* what that stage hands on to k_window_long, one list per list of the second stream */ DevBuf<uint32_t> d_retry[TIER_NSLOTS], d_work, d_gearly, d_pregen, d_pregen2, d_pregenlist; DevBuf<uint8_t> d_arena2; DevBuf<uint64_t> d_trslab; DevBuf<uint32_t> d_small; DevBuf<uint64_t> d_hand; DevBuf<uint32_t> d_handctr; uint32_t handcap; uint64_t handwant, nruns; bool nohand, oom; bool tier7_adapt_off; int env_t7adapt; int env_trdyn;
-	// the LDS tiers (tier_pipeline.hpp): their switches, the resolved chain of the current batch (capacities: BP.stageCaps), by TierId and the launch state of its stages.
-	// A main tier hands on through d_retry[slot] and is done at evslot[slot]; `handon` and `done` are those of the front tiers and of the trailing stages.
-	// `slab`: a trailing stage's own slab (layout included; the kernels' grids differ), allocated by the first batch the stage is resolved for.
-	TierSwitches sw; TierPipeline TP;
-	struct Stage { bool ran; uint32_t grid; DevBuf<uint32_t> handon; DevBuf<uint8_t> slab; hipEvent_t done; uint32_t const * in; /* the list it read in the last pass */ } st[TIER_NSTAGES];
-	uint32_t nlong[2];      // windows on the two lists of the second stream in the current pass (pre-scan, first tier's generic-only windows)
-	bool longran[2]; hipEvent_t evLong[4];      // the long string stage (tier 17): did it run over list i in the current pass, and the events around its two launches on the second stream
-	uint32_t retry_grid, early_grid; int sched;
-	uint32_t tr_grid, tr_lds, tr_words, tr_lanes, trace_bytes, win_grid;
-	int env_sched, env_dbgretry;     // debugging knobs, read once in dacc_create
-	uint32_t env_feasneed;           // DACC_FEAS_NEED=0: stretch feasibility of every (stretch, direction, position) instead of what the enumerations can read (A/B runs, tests)
-	std::vector<uint32_t> retry_flags;                      // DACC_DEBUG_RETRY: (window, flags) of what the last LDS tier handed on
-	std::vector<dacc_fragment> frags; std::string bases;
-	std::vector<int32_t> pile_status; std::vector<std::string> pile_errors; std::string pile_errors_joined;
-	std::vector<uint32_t> h_nfrag; std::vector<VoteFragment> h_frags; HostBuf<uint8_t> h_outsym;
-	dacc_timing timing;
-};
-
 #define HIPCHK(call) do { hipError_t const e_ = (call); if ( e_ != hipSuccess ) { c->err = std::string(#call) + ": " + hipGetErrorString(e_); if ( e_ == hipErrorOutOfMemory ) c->oom = true; return DACC_EHIP; } } while (0)
 
 template<typename T>
@@ -470,28 +389,23 @@ int dacc_create(dacc_ctx ** out, dacc_params const * p)
 	if ( hipSetDevice(p->device) != hipSuccess ) return DACC_ENODEV;
 	dacc_ctx * c = new (std::nothrow) dacc_ctx;
 	if ( !c ) return DACC_ENOMEM;
-	c->par = *p; c->device = p->device; c->haveprofile = c->havedb = c->havebatch = false; c->est_cor = 0; c->nlong[0] = c->nlong[1] = 0; c->longran[0] = c->longran[1] = false; c->handcap = 0; c->handwant = 0; c->nruns = 0; c->nohand = false; c->oom = false;
-	std::memset(&c->timing,0,sizeof(c->timing));
-	// launch geometry of the LDS tiers: set by every batch that uses them; a generic-only batch (DACC_NOFAST, w >= 64, a model table no
-	// tier holds) reads retry_grid in its scratch retry and must not find an indeterminate value there
-	c->retry_grid = c->early_grid = c->win_grid = 0; c->tier7_adapt_off = false; c->sched = 0;
-	c->tr_grid = c->tr_lds = c->tr_words = c->tr_lanes = c->trace_bytes = 0;
-	{
-		c->sw = readTierSwitches();      // DACC_NOFAST, DACC_TIERS, DACC_WIDE_TIER, DACC_DENSE_TIER, DACC_DEEP_TIER, the trailing stages' DACC_*_TIER and DACC_*_AS_SLOT2, DACC_LONGSTR_TIER, DACC_LONG128, DACC_HAND, DACC_T0INST, DACC_T7INST, DACC_LDS_T1, DACC_LDS_T0
-		char const * sc = getenv("DACC_SCHED"); c->env_sched = sc ? atoi(sc) : 1;      // bit 0: LDS tiers pull work from a counter, bit 1: generic engine too
-		{ char const * td = getenv("DACC_TRACE_DYN"); c->env_trdyn = !(td && td[0] == '0'); }      // 0: k_trace walks its blocks with a fixed stride (rounds 1-5)
-		char const * ta = getenv("DACC_T7_ADAPT"); c->env_t7adapt = !(ta && ta[0] == '0');      // 0: tier 7 stays on whatever it hands on
-		char const * dr = getenv("DACC_DEBUG_RETRY"); c->env_dbgretry = (dr && dr[0] == '1');
-		{ char const * fn = getenv("DACC_FEAS_NEED"); c->env_feasneed = (fn && fn[0] == '0') ? 0u : 1u; }
-	}
-	if ( hipStreamCreate(&c->stream) != hipSuccess ) { delete c; return DACC_EHIP; }
-	{ int lo = 0, hi = 0; hipDeviceGetStreamPriorityRange(&lo,&hi); if ( hipStreamCreateWithPriority(&c->stream2,hipStreamNonBlocking,hi) != hipSuccess ) { delete c; return DACC_EHIP; } }
-	hipEventCreateWithFlags(&c->evFirstTier,hipEventDisableTiming); hipEventCreateWithFlags(&c->evEarlyGeneric,hipEventDisableTiming); hipEventCreateWithFlags(&c->evPrescan,hipEventDisableTiming);
-	for ( int i = 0; i < 6; ++i ) hipEventCreate(&c->ev[i]);
-	for ( int i = 0; i < 2; ++i ) hipEventCreate(&c->evEmit[i]);
-	for ( int i = 0; i < 4; ++i ) hipEventCreate(&c->evLong[i]);
-	for ( int i = 0; i < TIER_NSLOTS; ++i ) hipEventCreate(&c->evslot[i]);
-	for ( int i = 0; i < TIER_NSTAGES; ++i ) { hipEventCreate(&c->st[i].done); c->st[i].ran = false; c->st[i].grid = 0; c->st[i].in = 0; }
+	c->par = *p; c->device = p->device;
+	c->sw = readTierSwitches();      // DACC_NOFAST, DACC_TIERS, DACC_WIDE_TIER, DACC_DENSE_TIER, DACC_DEEP_TIER, the trailing stages' DACC_*_TIER and DACC_*_AS_SLOT2, DACC_LONGSTR_TIER, DACC_LONG128, DACC_HAND, DACC_T0INST, DACC_T7INST, DACC_LDS_T1, DACC_LDS_T0
+	char const * sc = getenv("DACC_SCHED"); c->env_sched = sc ? atoi(sc) : 1;      // bit 0: LDS tiers pull work from a counter, bit 1: generic engine too
+	{ char const * td = getenv("DACC_TRACE_DYN"); c->env_trdyn = !(td && td[0] == '0'); }      // 0: k_trace walks its blocks with a fixed stride
+	char const * ta = getenv("DACC_T7_ADAPT"); c->env_t7adapt = !(ta && ta[0] == '0');      // 0: tier 7 stays on whatever it hands on
+	char const * dr = getenv("DACC_DEBUG_RETRY"); c->env_dbgretry = (dr && dr[0] == '1');
+	{ char const * fn = getenv("DACC_FEAS_NEED"); c->env_feasneed = (fn && fn[0] == '0') ? 0u : 1u; }
+	// (a failure from here on: `delete c` destroys what has been created)
+	if ( hipStreamCreate(&c->stream.h) != hipSuccess ) { delete c; return DACC_EHIP; }
+	{ int lo = 0, hi = 0; hipDeviceGetStreamPriorityRange(&lo,&hi); if ( hipStreamCreateWithPriority(&c->stream2.h,hipStreamNonBlocking,hi) != hipSuccess ) { delete c; return DACC_EHIP; } }
+	hipEventCreateWithFlags(&c->evFirstTier.h,hipEventDisableTiming); hipEventCreateWithFlags(&c->evEarlyGeneric.h,hipEventDisableTiming); hipEventCreateWithFlags(&c->evPrescan.h,hipEventDisableTiming);
+	for ( Event & e : c->ev ) hipEventCreate(&e.h);
+	for ( Event & e : c->evEmit ) hipEventCreate(&e.h);
+	for ( Event & e : c->evLong ) hipEventCreate(&e.h);
+	for ( Event & e : c->evslot ) hipEventCreate(&e.h);
+	for ( dacc_ctx::Stage & S : c->st ) hipEventCreate(&S.done.h);
+	hipEventCreate(&c->h2dend.h);
 	*out = c;
 	return DACC_OK;
 }
@@ -501,16 +415,6 @@ void dacc_destroy(dacc_ctx * c)
 	if ( !c ) return;
 	hipSetDevice(c->device);
 	hipStreamSynchronize(c->stream); hipStreamSynchronize(c->stream2);
-	c->d_dpnorm.release(); c->d_dpsq.release(); c->d_vs.release(); c->d_first.release(); c->d_size.release(); c->d_suplo.release(); c->d_suphi.release(); c->d_klim.release();
-	c->d_bps.release(); c->d_boff.release(); c->d_rlen.release();
-	c->d_piles.release(); c->d_ovl.release(); c->d_ovl_pile.release(); c->d_trace.release(); c->d_blk_ovl.release(); c->d_blk_b0.release(); c->d_wt_b.release(); c->d_wt_e.release();
-	c->d_wrec.release(); c->d_wout.release(); c->d_arena.release();
-	c->h_outsym.release(); c->d_pilebad.release(); c->d_has.release(); c->d_oc.release(); c->d_outsym.release(); c->d_ld0.release(); c->d_ocs.release(); c->d_nfrag.release(); c->d_err.release(); c->d_frags.release(); c->d_fragbase.release(); c->d_prof.release(); c->d_vst.release(); c->d_tab32.release(); c->d_gslab.release(); c->d_longslab.release(); c->d_longhand[0].release(); c->d_longhand[1].release(); for ( int i = 0; i < 3; ++i ) c->d_retry[i].release(); c->d_work.release(); c->d_gearly.release(); c->d_pregen.release(); c->d_pregen2.release(); c->d_pregenlist.release(); c->d_arena2.release(); c->d_trslab.release(); c->d_hand.release(); c->d_handctr.release();
-	for ( int i = 0; i < 6; ++i ) hipEventDestroy(c->ev[i]);
-	for ( int i = 0; i < 2; ++i ) hipEventDestroy(c->evEmit[i]);
-	for ( int i = 0; i < 4; ++i ) hipEventDestroy(c->evLong[i]);
-	hipStreamDestroy(c->stream); hipStreamDestroy(c->stream2); hipEventDestroy(c->evFirstTier); hipEventDestroy(c->evEarlyGeneric); hipEventDestroy(c->evPrescan); for ( int i = 0; i < TIER_NSLOTS; ++i ) hipEventDestroy(c->evslot[i]);
-	c->d_small.release(); for ( int i = 0; i < TIER_NSTAGES; ++i ) { hipEventDestroy(c->st[i].done); c->st[i].handon.release(); c->st[i].slab.release(); }
 	delete c;
 }
 
@@ -588,25 +492,65 @@ static StageCounters const STAGE_COUNTERS[] = {
 	{ ID_VDEEP, &dacc_timing::vdeep_ms, &dacc_timing::vdeep_windows, &dacc_timing::vdeep_out, true, VDEEP_MINS, WORK_VDEEP_COUNT },
 	{ ID_XDEEP, &dacc_timing::xdeep_ms, &dacc_timing::xdeep_windows, &dacc_timing::xdeep_out, true, VDEEP_MINS, WORK_XDEEP_COUNT } };
 
-static int runDevice(dacc_ctx * c)
+// ---- the device pass (runDevice): one function per phase, in the order they run; they share the context and the state of the pass
+// DACC_DEBUG_SYNC=1: wait for every kernel of the generic-only path and say so on stderr (a device fault then names its kernel)
+static bool dbgSync() { static bool const on = getenv("DACC_DEBUG_SYNC") && getenv("DACC_DEBUG_SYNC")[0] == '1'; return on; }
+static void mark(dacc_ctx * c, char const * what) { if ( dbgSync() ) { hipError_t const e = hipStreamSynchronize(c->stream); std::fprintf(stderr,"[dacc] %s: %s\n",what,hipGetErrorString(e)); std::fflush(stderr); } }
+// a stage's work counter (DACC_SCHED bit 0: the tiers pull their windows from a counter)
+static uint32_t * workCounter(dacc_ctx * c, uint32_t const off) { return (c->sched&1) ? c->d_work.p+off : static_cast<uint32_t *>(0); }
+static dacc_ctx::Stage * ranOf(dacc_ctx * c, TierId const id) { return c->st[id].ran ? &c->st[id] : static_cast<dacc_ctx::Stage *>(0); }
+
+struct Pass
 {
-	BatchPlan & BP = c->BP; TierPipeline & TP = c->TP;
-	hipStream_t const s = c->stream;
-	// DACC_DEBUG_SYNC=1: wait for every kernel of the generic-only path and say so on stderr (a device fault then names its kernel)
-	static bool const dbgsync = getenv("DACC_DEBUG_SYNC") && getenv("DACC_DEBUG_SYNC")[0] == '1';
-	auto const mark = [&](char const * what) { if ( dbgsync ) { hipError_t const e = hipStreamSynchronize(s); std::fprintf(stderr,"[dacc] %s: %s\n",what,hipGetErrorString(e)); std::fflush(stderr); } };
-	if ( c->nruns && c->handwant > c->handcap && !c->nohand )
-	{
-		// second use of this context: now the hand-over buffer pays (dacc_submit_piles); an optimisation only -- if the device
-		// cannot spare it, halve it, and in the end do without
-		uint64_t cap = c->handwant;
-		//  never more than half of what the device has free right now: the buffer is an optimisation and must not be what
-		// makes a later, larger batch of this context (or of another worker on the same device) fail its mandatory buffers
-		{ size_t fr = 0, tot = 0; if ( hipMemGetInfo(&fr,&tot) == hipSuccess ) { uint64_t const lim = (static_cast<uint64_t>(fr)/2) / (static_cast<uint64_t>(c->TP.handwords)*8ull); if ( cap > lim ) cap = lim; } else (void)hipGetLastError(); }
-		while ( cap && c->d_hand.ensure(static_cast<size_t>(cap)*c->TP.handwords) != hipSuccess ) { (void)hipGetLastError(); cap = cap > 65536 ? cap/2 : 0; }
-		c->handcap = static_cast<uint32_t>(cap); c->handwant = cap;
-	}
-	++c->nruns;
+	WindowBatch WB;                  // the batch's record; pregen: the pre-scan's first map once the chain starts
+	uint32_t const * list = 0;       // what the last slot or trailing stage that ran handed on (0: all windows)
+	int lastslot = -1;               // the last slot that ran
+	bool early = false;              // the first slot that runs has run: the early generic list is closed, the second stream may read it
+	uint32_t herr[4] = {0,0,0,0};    // d_err behind the last vote: generic engine out of scratch, vote, trace, a window handed on and never run
+	size_t symbytes = 0;             // the symbol stream of the batch
+};
+
+// the batch's record for the window kernels (the main pass's: with its profile counters), no pregen map
+static WindowBatch windowBatch(dacc_ctx * c)
+{
+	BatchPlan & BP = c->BP; WindowBatch WB;
+	WB.P = c->P; WB.T = c->T; WB.C = BP.caps; WB.bps = c->d_bps.p; WB.boff = c->d_boff.p; WB.rlen = c->d_rlen.p;
+	WB.piles = c->d_piles.p; WB.npiles = BP.piles.size(); WB.ovl = c->d_ovl.p; WB.wt_b = c->d_wt_b.p; WB.wt_e = c->d_wt_e.p;
+	WB.nwindows = BP.nwindows; WB.wrec = c->d_wrec.p; WB.wout = c->d_wout.p; WB.arena = c->d_arena.p; WB.prof = c->d_prof.p;
+	return WB;
+}
+// the base record of stage `id`: the batch's record, the stage's capacities, the model tables, the switches and, for a stage of the main stream's chain, the hand-over
+// slots and the ledger mask.  What differs from launch to launch (hand-on list, early list, slab and stride, pregen map, arena) is stated where the launch is
+static FastBatch stageBatch(dacc_ctx * c, WindowBatch const & WB, uint32_t const id, bool const chain = true)
+{
+	FastBatch FB; FB.W = WB; FB.F = c->BP.stageCaps(id); FB.dpsq_vst = c->d_vst.p; FB.tab32 = c->d_tab32.p; FB.feasneed = c->env_feasneed;
+	if ( !chain ) return FB;
+	// (a wide batch has handcap == 0, dacc_submit_piles: its hand-overs go to the generic engine, which sorts for itself)
+	FB.hand = c->handcap ? c->d_hand.p : static_cast<uint64_t *>(0); FB.handctr = c->d_handctr.p; FB.handcap = c->handcap; FB.handwords = c->TP.handwords;
+#if defined(DACC_LEDGER)
+	{ char const * lm = getenv("DACC_LEDGER_MASK"); FB.ledger = lm ? static_cast<uint32_t>(strtoul(lm,0,0)) : 0u; }      // (scripts/ledger.py)
+#endif
+	return FB;
+}
+// where the record's stage hands on, and its slab (one stride of the stage's gbytes per workgroup)
+static void handsOn(FastBatch & FB, uint32_t * const handon, uint8_t * const slab) { FB.retry = handon; FB.gslab = slab; FB.gstride = FB.F.gbytes; }
+
+// 1. second use of this context: now the hand-over buffer pays (dacc_submit_piles); an optimisation only -- if the device cannot spare it, halve it, and in the end do without
+static void growHandOver(dacc_ctx * c)
+{
+	if ( !(c->nruns && c->handwant > c->handcap && !c->nohand) ) return;
+	uint64_t cap = c->handwant;
+	// never more than half of what the device has free right now: the buffer is an optimisation and must not be what makes a later, larger
+	// batch of this context (or of another worker on the same device) fail its mandatory buffers
+	{ size_t fr = 0, tot = 0; if ( hipMemGetInfo(&fr,&tot) == hipSuccess ) { uint64_t const lim = (static_cast<uint64_t>(fr)/2) / (static_cast<uint64_t>(c->TP.handwords)*8ull); if ( cap > lim ) cap = lim; } else (void)hipGetLastError(); }
+	while ( cap && c->d_hand.ensure(static_cast<size_t>(cap)*c->TP.handwords) != hipSuccess ) { (void)hipGetLastError(); cap = cap > 65536 ? cap/2 : 0; }
+	c->handcap = static_cast<uint32_t>(cap); c->handwant = cap;
+}
+
+// 2. block task table, then the trace points of every block -> the window tables
+static int enqueuePrepAndTrace(dacc_ctx * c)
+{
+	BatchPlan & BP = c->BP; hipStream_t const s = c->stream;
 	HIPCHK(hipMemsetAsync(c->d_err.p,0,4*sizeof(uint32_t),s));
 	HIPCHK(hipEventRecord(c->ev[0],s));
 	if ( BP.ovl.size() )
@@ -627,306 +571,299 @@ static int runDevice(dacc_ctx * c)
 		else if ( c->tr_words == 4 ) hipLaunchKernelGGL(k_trace_wide<4>,dim3(c->tr_grid),dim3(64),c->tr_lds,s,TB,c->tr_lanes);
 		else hipLaunchKernelGGL(k_trace_wide<8>,dim3(c->tr_grid),dim3(64),c->tr_lds,s,TB,c->tr_lanes);
 	}
-	mark("prep + trace");
+	mark(c,"prep + trace");
 	HIPCHK(hipEventRecord(c->ev[1],s));
-	if ( BP.nwindows )
+	return DACC_OK;
+}
+
+// 3. windows only the generic engine can run (a string longer than 64 bases): found by a scan of the window tables, for the second stream to start
+// concurrently with all LDS tiers; then the lists and counters of the chain are cleared
+static int enqueuePrescan(dacc_ctx * c, Pass & P)
+{
+	BatchPlan & BP = c->BP; TierPipeline & TP = c->TP; hipStream_t const s = c->stream;
+	HIPCHK(hipMemsetAsync(c->d_pregen.p,0,((BP.nwindows+31)/32+1)*sizeof(uint32_t),s));
+	HIPCHK(hipMemsetAsync(c->d_pregen2.p,0,((BP.nwindows+31)/32+1)*sizeof(uint32_t),s));
+	HIPCHK(hipMemsetAsync(c->d_pregenlist.p,0,sizeof(uint32_t),s));
+	for ( int i = 0; i < TIER_NSLOTS; ++i ) HIPCHK(hipMemsetAsync(c->d_retry[i].p,0,sizeof(uint32_t),s));
+	if ( BP.ovl.size() )
 	{
-		WindowBatch WB;
-		WB.P = c->P; WB.T = c->T; WB.C = BP.caps; WB.bps = c->d_bps.p; WB.boff = c->d_boff.p; WB.rlen = c->d_rlen.p;
-		WB.piles = c->d_piles.p; WB.npiles = BP.piles.size(); WB.ovl = c->d_ovl.p; WB.wt_b = c->d_wt_b.p; WB.wt_e = c->d_wt_e.p;
-		WB.nwindows = BP.nwindows; WB.wrec = c->d_wrec.p; WB.wout = c->d_wout.p; WB.arena = c->d_arena.p; WB.prof = c->d_prof.p;
-		WB.pregen = 0;
-		for ( uint32_t i = 0; i < TIER_NSTAGES; ++i ) c->st[i].ran = false;
-		// no LDS tier usable (DACC_TIERS=0 or a model table no tier's overlay holds): everything runs in the generic engine on
-		// the main stream; the pre-scan / second stream would hand the same windows to two kernels
-		if ( TP.usefast && TP.anytier() )
-		{
-			// windows only the generic engine can run (a string longer than 64 bases): found by a scan of the window tables and
-			// started on the second stream now, concurrently with all LDS tiers
-			HIPCHK(hipMemsetAsync(c->d_pregen.p,0,((BP.nwindows+31)/32+1)*sizeof(uint32_t),s));
-			HIPCHK(hipMemsetAsync(c->d_pregen2.p,0,((BP.nwindows+31)/32+1)*sizeof(uint32_t),s));
-			HIPCHK(hipMemsetAsync(c->d_pregenlist.p,0,sizeof(uint32_t),s));
-			for ( int i = 0; i < TIER_NSLOTS; ++i ) HIPCHK(hipMemsetAsync(c->d_retry[i].p,0,sizeof(uint32_t),s));
-			if ( BP.ovl.size() )
-			{
-				hipLaunchKernelGGL(k_prescan,dim3((BP.ovl.size()+3)/4),dim3(256),0,s,c->d_ovl.p,static_cast<uint64_t>(BP.ovl.size()),c->d_ovl_pile.p,c->d_piles.p,c->d_wt_b.p,c->d_wt_e.p,c->d_pregen.p,c->d_pregen2.p,TP.widetier ? 128u : 64u);
-				// windows with a string of 65 ... 128 bases join the first slot's hand-overs when the second slot's tier holds such strings (tiers 6 / 3;
-				// a deep batch's tier 2 does not: it hands them on to tier 3 at its length check) and the first slot runs at all
-				hipLaunchKernelGGL(k_prescan_lists,dim3(((BP.nwindows+31)/32+255)/256),dim3(256),0,s,c->d_pregen.p,c->d_pregen2.p,static_cast<uint64_t>(BP.nwindows),c->d_pregenlist.p,
-					TP.slot1_long ? c->d_retry[0].p : static_cast<uint32_t *>(0),c->d_wout.p);
-			}
-			HIPCHK(hipEventRecord(c->evPrescan,s));
-			FastBatch FL; FL.W = WB; FL.W.arena = c->d_arena2.p; FL.W.prof = 0; FL.W.pregen = 0; FL.F = BP.stageCaps(ID_LONG); FL.dpsq_vst = c->d_vst.p; FL.retry = 0; FL.gearly = 0; FL.gslab = 0; FL.gstride = 0; FL.tab32 = c->d_tab32.p; FL.hand = 0; FL.handctr = 0; FL.handcap = 0; FL.handwords = 0; FL.feasneed = c->env_feasneed;
-#if defined(DACC_LEDGER)
-			FL.ledger = 0;
-#endif
-			// (k_window_long runs tier 5 in its own LDS; a wide batch's ID_LONG is tier 17, a kernel of its own in front of it -- k_window_long then is the generic
-			// engine alone and never sees that tier's capacities)
-			bool const long5 = TP.ok[ID_LONG] && TP.tier[ID_LONG] == 5;
-			if ( TP.tier[ID_LONG] != 5 ) FL.F = tierCaps(5,c->H.nrows,c->H.nsup);
-			if ( !long5 ) FL.F.ldsbytes = 0;
-			// a launch the device refuses (the LDS of a whole CU) falls back to the generic engine alone, for good
-			// (round 5) The length of a list is fetched before its launch and the grid follows it: an empty list -- the rule at the default
-			// window -- is not launched at all, a list of three windows asks for three CUs' worth of LDS instead of 256.  Rounds 1-4 queued
-			// the full grid twice per pass; its workgroups need the LDS of a whole CU each and sat in the queue until the tier in front retired
-			// (939 ms of "duration" for one window in the round-4 kernel table).
-			// (round 6) The 4 byte copy and the wait run on the SECOND stream, behind the event of the kernel that fills the
-			// list, and only after every tier and the generic kernel have been queued on the main stream: round 5 synchronised the main
-			// stream in the middle of the chain, which kept the host -- and a second context's batches on the same device -- out of the
-			// queue until the first tier had retired.
-			auto const launchLong = [&](uint32_t const * const lst, uint32_t & nlist, hipEvent_t const filled, uint32_t const which) -> int
-			{
-				nlist = 0;
-				HIPCHK(hipStreamWaitEvent(c->stream2,filled,0));
-				HIPCHK(hipMemcpyAsync(&nlist,lst,sizeof(uint32_t),hipMemcpyDeviceToHost,c->stream2));
-				HIPCHK(hipStreamSynchronize(c->stream2));
-				if ( !nlist ) return DACC_OK;
-				uint32_t const * glist = lst;      // what the generic engine of this stream reads
-				if ( TP.ok[ID_LONG] && TP.tier[ID_LONG] != 5 )
-				{
-					// the long string stage of a wide batch (tier 17: strings of up to 255 bases, layout in device memory): a kernel of its own over the list, no
-					// LDS, a slab of grid x gbytes and a hand-on list, both allocated here, where the list is known not to be empty (the second stream is idle: the
-					// copy above has been waited for).  Optional like the last stage's slab: without memory for it the batch runs without the stage
-					FastCaps const & F = BP.stageCaps(ID_LONG);
-					uint32_t const grid = tierGridGmem(F.gbytes,nlist);
-					hipError_t e = c->d_longhand[which].ensure(BP.nwindows+2);
-					if ( e == hipSuccess ) e = c->d_longslab.ensure(static_cast<size_t>(grid)*F.gbytes + 256);
-					if ( e == hipErrorOutOfMemory ) { (void)hipGetLastError(); c->d_longslab.release(); TP.ok[ID_LONG] = false; }
-					else
-					{
-						HIPCHK(e);
-						FastBatch FS = FL; FS.F = F; FS.W.pregen = 0; FS.retry = c->d_longhand[which].p; FS.gearly = 0; FS.gslab = c->d_longslab.p; FS.gstride = F.gbytes;
-						uint32_t * const wk = (c->sched&1) ? c->d_work.p + TIER_CHAIN[ID_LONG].work + 8u*which : static_cast<uint32_t *>(0);
-						HIPCHK(hipMemsetAsync(FS.retry,0,sizeof(uint32_t),c->stream2));
-						if ( wk ) HIPCHK(hipMemsetAsync(wk,0,8*sizeof(uint32_t),c->stream2));
-						HIPCHK(hipEventRecord(c->evLong[2*which],c->stream2));
-						hipLaunchKernelGGL(fastKernel(TP.tier[ID_LONG]),dim3(grid),dim3(64),0,c->stream2,FS,lst,wk);
-						HIPCHK(hipEventRecord(c->evLong[2*which+1],c->stream2));
-						c->longran[which] = true;
-						glist = FS.retry;      // (its length is read on the device: workgroups beyond it leave at once)
-					}
-				}
-				uint32_t const grid = nlist < c->early_grid ? nlist : c->early_grid;
-				(void)hipGetLastError();
-				hipLaunchKernelGGL(k_window_long,dim3(grid),dim3(64),FL.F.ldsbytes,c->stream2,FL,c->d_err.p,glist);
-				if ( FL.F.ldsbytes && hipGetLastError() != hipSuccess )
-				{
-					TP.ok[ID_LONG] = false; FL.F.ldsbytes = 0;
-					hipLaunchKernelGGL(k_window_long,dim3(grid),dim3(64),0,c->stream2,FL,c->d_err.p,glist);
-				}
-				return DACC_OK;
-			};
-			c->nlong[0] = c->nlong[1] = 0; c->longran[0] = c->longran[1] = false;
-			WB.pregen = c->d_pregen.p;
-			HIPCHK(hipMemsetAsync(c->d_gearly.p,0,sizeof(uint32_t),s));
-			HIPCHK(hipMemsetAsync(c->d_handctr.p,0,sizeof(uint32_t),s));
-			bool early = false;
-			HIPCHK(hipMemsetAsync(c->d_work.p,0,WORK_LONGSTR*sizeof(uint32_t),s));      // (the long string stage's counters are the second stream's: cleared there, in front of its launch)
-			// the chain (tier_pipeline.hpp): every slot takes the windows the previous one handed over (list = 0: all windows)
-			auto const work = [&](uint32_t const off) { return (c->sched&1) ? c->d_work.p+off : static_cast<uint32_t *>(0); };
-			uint32_t const * list = 0; int lastslot = -1;
-			FastBatch FZ;      // the trailing stages' batch record: that of the last slot that ran, with their own capacities, list and slab
-			for ( uint32_t slot = 0; slot < TIER_NSLOTS; ++slot )
-			{
-				if ( TP.slotok(slot) )
-				{
-					int const m = TIER_MAIN[slot];
-					FastBatch FB; FB.W = WB; FB.F = BP.stageCaps(m); FB.dpsq_vst = c->d_vst.p; FB.retry = c->d_retry[slot].p;
-					// the first slot's tiers skip every window with a string of more than 64 bases; the later ones only those the second stream has
-					// (without the 128-base route: all of them, as in rounds 3-5)
-					if ( (slot > 0 && TP.late_long) || TP.widetier ) FB.W.pregen = c->d_pregen2.p;
-					FB.gslab = c->d_gslab.p; FB.gstride = FB.F.gbytes; FB.tab32 = c->d_tab32.p;
-					// (a wide batch has handcap == 0, dacc_submit_piles: its hand-overs go to the generic engine, which sorts for itself)
-					FB.hand = c->handcap ? c->d_hand.p : static_cast<uint64_t *>(0); FB.handctr = c->d_handctr.p; FB.handcap = c->handcap; FB.handwords = TP.handwords; FB.feasneed = c->env_feasneed;
-#if defined(DACC_LEDGER)
-					{ char const * lm = getenv("DACC_LEDGER_MASK"); FB.ledger = lm ? static_cast<uint32_t>(strtoul(lm,0,0)) : 0u; }      // (scripts/ledger.py)
-#endif
-					// only the first tier feeds the early generic list (its kernel reads the list once, right after that tier): a
-					// window that reaches a later tier first (mao beyond the earlier tier) and turns out to be generic-only takes
-					// the ordinary hand-over chain to the generic kernel at the end
-					FB.gearly = early ? static_cast<uint32_t *>(0) : c->d_gearly.p;
-					// the front tiers of the slot that run in this pass, each handing on to the next stage of the slot
-					// (tier 7 switches itself off for the rest of a context's batches when it hands on more than a fifth of what it runs: on the
-					// ONT mix at k = 10 / 12 a third / a quarter of its windows overflow it late, on their stretches and pools, and the class costs
-					// 2.6 / 1.4 % instead of gaining the 3 % it gains at k = 14 and 16 and on config 2, profiles/r06j; results do not depend on it)
-					int fr[TIER_NSTAGES]; uint32_t nfr = 0;
-					for ( int i = 0; i < m; ++i ) if ( TIER_CHAIN[i].slot == slot && TP.ok[i] && !((TIER_CHAIN[i].flags & STAGE_ADAPTIVE) && c->tier7_adapt_off) ) fr[nfr++] = i;
-					bool const classed = nfr && (TIER_CHAIN[fr[0]].flags & STAGE_PREPASS);
-					if ( classed ) HIPCHK(hipMemsetAsync(c->d_small.p,0,sizeof(uint32_t),s));
-					for ( uint32_t k = 0; k < nfr; ++k ) HIPCHK(hipMemsetAsync(c->st[fr[k]].handon.p,0,sizeof(uint32_t),s));
-					uint32_t const * in = list;
-					if ( classed )
-					{
-						// size classes: the small windows run in tier 0 (8 wavefronts per CU), the middle class and tier 0's hand-overs in tier 7
-						// (7 per CU), tier 7's hand-overs and all other windows in tier 1 (6 per CU); without tier 7 the middle class counts as big
-						uint32_t * const mid = c->st[fr[0]].handon.p, * const big = c->st[fr[nfr-1]].handon.p;
-						hipLaunchKernelGGL(k_classify,dim3((BP.nwindows+255)/256),dim3(256),0,s,WB,c->d_small.p,mid,big,c->sw.t0inst,nfr > 1 ? c->sw.t7inst : 0u);
-						// (what the pre-pass itself put on the middle and the big list, before the tiers' hand-overs join them: for the counters of dacc_timing)
-						if ( nfr > 1 ) { HIPCHK(hipMemcpyAsync(c->d_work.p+WORK_PRE_MID,mid,sizeof(uint32_t),hipMemcpyDeviceToDevice,s)); HIPCHK(hipMemcpyAsync(c->d_work.p+WORK_PRE_BIG,big,sizeof(uint32_t),hipMemcpyDeviceToDevice,s)); }
-						in = c->d_small.p;
-					}
-					for ( uint32_t k = 0; k < nfr; ++k )
-					{
-						dacc_ctx::Stage & S = c->st[fr[k]];
-						FastBatch FF = FB; FF.F = BP.stageCaps(fr[k]); FF.retry = S.handon.p; FF.gstride = FF.F.gbytes;
-						hipLaunchKernelGGL(fastKernel(TP.tier[fr[k]]),dim3(S.grid),dim3(64),FF.F.gmem ? 0u : FF.F.ldsbytes,s,FF,in,work(TIER_CHAIN[fr[k]].work));
-						HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = in;
-						in = S.handon.p;
-					}
-					// (a device-memory tier in a slot, DACC_LAST_AS_SLOT2=1: no LDS)
-					hipLaunchKernelGGL(fastKernel(TP.tier[m]),dim3(c->st[m].grid),dim3(64),FB.F.gmem ? 0u : FB.F.ldsbytes,s,FB,in,work(TIER_CHAIN[m].work));
-					list = c->d_retry[slot].p; lastslot = static_cast<int>(slot);
-					if ( !early )
-					{
-						// the first tier has seen every window: what only the generic engine can run starts now, on its own
-						// (high priority) stream and arena, while the remaining tiers run
-						early = true;
-						HIPCHK(hipEventRecord(c->evFirstTier,s));
-					}
-					FZ = FB;
-				}
-				hipEventRecord(c->evslot[slot],s);
-			}
-			uint32_t const * const slotlist = list;      // what the last enabled slot handed on (dacc_debug_retry, tier_out)
-			// the trailing stages (tier_pipeline.hpp: layout in device memory), in chain order: each takes the list the stage or slot in front of it that ran
-			// handed on and hands on to the next, the last to the generic engine; one that does not run (switched off, no window deep enough in the batch)
-			// leaves the list as it is.  They skip the windows the second stream has, like every slot behind the first, and feed no early list (the early
-			// kernel has read its list)
-			for ( uint32_t i = 0; i < TIER_NSTAGES; ++i )
-				if ( TIER_CHAIN[i].role == ROLE_LAST && TP.ok[i] && list && lastslot >= 0 )
-				{
-					dacc_ctx::Stage & S = c->st[i];
-					FZ.F = BP.stageCaps(i); FZ.retry = S.handon.p; FZ.gearly = 0; FZ.gslab = S.slab.p; FZ.gstride = FZ.F.gbytes;
-					FZ.W.pregen = (TP.late_long || TP.widetier) ? c->d_pregen2.p : c->d_pregen.p;
-					HIPCHK(hipMemsetAsync(S.handon.p,0,sizeof(uint32_t),s));
-					hipLaunchKernelGGL(fastKernel(TP.tier[i]),dim3(S.grid),dim3(64),0,s,FZ,list,work(TIER_CHAIN[i].work));
-					HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = list;
-					list = S.handon.p;
-				}
-			if ( c->env_dbgretry && slotlist )
-			{
-				uint32_t const * const list = slotlist;
-				// debugging: which windows did the last LDS tier hand on, and why (flags of its FFAIL)
-				HIPCHK(hipStreamSynchronize(s));
-				uint32_t n = 0; HIPCHK(hipMemcpy(&n,list,sizeof(uint32_t),hipMemcpyDeviceToHost));
-				std::vector<uint32_t> idx(n); if ( n ) HIPCHK(hipMemcpy(idx.data(),list+1,n*sizeof(uint32_t),hipMemcpyDeviceToHost));
-				c->retry_flags.clear();
-				for ( uint32_t i = 0; i < n; ++i ) { WindowOut o; HIPCHK(hipMemcpy(&o,c->d_wout.p+idx[i],sizeof(WindowOut),hipMemcpyDeviceToHost)); c->retry_flags.push_back(idx[i]); c->retry_flags.push_back(o.flags); c->retry_flags.push_back(o.mao); c->retry_flags.push_back(static_cast<uint32_t>(o.filterfreq)); }
-			}
-			// what is left (rare shapes) goes through the generic engine
-			hipLaunchKernelGGL(k_window,dim3(c->retry_grid),dim3(64),0,s,WB,c->d_err.p,list,(c->sched&2) ? c->d_work.p+WORK_GENERIC : static_cast<uint32_t *>(0));
-			// the second stream: the pre-scan's list (a string of more than 64 bases) as soon as the pre-scan is done, the first tier's
-			// generic-only windows behind the first tier; the main stream's queue is full by now
-			{ int const rc = launchLong(static_cast<uint32_t const *>(c->d_pregenlist.p),c->nlong[0],c->evPrescan,0); if ( rc ) return rc; }
-			if ( early ) { int const rc = launchLong(static_cast<uint32_t const *>(c->d_gearly.p),c->nlong[1],c->evFirstTier,1); if ( rc ) return rc; }
-			// everything the second stream ran (pre-scan list, first tier's generic-only windows) must be done before the vote
-			HIPCHK(hipEventRecord(c->evEarlyGeneric,c->stream2));
-			HIPCHK(hipStreamWaitEvent(s,c->evEarlyGeneric,0));
-		}
-		else
-			{ HIPCHK(hipMemsetAsync(c->d_work.p,0,WORK_WORDS*sizeof(uint32_t),s)); hipLaunchKernelGGL(k_window,dim3(c->win_grid),dim3(64),0,s,WB,c->d_err.p,static_cast<uint32_t const *>(0),(c->sched&2) ? c->d_work.p+WORK_GENERIC : static_cast<uint32_t *>(0)); mark("k_window (all windows)"); }
+		hipLaunchKernelGGL(k_prescan,dim3((BP.ovl.size()+3)/4),dim3(256),0,s,c->d_ovl.p,static_cast<uint64_t>(BP.ovl.size()),c->d_ovl_pile.p,c->d_piles.p,c->d_wt_b.p,c->d_wt_e.p,c->d_pregen.p,c->d_pregen2.p,TP.widetier ? 128u : 64u);
+		// windows with a string of 65 ... 128 bases join the first slot's hand-overs when the second slot's tier holds such strings (tiers 6 / 3;
+		// a deep batch's tier 2 does not: it hands them on to tier 3 at its length check) and the first slot runs at all
+		hipLaunchKernelGGL(k_prescan_lists,dim3(((BP.nwindows+31)/32+255)/256),dim3(256),0,s,c->d_pregen.p,c->d_pregen2.p,static_cast<uint64_t>(BP.nwindows),c->d_pregenlist.p,
+			TP.slot1_long ? c->d_retry[0].p : static_cast<uint32_t *>(0),c->d_wout.p);
 	}
-	HIPCHK(hipEventRecord(c->ev[2],s));
-	uint32_t herr[4] = {0,0,0,0};
-	size_t const symbytes = 2*BP.npos + 64*BP.piles.size() + 64;
-	c->h_nfrag.resize(BP.piles.size()); c->h_frags.resize(BP.nfragslots+1); HIPCHK(c->h_outsym.ensure(symbytes));
-	auto voteAndFetch = [&]() -> int
+	HIPCHK(hipEventRecord(c->evPrescan,s));
+	c->nlong[0] = c->nlong[1] = 0; c->longran[0] = c->longran[1] = false;
+	P.WB.pregen = c->d_pregen.p;
+	HIPCHK(hipMemsetAsync(c->d_gearly.p,0,sizeof(uint32_t),s));
+	HIPCHK(hipMemsetAsync(c->d_handctr.p,0,sizeof(uint32_t),s));
+	HIPCHK(hipMemsetAsync(c->d_work.p,0,WORK_LONGSTR*sizeof(uint32_t),s));      // (the long string stage's counters are the second stream's: cleared there, in front of its launch)
+	return DACC_OK;
+}
+
+// 4. one slot of the chain (tier_pipeline.hpp): the pre-pass and the front tiers of the slot that run in this pass, each handing on to the next stage of the
+// slot, then its main tier; it takes the windows the slot in front handed over (P.list = 0: all windows)
+static int enqueueSlot(dacc_ctx * c, Pass & P, uint32_t const slot)
+{
+	BatchPlan & BP = c->BP; TierPipeline & TP = c->TP; hipStream_t const s = c->stream;
+	if ( !TP.slotok(slot) ) return DACC_OK;
+	int const m = TIER_MAIN[slot];
+	FastBatch FB = stageBatch(c,P.WB,m); handsOn(FB,c->d_retry[slot].p,c->d_gslab.p);
+	// the first slot's tiers skip every window with a string of more than 64 bases; the later ones only those the second stream has (without the 128-base route: all of them)
+	if ( (slot > 0 && TP.late_long) || TP.widetier ) FB.W.pregen = c->d_pregen2.p;
+	// only the first tier feeds the early generic list (its kernel reads the list once, right after that tier): a window that reaches a later tier first
+	// (mao beyond the earlier tier) and turns out to be generic-only takes the ordinary hand-over chain to the generic kernel at the end
+	FB.gearly = P.early ? static_cast<uint32_t *>(0) : c->d_gearly.p;
+	// (tier 7 switches itself off for the rest of a context's batches when it hands on more than a fifth of what it runs: on the
+	// ONT mix at k = 10 / 12 a third / a quarter of its windows overflow it late, on their stretches and pools, and the class costs
+	// 2.6 / 1.4 % instead of gaining the 3 % it gains at k = 14 and 16 and on config 2, profiles/r06j; results do not depend on it)
+	int fr[TIER_NSTAGES]; uint32_t nfr = 0;
+	for ( int i = 0; i < m; ++i ) if ( TIER_CHAIN[i].slot == slot && TP.ok[i] && !((TIER_CHAIN[i].flags & STAGE_ADAPTIVE) && c->tier7_adapt_off) ) fr[nfr++] = i;
+	bool const classed = nfr && (TIER_CHAIN[fr[0]].flags & STAGE_PREPASS);
+	if ( classed ) HIPCHK(hipMemsetAsync(c->d_small.p,0,sizeof(uint32_t),s));
+	for ( uint32_t k = 0; k < nfr; ++k ) HIPCHK(hipMemsetAsync(c->st[fr[k]].handon.p,0,sizeof(uint32_t),s));
+	uint32_t const * in = P.list;
+	if ( classed )
 	{
-		HIPCHK(hipMemsetAsync(c->d_pilebad.p,0,BP.piles.size()+1,s));
-		// the tiers' pending records become final ones (every engine is done: the main stream has waited for the second one); on the
-		// path where all windows went through k_window it finds nothing pending
-		HIPCHK(hipEventRecord(c->evEmit[0],s));
-		if ( BP.nwindows ) { hipLaunchKernelGGL(k_emit,dim3((BP.nwindows+255)/256),dim3(256),0,s,c->d_wrec.p,static_cast<uint64_t>(BP.nwindows),c->par.w); mark("k_emit"); }
-		HIPCHK(hipEventRecord(c->evEmit[1],s));
-		if ( BP.nwindows ) hipLaunchKernelGGL(k_check_done,dim3((BP.nwindows+255)/256),dim3(256),0,s,c->d_wout.p,BP.nwindows,c->d_err.p+3,c->d_piles.p,static_cast<uint32_t>(BP.piles.size()),c->d_pilebad.p);
-		if ( BP.piles.size() )
+		// size classes: the small windows run in tier 0 (8 wavefronts per CU), the middle class and tier 0's hand-overs in tier 7
+		// (7 per CU), tier 7's hand-overs and all other windows in tier 1 (6 per CU); without tier 7 the middle class counts as big
+		uint32_t * const mid = c->st[fr[0]].handon.p, * const big = c->st[fr[nfr-1]].handon.p;
+		hipLaunchKernelGGL(k_classify,dim3((BP.nwindows+255)/256),dim3(256),0,s,P.WB,c->d_small.p,mid,big,c->sw.t0inst,nfr > 1 ? c->sw.t7inst : 0u);
+		// (what the pre-pass itself put on the middle and the big list, before the tiers' hand-overs join them: for the counters of dacc_timing)
+		if ( nfr > 1 ) { HIPCHK(hipMemcpyAsync(c->d_work.p+WORK_PRE_MID,mid,sizeof(uint32_t),hipMemcpyDeviceToDevice,s)); HIPCHK(hipMemcpyAsync(c->d_work.p+WORK_PRE_BIG,big,sizeof(uint32_t),hipMemcpyDeviceToDevice,s)); }
+		in = c->d_small.p;
+	}
+	for ( uint32_t k = 0; k < nfr; ++k )
+	{
+		dacc_ctx::Stage & S = c->st[fr[k]];
+		FastBatch FF = FB; FF.F = BP.stageCaps(fr[k]); handsOn(FF,S.handon.p,FB.gslab);
+		hipLaunchKernelGGL(fastKernel(TP.tier[fr[k]]),dim3(S.grid),dim3(64),FF.F.gmem ? 0u : FF.F.ldsbytes,s,FF,in,workCounter(c,TIER_CHAIN[fr[k]].work));
+		HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = in;
+		in = S.handon.p;
+	}
+	// (a device-memory tier in a slot, DACC_LAST_AS_SLOT2=1: no LDS)
+	hipLaunchKernelGGL(fastKernel(TP.tier[m]),dim3(c->st[m].grid),dim3(64),FB.F.gmem ? 0u : FB.F.ldsbytes,s,FB,in,workCounter(c,TIER_CHAIN[m].work));
+	P.list = c->d_retry[slot].p; P.lastslot = static_cast<int>(slot);
+	if ( !P.early )
+	{
+		// the first tier has seen every window: what only the generic engine can run starts now, on its own (high priority) stream and arena, while the remaining tiers run
+		P.early = true;
+		HIPCHK(hipEventRecord(c->evFirstTier,s));
+	}
+	return DACC_OK;
+}
+
+// 5. the trailing stages (tier_pipeline.hpp: layout in device memory), in chain order: each takes the list the stage or slot in front of it that ran
+// handed on and hands on to the next, the last to the generic engine; one that does not run (switched off, no window deep enough in the batch)
+// leaves the list as it is.  They skip the windows the second stream has, like every slot behind the first, and feed no early list (the early
+// kernel has read its list)
+static int enqueueTrailingStages(dacc_ctx * c, Pass & P)
+{
+	TierPipeline & TP = c->TP; hipStream_t const s = c->stream;
+	for ( uint32_t i = 0; i < TIER_NSTAGES; ++i )
+		if ( TIER_CHAIN[i].role == ROLE_LAST && TP.ok[i] && P.list && P.lastslot >= 0 )
 		{
-			VoteBatch VB;
-			VB.P = c->P; VB.bps = c->d_bps.p; VB.boff = c->d_boff.p; VB.rlen = c->d_rlen.p; VB.piles = c->d_piles.p; VB.npiles = BP.piles.size();
-			VB.wrec = c->d_wrec.p; VB.has = c->d_has.p; VB.ld0 = c->d_ld0.p; VB.oc = c->d_oc.p; VB.ocs = c->d_ocs.p; VB.outsym = c->d_outsym.p;
-			VB.frags = c->d_frags.p; VB.fragbase = c->d_fragbase.p; VB.nfrag = c->d_nfrag.p; VB.errflag = c->d_err.p + 1; VB.pilebad = c->d_pilebad.p;
-			mark("k_check_done");
-			hipLaunchKernelGGL(k_vote,dim3(BP.piles.size()),dim3(256),0,s,VB);
-			mark("k_vote");
+			dacc_ctx::Stage & S = c->st[i];
+			FastBatch FZ = stageBatch(c,P.WB,i); handsOn(FZ,S.handon.p,S.slab.p);
+			FZ.W.pregen = (TP.late_long || TP.widetier) ? c->d_pregen2.p : c->d_pregen.p;
+			HIPCHK(hipMemsetAsync(S.handon.p,0,sizeof(uint32_t),s));
+			hipLaunchKernelGGL(fastKernel(TP.tier[i]),dim3(S.grid),dim3(64),0,s,FZ,P.list,workCounter(c,TIER_CHAIN[i].work));
+			HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = P.list;
+			P.list = S.handon.p;
 		}
-		HIPCHK(hipEventRecord(c->ev[3],s));
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(herr,c->d_err.p,sizeof(herr),hipMemcpyDeviceToHost,s));
-		if ( BP.piles.size() )
+	return DACC_OK;
+}
+
+// 6. DACC_DEBUG_RETRY: which windows did the last LDS tier hand on, and why (flags of its FFAIL)
+static int dumpRetryFlags(dacc_ctx * c, uint32_t const * const list)
+{
+	HIPCHK(hipStreamSynchronize(c->stream));
+	uint32_t n = 0; HIPCHK(hipMemcpy(&n,list,sizeof(uint32_t),hipMemcpyDeviceToHost));
+	std::vector<uint32_t> idx(n); if ( n ) HIPCHK(hipMemcpy(idx.data(),list+1,n*sizeof(uint32_t),hipMemcpyDeviceToHost));
+	c->retry_flags.clear();
+	for ( uint32_t i = 0; i < n; ++i ) { WindowOut o; HIPCHK(hipMemcpy(&o,c->d_wout.p+idx[i],sizeof(WindowOut),hipMemcpyDeviceToHost)); c->retry_flags.push_back(idx[i]); c->retry_flags.push_back(o.flags); c->retry_flags.push_back(o.mao); c->retry_flags.push_back(static_cast<uint32_t>(o.filterfreq)); }
+	return DACC_OK;
+}
+
+// 7b. one list of the second stream.  The length of the list is fetched before its launch and the grid follows it: an empty list -- the rule at the
+// default window -- is not launched at all, a list of three windows asks for three CUs' worth of LDS instead of 256.
+// The 4 byte copy and the wait run on the SECOND stream, behind the event of the kernel that fills the list, and only after every tier and the
+// generic kernel have been queued on the main stream: a wait in the middle of the chain keeps the host -- and a second context's batches on the
+// same device -- out of the queue until the first tier has retired.
+static int launchLong(dacc_ctx * c, FastBatch & FL, uint32_t const * const lst, hipEvent_t const filled, uint32_t const which)
+{
+	BatchPlan & BP = c->BP; TierPipeline & TP = c->TP;
+	uint32_t & nlist = c->nlong[which]; nlist = 0;
+	HIPCHK(hipStreamWaitEvent(c->stream2,filled,0));
+	HIPCHK(hipMemcpyAsync(&nlist,lst,sizeof(uint32_t),hipMemcpyDeviceToHost,c->stream2));
+	HIPCHK(hipStreamSynchronize(c->stream2));
+	if ( !nlist ) return DACC_OK;
+	uint32_t const * glist = lst;      // what the generic engine of this stream reads
+	if ( TP.ok[ID_LONG] && TP.tier[ID_LONG] != 5 )
+	{
+		// the long string stage of a wide batch (tier 17: strings of up to 255 bases, layout in device memory): a kernel of its own over the list, no
+		// LDS, a slab of grid x gbytes and a hand-on list, both allocated here, where the list is known not to be empty (the second stream is idle: the
+		// copy above has been waited for).  Optional like the last stage's slab: without memory for it the batch runs without the stage
+		FastCaps const & F = BP.stageCaps(ID_LONG);
+		uint32_t const grid = tierGridGmem(F.gbytes,nlist);
+		hipError_t e = c->d_longhand[which].ensure(BP.nwindows+2);
+		if ( e == hipSuccess ) e = c->d_longslab.ensure(static_cast<size_t>(grid)*F.gbytes + 256);
+		if ( e == hipErrorOutOfMemory ) { (void)hipGetLastError(); c->d_longslab.release(); TP.ok[ID_LONG] = false; }
+		else
 		{
-			HIPCHK(hipMemcpyAsync(c->h_nfrag.data(),c->d_nfrag.p,BP.piles.size()*sizeof(uint32_t),hipMemcpyDeviceToHost,s));
-			HIPCHK(hipMemcpyAsync(c->h_frags.data(),c->d_frags.p,BP.nfragslots*sizeof(VoteFragment),hipMemcpyDeviceToHost,s));
-			HIPCHK(hipMemcpyAsync(c->h_outsym.p,c->d_outsym.p,symbytes,hipMemcpyDeviceToHost,s));
+			HIPCHK(e);
+			FastBatch FS = FL; FS.F = F; handsOn(FS,c->d_longhand[which].p,c->d_longslab.p);
+			uint32_t * const wk = (c->sched&1) ? c->d_work.p + TIER_CHAIN[ID_LONG].work + 8u*which : static_cast<uint32_t *>(0);
+			HIPCHK(hipMemsetAsync(FS.retry,0,sizeof(uint32_t),c->stream2));
+			if ( wk ) HIPCHK(hipMemsetAsync(wk,0,8*sizeof(uint32_t),c->stream2));
+			HIPCHK(hipEventRecord(c->evLong[2*which],c->stream2));
+			hipLaunchKernelGGL(fastKernel(TP.tier[ID_LONG]),dim3(grid),dim3(64),0,c->stream2,FS,lst,wk);
+			HIPCHK(hipEventRecord(c->evLong[2*which+1],c->stream2));
+			c->longran[which] = true;
+			glist = FS.retry;      // (its length is read on the device: workgroups beyond it leave at once)
 		}
-		HIPCHK(hipEventRecord(c->ev[4],s));
-		HIPCHK(hipStreamSynchronize(s));
-		return DACC_OK;
-	};
-	{ int const rc = voteAndFetch(); if ( rc ) return rc; }
-	// dacc_timing's names for the front tiers: tier 0 and tier 7 are the first slot's (size classes), tier 10 the last slot's (dense graphs; tier 11 in deep batches)
-	auto const ranOf = [&](TierId const id) { return c->st[id].ran ? &c->st[id] : static_cast<dacc_ctx::Stage *>(0); };
-	dacc_ctx::Stage * const f0 = ranOf(ID_T0), * const f7 = ranOf(ID_T7), * const fD = ranOf(ID_DENSE), * const fX = ranOf(ID_DEEP);
+	}
+	uint32_t const grid = nlist < c->early_grid ? nlist : c->early_grid;
+	(void)hipGetLastError();
+	hipLaunchKernelGGL(k_window_long,dim3(grid),dim3(64),FL.F.ldsbytes,c->stream2,FL,c->d_err.p,glist);
+	// a launch the device refuses (the LDS of a whole CU) falls back to the generic engine alone, for good
+	if ( FL.F.ldsbytes && hipGetLastError() != hipSuccess )
+	{
+		TP.ok[ID_LONG] = false; FL.F.ldsbytes = 0;
+		hipLaunchKernelGGL(k_window_long,dim3(grid),dim3(64),0,c->stream2,FL,c->d_err.p,glist);
+	}
+	return DACC_OK;
+}
+
+// 7. what is left (rare shapes) goes through the generic engine.  Then, the main stream's queue being full, the second stream: the pre-scan's list (a
+// string of more than 64 bases) as soon as the pre-scan is done, the first tier's generic-only windows behind the first tier
+static int enqueueGenericAndSecondStream(dacc_ctx * c, Pass & P)
+{
+	TierPipeline & TP = c->TP; hipStream_t const s = c->stream; int rc;
+	hipLaunchKernelGGL(k_window,dim3(c->retry_grid),dim3(64),0,s,P.WB,c->d_err.p,P.list,(c->sched&2) ? c->d_work.p+WORK_GENERIC : static_cast<uint32_t *>(0));
+	// the second stream's record: its own arena, no profile counters, every window of its list, no hand-over slots
+	FastBatch FL = stageBatch(c,P.WB,ID_LONG,false); FL.W.arena = c->d_arena2.p; FL.W.prof = 0; FL.W.pregen = 0;
+	// (k_window_long runs tier 5 in its own LDS; a wide batch's ID_LONG is tier 17, a kernel of its own in front of it -- k_window_long then is the generic
+	// engine alone and never sees that tier's capacities)
+	bool const long5 = TP.ok[ID_LONG] && TP.tier[ID_LONG] == 5;
+	if ( TP.tier[ID_LONG] != 5 ) FL.F = tierCaps(5,c->H.nrows,c->H.nsup);
+	if ( !long5 ) FL.F.ldsbytes = 0;
+	if ( (rc = launchLong(c,FL,c->d_pregenlist.p,c->evPrescan,0)) ) return rc;
+	if ( P.early && (rc = launchLong(c,FL,c->d_gearly.p,c->evFirstTier,1)) ) return rc;
+	// everything the second stream ran (pre-scan list, first tier's generic-only windows) must be done before the vote
+	HIPCHK(hipEventRecord(c->evEarlyGeneric,c->stream2));
+	HIPCHK(hipStreamWaitEvent(s,c->evEarlyGeneric,0));
+	return DACC_OK;
+}
+
+// 8. pending records -> final ones, the check that every window was run, the vote; then the error flags, fragments and symbols come back
+static int voteAndFetch(dacc_ctx * c, Pass & P)
+{
+	BatchPlan & BP = c->BP; hipStream_t const s = c->stream;
+	HIPCHK(hipMemsetAsync(c->d_pilebad.p,0,BP.piles.size()+1,s));
+	// the tiers' pending records become final ones (every engine is done: the main stream has waited for the second one); on the
+	// path where all windows went through k_window it finds nothing pending
+	HIPCHK(hipEventRecord(c->evEmit[0],s));
+	if ( BP.nwindows ) { hipLaunchKernelGGL(k_emit,dim3((BP.nwindows+255)/256),dim3(256),0,s,c->d_wrec.p,static_cast<uint64_t>(BP.nwindows),c->par.w); mark(c,"k_emit"); }
+	HIPCHK(hipEventRecord(c->evEmit[1],s));
+	if ( BP.nwindows ) hipLaunchKernelGGL(k_check_done,dim3((BP.nwindows+255)/256),dim3(256),0,s,c->d_wout.p,BP.nwindows,c->d_err.p+3,c->d_piles.p,static_cast<uint32_t>(BP.piles.size()),c->d_pilebad.p);
+	if ( BP.piles.size() )
+	{
+		VoteBatch VB;
+		VB.P = c->P; VB.bps = c->d_bps.p; VB.boff = c->d_boff.p; VB.rlen = c->d_rlen.p; VB.piles = c->d_piles.p; VB.npiles = BP.piles.size();
+		VB.wrec = c->d_wrec.p; VB.has = c->d_has.p; VB.ld0 = c->d_ld0.p; VB.oc = c->d_oc.p; VB.ocs = c->d_ocs.p; VB.outsym = c->d_outsym.p;
+		VB.frags = c->d_frags.p; VB.fragbase = c->d_fragbase.p; VB.nfrag = c->d_nfrag.p; VB.errflag = c->d_err.p + 1; VB.pilebad = c->d_pilebad.p;
+		mark(c,"k_check_done");
+		hipLaunchKernelGGL(k_vote,dim3(BP.piles.size()),dim3(256),0,s,VB);
+		mark(c,"k_vote");
+	}
+	HIPCHK(hipEventRecord(c->ev[3],s));
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(P.herr,c->d_err.p,sizeof(P.herr),hipMemcpyDeviceToHost,s));
+	if ( BP.piles.size() )
+	{
+		HIPCHK(hipMemcpyAsync(c->h_nfrag.data(),c->d_nfrag.p,BP.piles.size()*sizeof(uint32_t),hipMemcpyDeviceToHost,s));
+		HIPCHK(hipMemcpyAsync(c->h_frags.data(),c->d_frags.p,BP.nfragslots*sizeof(VoteFragment),hipMemcpyDeviceToHost,s));
+		HIPCHK(hipMemcpyAsync(c->h_outsym.p,c->d_outsym.p,P.symbytes,hipMemcpyDeviceToHost,s));
+	}
+	HIPCHK(hipEventRecord(c->ev[4],s));
+	HIPCHK(hipStreamSynchronize(s));
+	return DACC_OK;
+}
+
+// 9. dacc_timing's counters of the slots and of the front tiers: tier 0 and tier 7 are the first slot's (size classes), tier 10 the last slot's (dense
+// graphs; tier 11 in deep batches); and tier 7's adaptive switch
+static int fetchTierCounters(dacc_ctx * c)
+{
+	BatchPlan & BP = c->BP; TierPipeline & TP = c->TP;
+	dacc_ctx::Stage * const f0 = ranOf(c,ID_T0), * const f7 = ranOf(c,ID_T7), * const fD = ranOf(c,ID_DENSE);
 	for ( int i = 0; i < 3; ++i ) c->timing.tier_out[i] = 0;
 	if ( TP.usefast && BP.nwindows ) for ( int i = 0; i < 3; ++i ) if ( TP.slotok(i) ) HIPCHK(hipMemcpy(&c->timing.tier_out[i],c->d_retry[i].p,sizeof(uint32_t),hipMemcpyDeviceToHost));
 	c->timing.tier10_out = 0;
 	if ( fD ) HIPCHK(hipMemcpy(&c->timing.tier10_out,fD->handon.p,sizeof(uint32_t),hipMemcpyDeviceToHost));
 	c->timing.tier0_in = 0; c->timing.tier0_out = 0; c->timing.tier7_in = 0; c->timing.tier7_out = 0;
-	if ( TP.usefast && BP.nwindows && TP.anytier() )
+	if ( !(TP.usefast && BP.nwindows && TP.anytier()) ) return DACC_OK;
+	// length of the two lists of the second stream (pre-scan, first tier's generic-only windows), fetched before their launches
+	uint32_t const n1 = c->nlong[0], n2 = c->nlong[1];
+	c->timing.long_windows = n1 + n2; c->timing.long_first_tier = n2;
+	if ( !f0 ) return DACC_OK;
+	// size classes: the pre-pass sent nsmall windows to tier 0, nmid0 to the middle list and nwindows - nsmall - nmid0 - n1 to the big
+	// list; tier 0's hand-overs have joined the middle list since (the big list without tier 7), tier 7's the big list
+	uint32_t nsmall = 0, nbig = 0, nmid = 0;
+	HIPCHK(hipMemcpy(&nsmall,c->d_small.p,sizeof(uint32_t),hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&nbig,(f7 ? f7 : f0)->handon.p,sizeof(uint32_t),hipMemcpyDeviceToHost));
+	if ( f7 ) HIPCHK(hipMemcpy(&nmid,f0->handon.p,sizeof(uint32_t),hipMemcpyDeviceToHost));
+	c->timing.tier0_in = nsmall;
+	if ( !f7 )
 	{
-		// length of the two lists of the second stream (pre-scan, first tier's generic-only windows), fetched before their launches
-		uint32_t const n1 = c->nlong[0], n2 = c->nlong[1];
-		c->timing.long_windows = n1 + n2; c->timing.long_first_tier = n2;
-		if ( f0 )
-		{
-			// size classes: the pre-pass sent nsmall windows to tier 0, nmid0 to the middle list and nwindows - nsmall - nmid0 - n1 to the big
-			// list; tier 0's hand-overs have joined the middle list since (the big list without tier 7), tier 7's the big list
-			uint32_t nsmall = 0, nbig = 0, nmid = 0;
-			HIPCHK(hipMemcpy(&nsmall,c->d_small.p,sizeof(uint32_t),hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&nbig,(f7 ? f7 : f0)->handon.p,sizeof(uint32_t),hipMemcpyDeviceToHost));
-			if ( f7 ) HIPCHK(hipMemcpy(&nmid,f0->handon.p,sizeof(uint32_t),hipMemcpyDeviceToHost));
-			c->timing.tier0_in = nsmall;
-			if ( !f7 )
-			{
-				uint64_t const big0 = BP.nwindows - std::min<uint64_t>(BP.nwindows,static_cast<uint64_t>(nsmall) + n1);
-				c->timing.tier0_out = nbig > big0 ? static_cast<uint32_t>(nbig - big0) : 0u;
-			}
-			else
-			{
-				// nmid = what the pre-pass put on the middle list + tier 0's hand-overs, nbig = the pre-pass's big windows + tier 7's hand-overs
-				uint32_t pre[2] = {0,0};
-				HIPCHK(hipMemcpy(pre,c->d_work.p+WORK_PRE_MID,2*sizeof(uint32_t),hipMemcpyDeviceToHost));
-				uint32_t const t7out = nbig > pre[1] ? nbig - pre[1] : 0u;
-				c->timing.tier0_out = nmid > pre[0] ? nmid - pre[0] : 0u;
-				c->timing.tier7_in = nmid; c->timing.tier7_out = t7out;
-				if ( c->env_t7adapt && nmid >= 4096 && static_cast<uint64_t>(t7out)*5 > nmid ) c->tier7_adapt_off = true;
-			}
-		}
+		uint64_t const big0 = BP.nwindows - std::min<uint64_t>(BP.nwindows,static_cast<uint64_t>(nsmall) + n1);
+		c->timing.tier0_out = nbig > big0 ? static_cast<uint32_t>(nbig - big0) : 0u;
 	}
-	// a window the generic engine could not hold (dense graph at small k): grow its scratch capacities and run those
-	// windows again, then the vote (rare; the capacities stay grown for the rest of the batch geometry)
-	for ( int attempt = 0; herr[0] && !herr[1] && !herr[2] && attempt < 3; ++attempt )
+	else
+	{
+		// nmid = what the pre-pass put on the middle list + tier 0's hand-overs, nbig = the pre-pass's big windows + tier 7's hand-overs
+		uint32_t pre[2] = {0,0};
+		HIPCHK(hipMemcpy(pre,c->d_work.p+WORK_PRE_MID,2*sizeof(uint32_t),hipMemcpyDeviceToHost));
+		uint32_t const t7out = nbig > pre[1] ? nbig - pre[1] : 0u;
+		c->timing.tier0_out = nmid > pre[0] ? nmid - pre[0] : 0u;
+		c->timing.tier7_in = nmid; c->timing.tier7_out = t7out;
+		if ( c->env_t7adapt && nmid >= 4096 && static_cast<uint64_t>(t7out)*5 > nmid ) c->tier7_adapt_off = true;
+	}
+	return DACC_OK;
+}
+
+// 10. a window the generic engine could not hold (dense graph at small k): grow its scratch capacities and run those
+// windows again, then the vote (rare; the capacities stay grown for the rest of the batch geometry)
+static int scratchRetry(dacc_ctx * c, Pass & P)
+{
+	BatchPlan & BP = c->BP; hipStream_t const s = c->stream;
+	for ( int attempt = 0; P.herr[0] && !P.herr[1] && !P.herr[2] && attempt < 3; ++attempt )
 	{
 		growArenaCaps(BP.caps,c->par.w);
 		Arena Atmp; BP.caps.bytes = arena_carve(Atmp,0,BP.caps,c->par.w);
 		uint32_t const g = boundByArena(c->retry_grid < 64 ? c->retry_grid : 64,BP.caps.bytes,4);
 		c->retry_grid = g; c->win_grid = g; if ( c->early_grid > g ) c->early_grid = g;     // later launches of this batch use the grown arenas
 		HIPCHK(c->d_arena.ensure(static_cast<size_t>(g)*BP.caps.bytes));
-		if ( TP.usefast ) HIPCHK(c->d_arena2.ensure(static_cast<size_t>(c->early_grid)*BP.caps.bytes));
+		if ( c->TP.usefast ) HIPCHK(c->d_arena2.ensure(static_cast<size_t>(c->early_grid)*BP.caps.bytes));
 		HIPCHK(c->d_gearly.ensure(BP.nwindows+2)); HIPCHK(c->d_pregenlist.ensure(BP.nwindows+2)); HIPCHK(c->d_pregen.ensure((BP.nwindows+31)/32+2)); HIPCHK(c->d_pregen2.ensure((BP.nwindows+31)/32+2));
 		HIPCHK(hipMemsetAsync(c->d_err.p,0,4*sizeof(uint32_t),s));
 		HIPCHK(hipMemsetAsync(c->d_gearly.p,0,sizeof(uint32_t),s));
 		hipLaunchKernelGGL(k_collect_overflow,dim3((BP.nwindows+255)/256),dim3(256),0,s,c->d_wout.p,BP.nwindows,c->d_gearly.p);
-		mark("k_collect_overflow");
-		if ( dbgsync ) std::fprintf(stderr,"[dacc] scratch retry %d: grid %u, arena %llu bytes per wavefront\n",attempt,g,static_cast<unsigned long long>(BP.caps.bytes));
-		WindowBatch WB;
-		WB.P = c->P; WB.T = c->T; WB.C = BP.caps; WB.bps = c->d_bps.p; WB.boff = c->d_boff.p; WB.rlen = c->d_rlen.p;
-		WB.piles = c->d_piles.p; WB.npiles = BP.piles.size(); WB.ovl = c->d_ovl.p; WB.wt_b = c->d_wt_b.p; WB.wt_e = c->d_wt_e.p;
-		WB.nwindows = BP.nwindows; WB.wrec = c->d_wrec.p; WB.wout = c->d_wout.p; WB.arena = c->d_arena.p; WB.prof = 0; WB.pregen = 0;
+		mark(c,"k_collect_overflow");
+		if ( dbgSync() ) std::fprintf(stderr,"[dacc] scratch retry %d: grid %u, arena %llu bytes per wavefront\n",attempt,g,static_cast<unsigned long long>(BP.caps.bytes));
+		WindowBatch WB = windowBatch(c); WB.prof = 0;      // (the grown capacities and arena)
 		hipLaunchKernelGGL(k_window,dim3(g),dim3(64),0,s,WB,c->d_err.p,static_cast<uint32_t const *>(c->d_gearly.p),static_cast<uint32_t *>(0));
-		mark("k_window (scratch retry)");
-		int const rc = voteAndFetch(); if ( rc ) return rc;
+		mark(c,"k_window (scratch retry)");
+		int const rc = voteAndFetch(c,P); if ( rc ) return rc;
 	}
-	// the counters of the deep-window tier and of the trailing stages (STAGE_COUNTERS), zero for a stage that did not run.  A trailing stage's time runs from
-	// the nearest trailing stage in front of it that ran, else from the last slot
+	return DACC_OK;
+}
+
+// 11. the counters of the deep-window tier and of the trailing stages (STAGE_COUNTERS), zero for a stage that did not run.  A trailing stage's time runs from
+// the nearest trailing stage in front of it that ran, else from the last slot.  Then the long string stage's
+static int fetchStageCounters(dacc_ctx * c)
+{
+	BatchPlan & BP = c->BP; TierPipeline & TP = c->TP; hipStream_t const s = c->stream;
 	hipEvent_t from = c->evslot[TIER_NSLOTS-1];
 	for ( StageCounters const & K : STAGE_COUNTERS )
 	{
@@ -956,8 +893,15 @@ static int runDevice(dacc_ctx * c)
 			hipEventElapsedTime(&lms,c->evLong[2*i],c->evLong[2*i+1]);
 			c->timing.longstr_ms += lms; c->timing.longstr_out += nout; c->timing.longstr_windows += c->nlong[i] > nout ? c->nlong[i] - nout : 0u;
 		}
+	return DACC_OK;
+}
+
+// 12. what the caller collects: the status of every pile and the text of what went wrong, then the fragments
+static int assembleResults(dacc_ctx * c, Pass const & P)
+{
+	BatchPlan & BP = c->BP;
 	c->pile_status = BP.pile_status; c->pile_errors = BP.pile_errors;
-	if ( herr[0] && BP.piles.size() )
+	if ( P.herr[0] && BP.piles.size() )
 	{
 		// windows the generic engine could not hold even with grown scratch: their piles were dropped by the vote
 		std::vector<uint8_t> bad(BP.piles.size());
@@ -969,9 +913,10 @@ static int runDevice(dacc_ctx * c)
 				if ( c->pile_errors.size() < 64 ) c->pile_errors.push_back("read " + std::to_string(BP.piles[pi].aread) + ": window kernel scratch capacity exceeded (depth / graph size), read skipped");
 			}
 	}
-	if ( herr[3] ) { c->err = "internal error: a window was handed on between engines and never processed"; return DACC_EHIP; }
-	if ( herr[1] ) { c->err = "vote kernel capacity exceeded"; return DACC_ENOTSUP; }
-	if ( herr[2] ) { c->err = "trace kernel capacity exceeded (a tspace block longer than the column vectors or a B span beyond the column store)"; return DACC_ENOTSUP; }
+	if ( P.herr[3] ) { c->err = "internal error: a window was handed on between engines and never processed"; return DACC_EHIP; }
+	if ( P.herr[1] ) { c->err = "vote kernel capacity exceeded"; return DACC_ENOTSUP; }
+	if ( P.herr[2] ) { c->err = "trace kernel capacity exceeded (a tspace block longer than the column vectors or a B span beyond the column store)"; return DACC_ENOTSUP; }
+	// 13. the fragments of every pile and their bases, in pile order
 	c->frags.clear(); c->bases.clear();
 	uint64_t nbases = 0;
 	for ( uint64_t pi = 0; pi < BP.piles.size(); ++pi )
@@ -985,6 +930,14 @@ static int runDevice(dacc_ctx * c)
 			c->bases.append(reinterpret_cast<char const *>(c->h_outsym.p)+F.off,F.len);
 			c->frags.push_back(g);
 		}
+	return DACC_OK;
+}
+
+// 14. dacc_timing's times, from the events of the pass
+static void eventTimes(dacc_ctx * c)
+{
+	BatchPlan & BP = c->BP; TierPipeline & TP = c->TP;
+	dacc_ctx::Stage * const f0 = ranOf(c,ID_T0), * const f7 = ranOf(c,ID_T7), * const fD = ranOf(c,ID_DENSE), * const fX = ranOf(c,ID_DEEP);
 	float ms = 0;
 	hipEventElapsedTime(&ms,c->ev[0],c->ev[1]); c->timing.trace_ms = ms;
 	hipEventElapsedTime(&ms,c->ev[1],c->ev[2]); c->timing.window_ms = ms;
@@ -1001,7 +954,47 @@ static int runDevice(dacc_ctx * c)
 	hipEventElapsedTime(&ms,c->ev[3],c->ev[4]); c->timing.d2h_ms = ms;
 	hipEventElapsedTime(&ms,c->ev[0],c->ev[3]); c->timing.total_ms = ms;
 	c->timing.first_tier = (TP.usefast && BP.deep) ? 4u : 1u;
-	c->timing.nwindows = BP.nwindows; c->timing.nblocks = BP.nblocks; c->timing.algo_bytes = BP.algo_bytes + nbases;
+	c->timing.nwindows = BP.nwindows; c->timing.nblocks = BP.nblocks; c->timing.algo_bytes = BP.algo_bytes + c->bases.size();
+}
+
+static int runDevice(dacc_ctx * c)
+{
+	BatchPlan & BP = c->BP; TierPipeline & TP = c->TP; hipStream_t const s = c->stream;
+	Pass P; int rc;
+	growHandOver(c);
+	++c->nruns;
+	if ( (rc = enqueuePrepAndTrace(c)) ) return rc;
+	if ( BP.nwindows )
+	{
+		P.WB = windowBatch(c);
+		for ( dacc_ctx::Stage & S : c->st ) S.ran = false;
+		// no LDS tier usable (DACC_TIERS=0 or a model table no tier's overlay holds): everything runs in the generic engine on
+		// the main stream; the pre-scan / second stream would hand the same windows to two kernels
+		if ( TP.usefast && TP.anytier() )
+		{
+			if ( (rc = enqueuePrescan(c,P)) ) return rc;
+			for ( uint32_t slot = 0; slot < TIER_NSLOTS; ++slot ) { if ( (rc = enqueueSlot(c,P,slot)) ) return rc; hipEventRecord(c->evslot[slot],s); }
+			uint32_t const * const slotlist = P.list;      // what the last enabled slot handed on (dacc_debug_retry, tier_out)
+			if ( (rc = enqueueTrailingStages(c,P)) ) return rc;
+			if ( c->env_dbgretry && slotlist && (rc = dumpRetryFlags(c,slotlist)) ) return rc;
+			if ( (rc = enqueueGenericAndSecondStream(c,P)) ) return rc;
+		}
+		else
+		{
+			HIPCHK(hipMemsetAsync(c->d_work.p,0,WORK_WORDS*sizeof(uint32_t),s));
+			hipLaunchKernelGGL(k_window,dim3(c->win_grid),dim3(64),0,s,P.WB,c->d_err.p,static_cast<uint32_t const *>(0),(c->sched&2) ? c->d_work.p+WORK_GENERIC : static_cast<uint32_t *>(0));
+			mark(c,"k_window (all windows)");
+		}
+	}
+	HIPCHK(hipEventRecord(c->ev[2],s));
+	P.symbytes = 2*BP.npos + 64*BP.piles.size() + 64;
+	c->h_nfrag.resize(BP.piles.size()); c->h_frags.resize(BP.nfragslots+1); HIPCHK(c->h_outsym.ensure(P.symbytes));
+	if ( (rc = voteAndFetch(c,P)) ) return rc;
+	if ( (rc = fetchTierCounters(c)) ) return rc;
+	if ( (rc = scratchRetry(c,P)) ) return rc;
+	if ( (rc = fetchStageCounters(c)) ) return rc;
+	if ( (rc = assembleResults(c,P)) ) return rc;
+	eventTimes(c);
 	return DACC_OK;
 }
 
@@ -1114,7 +1107,7 @@ static int dacc_submit_piles_body(dacc_ctx * c, dacc_pile const * piles, uint64_
 			// 16 GB (config 2: 1.6 M hand-overs of 10 M windows).  DACC_HAND=0 switches the mechanism off (every hand-over restarts).
 			// The buffer is an optimisation for contexts that live: the driver clears device memory it hands out (16 GB = half a
 			// second on some boxes), which a single pass does not earn back, so the FIRST pass of a context runs without it and the
-			// buffer is allocated when the context is used again (runDevice).
+			// buffer is allocated when the context is used again (growHandOver).
 			uint64_t cap = BP.nwindows/3 + 4096; uint64_t const maxcap = (16ull<<30) / (static_cast<uint64_t>(TP.handwords)*8ull);
 			if ( cap > maxcap ) cap = maxcap;
 			if ( c->par.klow != c->par.khigh ) cap = 0;
@@ -1149,9 +1142,9 @@ static int dacc_submit_piles_body(dacc_ctx * c, dacc_pile const * piles, uint64_
 	HIPCHK(c->d_has.ensure(BP.npos+1)); HIPCHK(c->d_oc.ensure(BP.npos+1)); HIPCHK(c->d_ld0.ensure(BP.npos+1)); HIPCHK(c->d_ocs.ensure(BP.npos+1));
 	HIPCHK(c->d_outsym.ensure(2*BP.npos + 64*BP.piles.size() + 64));
 	HIPCHK(c->d_nfrag.ensure(BP.piles.size()+1)); HIPCHK(c->d_frags.ensure(BP.nfragslots+1)); HIPCHK(c->d_pilebad.ensure(BP.piles.size()+1));
-	hipEvent_t h2dend; hipEventCreate(&h2dend); hipEventRecord(h2dend,s);
+	hipEventRecord(c->h2dend,s);
 	rc = runDevice(c);
-	float ms = 0; hipEventElapsedTime(&ms,c->ev[5],h2dend); c->timing.h2d_ms = ms; hipEventDestroy(h2dend);
+	float ms = 0; hipEventElapsedTime(&ms,c->ev[5],c->h2dend); c->timing.h2d_ms = ms;
 	if ( rc ) return rc;
 	c->havebatch = true;
 	return DACC_OK;
@@ -1305,7 +1298,7 @@ int dacc_plan_only(dacc_params const * par, uint32_t const * rlen, uint64_t nrea
 
 //  a device ALLOCATION failure while the optional hand-over buffer is held (up to 16 GB) may be an allocation it
 // starved: give the buffer back and run the call once more without it -- the context keeps `nohand` set, so neither the planner of the
-// retried call nor runDevice's "second use" allocation brings the buffer back.  Other failures (a device fault, internal error
+// retried call nor growHandOver's "second use" allocation brings the buffer back.  Other failures (a device fault, internal error
 // flags, host allocation) are not retried: a second pass would only overwrite the first error's text.
 static bool dacc_drop_hand(dacc_ctx * c)
 {

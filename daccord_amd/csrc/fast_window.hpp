@@ -691,20 +691,20 @@ HDEV FastCaps fastCapsOf(uint32_t const nrows, uint32_t const nsup)
 struct FastBatch
 {
 	WindowBatch W;
-	FastCaps F;
-	uint64_t const * dpsq_vst;  // [nsup][nrows] transposed fixed-point table (HBM); copied to LDS as 32-bit
-	uint32_t * retry;           // [0] = count, [1..] = window indices for the next capacity tier
-	uint32_t * gearly;          // same layout: windows no LDS tier can run (w > 63, a string > 64): straight to the generic engine
-	uint8_t * gslab;            // gw tiers: global scratch, gstride bytes per workgroup (weights, spill of the build-phase arrays)
-	uint64_t gstride;
-	uint32_t const * tab32;     // gw tiers: [nsup+1][nrows+1] 32 bit copy of the fixed-point table, zero row / column at the end
+	FastCaps F = {};
+	uint64_t const * dpsq_vst = 0;  // [nsup][nrows] transposed fixed-point table (HBM); copied to LDS as 32-bit
+	uint32_t * retry = 0;           // [0] = count, [1..] = window indices for the next capacity tier
+	uint32_t * gearly = 0;          // same layout: windows no LDS tier can run (w > 63, a string > 64): straight to the generic engine
+	uint8_t * gslab = 0;            // gw tiers: global scratch, gstride bytes per workgroup (weights, spill of the build-phase arrays)
+	uint64_t gstride = 0;
+	uint32_t const * tab32 = 0;     // gw tiers: [nsup+1][nrows+1] 32 bit copy of the fixed-point table, zero row / column at the end
 	// round 4: hand-over without restart.  A window that overflows a tier's node table leaves its sorted k-mer instances and last k-mer
 	// list in a slot of this buffer (handwords 64 bit words per slot: header {npre, nlast}, instances, last k-mers); the tier that picks
 	// the window up loads them instead of generating and sorting them again.  hand == 0: every hand-over restarts from the strings.
-	uint64_t * hand; uint32_t * handctr; uint32_t handcap, handwords;
-	uint32_t feasneed;          // 0: stretch feasibility of every (stretch, direction, position), as before the filter (DACC_FEAS_NEED=0: A/B runs and tests)
+	uint64_t * hand = 0; uint32_t * handctr = 0; uint32_t handcap = 0, handwords = 0;
+	uint32_t feasneed = 1;          // the product default; 0: stretch feasibility of every (stretch, direction, position), as before the filter (DACC_FEAS_NEED=0: A/B runs and tests)
 #if defined(DACC_LEDGER)
-	uint32_t ledger;            // instruction ledger build (scripts/ledger.py): bit p set = phase p of every window runs twice
+	uint32_t ledger = 0;            // instruction ledger build (scripts/ledger.py): bit p set = phase p of every window runs twice
 #endif
 };
 

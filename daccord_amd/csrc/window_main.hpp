@@ -11,24 +11,25 @@
 
 namespace dacc {
 
+// (default member initialisers: a record a launch site does not fill completely is defined -- null, 0)
 struct WindowBatch
 {
-	DevParams P;
-	DevTables T;
-	ArenaCaps C;
+	DevParams P = {};
+	DevTables T = {};
+	ArenaCaps C = {};
 	// resident read store (.bps layout)
-	uint8_t const * bps; uint64_t const * boff; uint32_t const * rlen;
+	uint8_t const * bps = 0; uint64_t const * boff = 0; uint32_t const * rlen = 0;
 	// batch
-	DevPile const * piles; uint32_t npiles;
-	DevOvl const * ovl;
-	uint32_t const * wt_b; uint32_t const * wt_e;   // per (overlap, active window): B start / end offset
-	uint64_t nwindows;
+	DevPile const * piles = 0; uint32_t npiles = 0;
+	DevOvl const * ovl = 0;
+	uint32_t const * wt_b = 0; uint32_t const * wt_e = 0;   // per (overlap, active window): B start / end offset
+	uint64_t nwindows = 0;
 	// outputs
-	uint8_t * wrec;            // [nwindows][DACC_WREC_OF(w)]
-	WindowOut * wout;          // [nwindows]
-	uint8_t * arena;           // [gridDim][C.bytes]
-	uint64_t * prof;           // optional per-phase cycle counters (profiling builds)
-	uint32_t const * pregen;   // optional bit per window: already handed to the generic engine by the pre-scan (the LDS tiers skip it)
+	uint8_t * wrec = 0;            // [nwindows][DACC_WREC_OF(w)]
+	WindowOut * wout = 0;          // [nwindows]
+	uint8_t * arena = 0;           // [gridDim][C.bytes]
+	uint64_t * prof = 0;           // optional per-phase cycle counters (profiling builds)
+	uint32_t const * pregen = 0;   // optional bit per window: already handed to the generic engine by the pre-scan (the LDS tiers skip it)
 };
 
 // base i of read r in the orientation the overlap uses (HandleContext.hpp:1910, 1952)

@@ -23,17 +23,17 @@ using namespace dacc;
 
 struct EmulCtx
 {
-	dacc_params par;
+	dacc_params par = {};
 	HostTables H;
-	bool haveprofile;
-	double est_cor;
+	bool haveprofile = false;
+	double est_cor = 0;
 	std::vector<uint8_t> bps; std::vector<uint64_t> boff; std::vector<uint32_t> rlen;
 	std::vector<dacc_fragment> frags; std::string bases;
 	std::vector<dacc_window_result> windows;
 	std::string err;
-	bool usefast; uint64_t ntier[3], nretry, nlong, ntier0, ntier7, ntier10;
+	bool usefast = true; uint64_t ntier[3] = {0,0,0}, nretry = 0, nlong = 0, ntier0 = 0, ntier7 = 0, ntier10 = 0;
 	std::vector<uint64_t> glist;   // windows that went to the generic engine: index, flags of the last tier
-	uint64_t reasonsT[3][64]; uint64_t flagbitsT[3][24];
+	uint64_t reasonsT[3][64] = {}; uint64_t flagbitsT[3][24] = {};
 };
 
 // arena.hpp's guard sink (arenaGuardSink) is ONE pointer per process, and every arena_carve pushes its field offsets into whatever it
@@ -61,7 +61,7 @@ static void fillDev(EmulCtx & c, DevParams & P, DevTables & T)
 
 extern "C" {
 
-void * emul_create(dacc_params const * p) { EmulCtx * c = new EmulCtx; c->par = *p; c->haveprofile = false; c->est_cor = 0; c->usefast = true; c->ntier[0] = c->ntier[1] = c->ntier[2] = c->nretry = 0; c->nlong = 0; c->ntier0 = 0; c->ntier7 = 0; c->ntier10 = 0; return c; }
+void * emul_create(dacc_params const * p) { EmulCtx * c = new EmulCtx; c->par = *p; return c; }
 void emul_set_fast(void * v, int on) { static_cast<EmulCtx *>(v)->usefast = on; }
 void emul_reasons_tier(void * v, int t, uint64_t * r, uint64_t * fb) { EmulCtx * c = static_cast<EmulCtx *>(v); for ( int i = 0; i < 64; ++i ) r[i] = c->reasonsT[t][i]; for ( int i = 0; i < 24; ++i ) fb[i] = c->flagbitsT[t][i]; }
 void emul_reasons2(void * v, uint64_t * r, uint64_t * fb) { emul_reasons_tier(v,1,r,fb); }
@@ -217,7 +217,7 @@ int emul_run(void * v, dacc_pile const * piles, uint64_t npiles, dacc_overlap co
 		WindowBatch WB;
 		WB.P = P; WB.T = T; WB.C = caps; WB.bps = c->bps.data(); WB.boff = c->boff.data(); WB.rlen = c->rlen.data();
 		WB.piles = BP.piles.data(); WB.npiles = BP.piles.size(); WB.ovl = BP.ovl.data(); WB.wt_b = wt_b.data(); WB.wt_e = wt_e.data();
-		WB.nwindows = BP.nwindows; WB.wrec = wrec.data(); WB.wout = wout.data(); WB.arena = arena.data(); WB.prof = 0; WB.pregen = 0;
+		WB.nwindows = BP.nwindows; WB.wrec = wrec.data(); WB.wout = wout.data(); WB.arena = arena.data();
 		// the chain of LDS tiers as the library resolves it (tier_pipeline.hpp: the same switches, gates and stages as capi.hip)
 		TierSwitches const sw = readTierSwitches();
 		bool big = false; for ( size_t i = 0; i < c->H.dpsq_vst.size(); ++i ) if ( c->H.dpsq_vst[i] >> 32 ) big = true;
@@ -265,7 +265,7 @@ int emul_run(void * v, dacc_pile const * piles, uint64_t npiles, dacc_overlap co
 			if ( !TP.ok[i] ) continue;
 			TierStage const & st = TIER_CHAIN[i]; FastBatch & F = FB[i];
 			bool const second = st.role == ROLE_LONG;      // the second stream's tier: every window of its list, no slab, no hand-over slots
-			F.W = WB; F.F = BP.stageCaps(i); F.dpsq_vst = c->H.dpsq_vst.data(); F.retry = 0; F.gearly = 0; F.gstride = 0; F.tab32 = c->H.tab32.data();
+			F.W = WB; F.F = BP.stageCaps(i); F.dpsq_vst = c->H.dpsq_vst.data(); F.tab32 = c->H.tab32.data();
 			if ( second || (st.slot > 0 && TP.late_long) || TP.widetier ) F.W.pregen = second ? 0 : pregen2.data();
 			gslab[i].assign(second ? 0 : F.F.gbytes+64,arenafill); F.gslab = second ? 0 : gslab[i].data();
 			F.hand = (usehand && !second) ? hand.data() : 0; F.handctr = second ? 0 : &handctr; F.handcap = F.hand ? static_cast<uint32_t>(BP.nwindows) : 0u; F.handwords = second ? 0u : TP.handwords;
