@@ -803,6 +803,7 @@ static int fetchTierCounters(dacc_ctx * c)
 	c->timing.tier10_out = 0;
 	if ( fD ) HIPCHK(hipMemcpy(&c->timing.tier10_out,fD->handon.p,sizeof(uint32_t),hipMemcpyDeviceToHost));
 	c->timing.tier0_in = 0; c->timing.tier0_out = 0; c->timing.tier7_in = 0; c->timing.tier7_out = 0;
+	c->timing.long_windows = 0; c->timing.long_first_tier = 0;      // (a pass that does not get to the second stream ran nothing there)
 	if ( !(TP.usefast && BP.nwindows && TP.anytier()) ) return DACC_OK;
 	// length of the two lists of the second stream (pre-scan, first tier's generic-only windows), fetched before their launches
 	uint32_t const n1 = c->nlong[0], n2 = c->nlong[1];
@@ -964,10 +965,13 @@ static int runDevice(dacc_ctx * c)
 	growHandOver(c);
 	++c->nruns;
 	if ( (rc = enqueuePrepAndTrace(c)) ) return rc;
+	// the run state of the stages and of the second stream is this pass's alone: a pass without windows launches none of them, and the counter and time
+	// fetches behind it must not see what the pass before it ran (nor read the lists it kept)
+	for ( dacc_ctx::Stage & S : c->st ) { S.ran = false; S.in = 0; }
+	c->nlong[0] = c->nlong[1] = 0; c->longran[0] = c->longran[1] = false;
 	if ( BP.nwindows )
 	{
 		P.WB = windowBatch(c);
-		for ( dacc_ctx::Stage & S : c->st ) S.ran = false;
 		// no LDS tier usable (DACC_TIERS=0 or a model table no tier's overlay holds): everything runs in the generic engine on
 		// the main stream; the pre-scan / second stream would hand the same windows to two kernels
 		if ( TP.usefast && TP.anytier() )

@@ -34,6 +34,7 @@ struct EmulCtx
 	bool usefast = true; uint64_t ntier[3] = {0,0,0}, nretry = 0, nlong = 0, ntier0 = 0, ntier7 = 0, ntier10 = 0;
 	std::vector<uint64_t> glist;   // windows that went to the generic engine: index, flags of the last tier
 	uint64_t reasonsT[3][64] = {}; uint64_t flagbitsT[3][24] = {};
+	BatchPlan BP;                  // emul_plan_digest_reused: one planner object for the life of the context, like dacc_ctx::BP (emul_run plans into a fresh one)
 };
 
 // arena.hpp's guard sink (arenaGuardSink) is ONE pointer per process, and every arena_carve pushes its field offsets into whatever it
@@ -101,12 +102,8 @@ int emul_load_db(void * v, uint8_t const * bps, uint64_t nb, uint64_t const * bo
 // FNV-1a over everything BatchPlan::plan produces (tests/test_plan.py: the plan of a batch is a pure function of its input, and its
 // digest for a set of inputs -- malformed piles included -- is committed; a faster planner must reproduce it)
 static void fnv(uint64_t & h, void const * p, size_t n) { uint8_t const * b = static_cast<uint8_t const *>(p); for ( size_t i = 0; i < n; ++i ) { h ^= b[i]; h *= 1099511628211ull; } }
-uint64_t emul_plan_digest(void * v, dacc_pile const * piles, uint64_t npiles, dacc_overlap const * ovl, uint64_t novl, void const * trace, uint64_t ntrace, int trace_bytes, int * rcout)
+static uint64_t planDigest(BatchPlan & BP, int const rc, std::string const & err)
 {
-	EmulCtx * c = static_cast<EmulCtx *>(v);
-	BatchPlan BP; std::string err;
-	int const rc = BP.plan(c->par,piles,npiles,ovl,novl,trace,ntrace,trace_bytes,c->rlen.data(),c->rlen.size(),err,c->H.nrows,c->H.nsup);
-	if ( rcout ) *rcout = rc;
 	uint64_t h = 1469598103934665603ull;
 	fnv(h,&rc,sizeof(rc)); fnv(h,err.data(),err.size());
 	if ( rc ) return h;
@@ -121,6 +118,25 @@ uint64_t emul_plan_digest(void * v, dacc_pile const * piles, uint64_t npiles, da
 	if ( BP.pile_status.size() ) fnv(h,BP.pile_status.data(),BP.pile_status.size()*sizeof(int32_t));
 	for ( size_t i = 0; i < BP.pile_errors.size(); ++i ) { fnv(h,BP.pile_errors[i].data(),BP.pile_errors[i].size()); fnv(h,"|",1); }
 	return h;
+}
+uint64_t emul_plan_digest(void * v, dacc_pile const * piles, uint64_t npiles, dacc_overlap const * ovl, uint64_t novl, void const * trace, uint64_t ntrace, int trace_bytes, int * rcout)
+{
+	EmulCtx * c = static_cast<EmulCtx *>(v);
+	BatchPlan BP; std::string err;
+	int const rc = BP.plan(c->par,piles,npiles,ovl,novl,trace,ntrace,trace_bytes,c->rlen.data(),c->rlen.size(),err,c->H.nrows,c->H.nsup);
+	if ( rcout ) *rcout = rc;
+	return planDigest(BP,rc,err);
+}
+// the same digest of a plan made by the context's OWN BatchPlan, which lives as long as the context and has planned whatever this entry was given before
+// (dacc_ctx::BP is one object for the life of a context: a plan must not depend on the batches planned into the object before it).  The error text
+// starts empty like emul_plan_digest's; emul_load_db and emul_set_error_profile may be called between two plans
+uint64_t emul_plan_digest_reused(void * v, dacc_pile const * piles, uint64_t npiles, dacc_overlap const * ovl, uint64_t novl, void const * trace, uint64_t ntrace, int trace_bytes, int * rcout)
+{
+	EmulCtx * c = static_cast<EmulCtx *>(v);
+	std::string err;
+	int const rc = c->BP.plan(c->par,piles,npiles,ovl,novl,trace,ntrace,trace_bytes,c->rlen.data(),c->rlen.size(),err,c->H.nrows,c->H.nsup);
+	if ( rcout ) *rcout = rc;
+	return planDigest(c->BP,rc,err);
 }
 
 // host planning of a batch alone (BatchPlan::plan, what dacc_submit_piles does before any upload): seconds of `reps` runs

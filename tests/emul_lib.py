@@ -113,6 +113,17 @@ class Emul:
         bps = np.ascontiguousarray(bps); boff = np.ascontiguousarray(boff); rlen = np.ascontiguousarray(rlen)
         self.L.emul_load_db(self.h, _ptr(bps), len(bps), _ptr(boff), _ptr(rlen), len(rlen))
 
+    def plan_digest(self, piles, ovl, trace, trace_bytes=1, reused=False):
+        """(digest, return code) of BatchPlan::plan for a batch (tests/test_plan.py).  reused: planned by the context's own BatchPlan, which has
+        planned every batch this was called with before (dacc_ctx::BP lives as long as its context), instead of by a fresh one."""
+        f = self.L.emul_plan_digest_reused if reused else self.L.emul_plan_digest
+        f.restype = C.c_uint64
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_int)]
+        piles = np.ascontiguousarray(piles); ovl = np.ascontiguousarray(ovl); trace = np.ascontiguousarray(trace)
+        rc = C.c_int(0)
+        h = f(self.h, _ptr(piles), len(piles), _ptr(ovl), len(ovl), _ptr(trace), trace.nbytes // trace_bytes, trace_bytes, C.byref(rc))
+        return "%016x" % h, rc.value
+
     def run(self, piles, ovl, trace, trace_bytes=1):
         piles = np.ascontiguousarray(piles); ovl = np.ascontiguousarray(ovl); trace = np.ascontiguousarray(trace)
         rc = self.L.emul_run(self.h, _ptr(piles), len(piles), _ptr(ovl), len(ovl), _ptr(trace), len(trace), trace_bytes)

@@ -110,6 +110,64 @@ def test_plan_with_sixteen_threads_that_really_run():
     assert serial == par16 == unset == many and serial[1] == 0, (serial, par16, unset, many)
 
 
+_REUSE = ["S1", "D50", "M", "Z", "malformed"]
+_reuse_batches = {}
+_reuse_fresh = {}
+
+
+def _reuse_batch(name):
+    """(data set, piles, overlaps, trace, bytes per trace value, error profile) of a batch of the reuse pairs: the steps of tests/lifecycle_cases.py
+    (shallow, deep chain, very deep pile, no overlaps) and this file's batch with malformed and empty piles"""
+    if name not in _reuse_batches:
+        if name == "malformed":
+            kw, d, ovl, piles, trace = [c for c in _cases() if c[0] == "narrow_k8_malformed"][0][1:]
+            _reuse_batches[name] = (d, piles, ovl, trace, d.trace_bytes, tuple(d.error_profile()))
+        else:
+            import lifecycle_cases as LF
+            s = LF.step(name)
+            _reuse_batches[name] = (s.d, s.piles, s.ovl, s.trace, s.trace_bytes, s.profile)
+    return _reuse_batches[name]
+
+
+def _reuse_plan(E, name, reused):
+    d, piles, ovl, trace, tb, prof = _reuse_batch(name)
+    E.set_error_profile(*prof); E.load_db(d.bps, d.boff, d.rlen)
+    return E.plan_digest(piles, ovl, trace, tb, reused=reused)
+
+
+@pytest.mark.parametrize("second", _REUSE)
+@pytest.mark.parametrize("first", _REUSE)
+def test_plan_does_not_depend_on_what_the_planner_object_planned_before(first, second):
+    """dacc_ctx::BP is ONE BatchPlan for the life of a context, emul_plan_digest plans into a fresh one every time: here batch `second` is planned by
+    the object that has planned batch `first` (another data set, another chain, more or fewer piles, dropped piles and their messages) and must give
+    the digest a fresh object gives.  All at k = 14, the parameters of the narrow context of tests/lifecycle_cases.py."""
+    p = default_params(k=14)
+    if second not in _reuse_fresh:
+        _reuse_fresh[second] = _reuse_plan(emul_lib.Emul(p), second, False)
+    E = emul_lib.Emul(p)
+    h1 = _reuse_plan(E, first, True)
+    h2 = _reuse_plan(E, second, True)
+    assert h1[1] == 0 and h2[1] == 0
+    assert h2 == _reuse_fresh[second], (first, second, h2, _reuse_fresh[second])
+    if first != second:
+        assert h1 != h2      # (the digest tells the batches apart)
+
+
+def test_reuse_batches_are_what_they_are_meant_to_be():
+    """the malformed batch drops piles and says so, Z has no window: the premises of the pairs above"""
+    p = default_params(k=14)
+    good = [c for c in _cases() if c[0] == "narrow_k8"][0]
+    d, piles, ovl, trace, tb, prof = _reuse_batch("malformed")
+    assert good[2] is d and int((good[4]["novl"] != piles["novl"]).sum()) == 1      # the same piles, one emptied by hand, five more malformed
+    E = emul_lib.Emul(p); E.set_error_profile(*prof); E.load_db(d.bps, d.boff, d.rlen)
+    hg = E.plan_digest(good[4], good[3], good[5], tb)
+    hm = E.plan_digest(piles, ovl, trace, tb)
+    assert hg[1] == 0 and hm[1] == 0 and hg[0] != hm[0]
+    E = emul_lib.Emul(p); d, piles, ovl, trace, tb, prof = _reuse_batch("Z"); E.set_error_profile(*prof); E.load_db(d.bps, d.boff, d.rlen)
+    fe, be = E.run(piles, ovl, trace, tb)
+    assert len(E.windows()) == 0 and len(fe) == 0 and be == b""
+
+
 def test_plan_has_no_data_race(tmp_path):
     """the planner's threads under ThreadSanitizer (tests/emul/plan_tsan.cpp): no report, one digest for 1 / 8 / 3 / 16 threads;
     an exception in a worker is rethrown in the caller after the join"""
