@@ -49,10 +49,17 @@ class DaccTiming(C.Structure):
 
 
 class DaccTimingLong(C.Structure):
-    """dacc_timing as it is since the long string stage: DaccTiming (176 bytes, unchanged) and the 16 bytes appended behind emit_ms"""
+    """dacc_timing as it was with the long string stage: DaccTiming (176 bytes, unchanged) and the 16 bytes appended behind emit_ms"""
     _fields_ = DaccTiming._fields_ + [
         # the long string stage (k_window_fast<17>: strings of 129 ... 255 bases, second stream of a wide batch, in front of the generic engine there)
         ("longstr_ms", C.c_float), ("longstr_windows", C.c_uint32), ("longstr_out", C.c_uint32), ("pad2_", C.c_uint32)]
+
+
+class DaccTimingFull(C.Structure):
+    """dacc_timing as it is since the full-depth stage: DaccTimingLong (192 bytes, unchanged) and the 16 bytes appended behind pad2_"""
+    _fields_ = DaccTimingLong._fields_ + [
+        # the full-depth stage (k_window_fast<18>: windows of 2001 ... 5001 strings, behind the deepest stage and in front of k_window)
+        ("fdeep_ms", C.c_float), ("fdeep_windows", C.c_uint32), ("fdeep_out", C.c_uint32), ("pad3_", C.c_uint32)]
 
 
 TIMING_SIZE_V1 = 128

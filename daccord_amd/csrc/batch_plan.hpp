@@ -61,7 +61,7 @@ struct BatchPlan
 	std::vector<std::string> pile_errors;     // first messages of dropped piles
 	ArenaCaps caps;
 	// LDS fast path: capacities of the stages of the tier chain (tier_pipeline.hpp), by TierId
-	FastCaps stage[TIER_NSTAGES];
+	FastCaps stage[TIER_NROWS];
 	FastCaps & stageCaps(uint32_t const id) { return stage[id]; }
 	// strings of the deepest window of the batch: the A window and its active overlaps (maxdepth), capped by -d like the kernels' mao
 	uint32_t maxstrings(dacc_params const & par) const { uint64_t const nb = par.maxalign > 0 ? static_cast<uint64_t>(par.maxalign-1) : 0; return 1u + static_cast<uint32_t>(std::min<uint64_t>(maxdepth,nb)); }
@@ -326,7 +326,7 @@ struct BatchPlan
 		deep = 2*ndeepwin > nwindows;
 		// (round 6) wide windows: tier 8 (second slot, no hand-over list in front of it = all windows), tier 9, then the generic engine
 		wide = par.w > 63 && par.w <= 127;
-		for ( uint32_t i = 0; i < TIER_NSTAGES; ++i ) stageCaps(i) = tierCaps(stageTier(TIER_CHAIN[i],deep,wide),tab_nrows,tab_nsup);
+		for ( uint32_t i = 0; i < TIER_NROWS; ++i ) stageCaps(i) = tierCaps(stageTier(TIER_CHAIN[i],deep,wide),tab_nrows,tab_nsup);
 		return DACC_OK;
 	}
 };

@@ -483,14 +483,15 @@ static int dacc_load_db_body(dacc_ctx * c, uint8_t const * bps, uint64_t bps_byt
 // dacc_timing's counters of the stages that pass on untouched what is not theirs, in chain order.  `deeper`: the stage's own share are the windows of more than
 // `mins` strings on the list it read (windows + out) and on the list it handed on (out), counted by k_count_deeper into two words of d_work from the final
 // window records (behind the scratch retries of the generic engine); else everything on its list is its own: the difference of the two list lengths -- what the
-// last stage handed on is what k_window ran, or what the very deep stage read.  The deepest stage counts with the very deep stage's threshold: what it read with
-// more than VDEEP_MINS strings is vdeep_out where that stage ran.  `ms`: a trailing stage's kernel time (the deep-window tier's has a start event of its own)
+// last stage handed on is what k_window ran, or what the very deep stage read.  The deepest stage and the full-depth stage count with the very deep stage's threshold:
+// what the deepest stage read with more than VDEEP_MINS strings is vdeep_out where that stage ran, what the full-depth stage read is xdeep_out where the deepest ran.  `ms`: a trailing stage's kernel time (the deep-window tier's has a start event of its own)
 struct StageCounters { TierId id; float dacc_timing::* ms; uint32_t dacc_timing::* windows, dacc_timing::* out; bool deeper; uint32_t mins, countwords; };
 static StageCounters const STAGE_COUNTERS[] = {
 	{ ID_DEEP, nullptr, &dacc_timing::deep_windows, &dacc_timing::deep_out, true, FastTier<12>::mins, WORK_DEEP_COUNT },
 	{ ID_LAST, &dacc_timing::last_ms, &dacc_timing::last_windows, &dacc_timing::last_out, false, 0, 0 },
 	{ ID_VDEEP, &dacc_timing::vdeep_ms, &dacc_timing::vdeep_windows, &dacc_timing::vdeep_out, true, VDEEP_MINS, WORK_VDEEP_COUNT },
-	{ ID_XDEEP, &dacc_timing::xdeep_ms, &dacc_timing::xdeep_windows, &dacc_timing::xdeep_out, true, VDEEP_MINS, WORK_XDEEP_COUNT } };
+	{ ID_XDEEP, &dacc_timing::xdeep_ms, &dacc_timing::xdeep_windows, &dacc_timing::xdeep_out, true, VDEEP_MINS, WORK_XDEEP_COUNT },
+	{ ID_FDEEP, &dacc_timing::fdeep_ms, &dacc_timing::fdeep_windows, &dacc_timing::fdeep_out, true, VDEEP_MINS, WORK_FDEEP_COUNT } };
 
 // ---- the device pass (runDevice): one function per phase, in the order they run; they share the context and the state of the pass
 // DACC_DEBUG_SYNC=1: wait for every kernel of the generic-only path and say so on stderr (a device fault then names its kernel)
@@ -661,7 +662,7 @@ static int enqueueSlot(dacc_ctx * c, Pass & P, uint32_t const slot)
 static int enqueueTrailingStages(dacc_ctx * c, Pass & P)
 {
 	TierPipeline & TP = c->TP; hipStream_t const s = c->stream;
-	for ( uint32_t i = 0; i < TIER_NSTAGES; ++i )
+	for ( uint32_t i = 0; i < TIER_NROWS; ++i )
 		if ( TIER_CHAIN[i].role == ROLE_LAST && TP.ok[i] && P.list && P.lastslot >= 0 )
 		{
 			dacc_ctx::Stage & S = c->st[i];
@@ -884,7 +885,7 @@ static int fetchStageCounters(dacc_ctx * c)
 		if ( K.ms ) { float sms = 0; hipEventElapsedTime(&sms,from,S.done); c->timing.*K.ms = sms; from = S.done; }
 	}
 	// the long string stage (wide batches, second stream): what it read is what the second stream read (long_windows), what it handed on is what k_window_long ran
-	c->timing.longstr_ms = 0; c->timing.longstr_windows = 0; c->timing.longstr_out = 0; c->timing.pad2_ = 0;
+	c->timing.longstr_ms = 0; c->timing.longstr_windows = 0; c->timing.longstr_out = 0; c->timing.pad2_ = 0; c->timing.pad3_ = 0;
 	if ( !(TP.usefast && BP.nwindows && TP.anytier()) ) c->longran[0] = c->longran[1] = false;
 	for ( int i = 0; i < 2; ++i )
 		if ( c->longran[i] )
@@ -1077,14 +1078,14 @@ static int dacc_submit_piles_body(dacc_ctx * c, dacc_pile const * piles, uint64_
 	bool fits32 = true;
 	for ( size_t i = 0; i < c->H.dpsq_vst.size(); ++i ) if ( c->H.dpsq_vst[i] >> 32 ) fits32 = false; // table must fit 32 bits
 	// which LDS tiers this batch runs (tier_pipeline.hpp); none: the generic engine alone
-	c->TP = resolveTiers(c->sw,!c->sw.nofast && fits32,BP.deep,BP.wide,c->H.nrows,c->H.nsup,c->par.w,[&](uint32_t const id) -> FastCaps & { return BP.stageCaps(id); },BP.maxstrings(c->par));
+	c->TP = resolveTiers(c->sw,!c->sw.nofast && fits32,BP.deep,BP.wide,c->H.nrows,c->H.nsup,c->par.w,[&](uint32_t const id) -> FastCaps & { return BP.stageCaps(id); },BP.maxstrings(c->par),TIER_NROWS);
 	TierPipeline const & TP = c->TP;
 	if ( TP.usefast )
 	{
 		for ( int t = 0; t < TIER_NSLOTS; ++t ) HIPCHK(c->d_retry[t].ensure(BP.nwindows+2));
 		// the stages of the chain: launch geometry, hand-on lists of the front tiers (and the pre-pass's list of small windows), global slab
 		// of the gw tiers (weights, spill): one per workgroup, the tiers run one after the other and share the buffer
-		for ( uint32_t i = 0; i < TIER_NSTAGES; ++i )
+		for ( uint32_t i = 0; i < TIER_NROWS; ++i )
 		{
 			FastCaps const & F = BP.stageCaps(i);
 			c->st[i].grid = F.gmem ? tierGridGmem(F.gbytes,BP.nwindows) : tierGrid(F.ldsbytes,BP.nwindows);
@@ -1175,7 +1176,7 @@ void dacc_release(dacc_ctx * c) { if ( c ) { c->frags.clear(); c->bases.clear();
 // dacc_last_timing: the record as it was when the call got its signature (everything in front of deep_ms), so that a caller compiled against
 // that header is not overrun; dacc_last_timing2 copies as much of today's record as the caller says it has room for
 static_assert(offsetof(dacc_timing,deep_ms) == DACC_TIMING_SIZE_V1,"dacc_last_timing fills the record in front of deep_ms");
-static_assert(offsetof(dacc_timing,vdeep_ms) == 160 && offsetof(dacc_timing,longstr_ms) == DACC_TIMING_SIZE_V2 && DACC_TIMING_SIZE_V2 == 176 && sizeof(dacc_timing) == 192,"the very deep stage's fields are appended behind last_*, the long string stage's 16 bytes behind emit_ms");
+static_assert(offsetof(dacc_timing,vdeep_ms) == 160 && offsetof(dacc_timing,longstr_ms) == DACC_TIMING_SIZE_V2 && DACC_TIMING_SIZE_V2 == 176 && offsetof(dacc_timing,fdeep_ms) == DACC_TIMING_SIZE_V3 && DACC_TIMING_SIZE_V3 == 192 && sizeof(dacc_timing) == 208,"the very deep stage's fields are appended behind last_*, the long string stage's 16 bytes behind emit_ms, the full-depth stage's 16 bytes behind those");
 static_assert(offsetof(dacc_timing,xdeep_ms) == 140 && offsetof(dacc_timing,xdeep_windows) == 156 && offsetof(dacc_timing,xdeep_out) == 124,"the deepest stage's fields take the pad words: the record keeps its size");
 static_assert(offsetof(dacc_timing,emit_ms) == 172,"emit_ms is the last word of the first 176 bytes, where the very deep stage's pad word was");
 int dacc_last_timing(dacc_ctx * c, dacc_timing * t)
@@ -1188,8 +1189,9 @@ int dacc_last_timing2(dacc_ctx * c, dacc_timing * t, size_t size)
 {
 	if ( !c || !t ) return DACC_EINVAL;
 	// the long string stage's 16 bytes behind emit_ms go only to a caller that has room for all of them: a caller built with the 176 byte record that
-	// passes a larger size (its record inside a larger buffer) gets the 176 bytes it knows, as before the record grew
-	size_t const n = size >= sizeof(dacc_timing) ? sizeof(dacc_timing) : (size < DACC_TIMING_SIZE_V2 ? size : static_cast<size_t>(DACC_TIMING_SIZE_V2));
+	// passes a larger size (its record inside a larger buffer) gets the 176 bytes it knows, as before the record grew; the full-depth stage's 16 bytes behind
+	// those follow the same rule: a size in [192, 208) copies 192 bytes
+	size_t const n = size >= sizeof(dacc_timing) ? sizeof(dacc_timing) : (size >= DACC_TIMING_SIZE_V3 ? static_cast<size_t>(DACC_TIMING_SIZE_V3) : (size < DACC_TIMING_SIZE_V2 ? size : static_cast<size_t>(DACC_TIMING_SIZE_V2)));
 	std::memcpy(static_cast<void *>(t),&c->timing,n);
 	return DACC_OK;
 }

@@ -104,7 +104,7 @@ struct Context
 	// A main tier hands on through d_retry[slot] and is done at evslot[slot]; `handon` and `done` are those of the front tiers and of the trailing stages.
 	// `slab`: a trailing stage's own slab (layout included; the kernels' grids differ), allocated by the first batch the stage is resolved for.
 	TierSwitches sw = {}; TierPipeline TP = {};
-	struct Stage { bool ran = false; uint32_t grid = 0; DevBuf<uint32_t> handon; DevBuf<uint8_t> slab; Event done; uint32_t const * in = 0; /* the list it read in the last pass */ } st[TIER_NSTAGES];
+	struct Stage { bool ran = false; uint32_t grid = 0; DevBuf<uint32_t> handon; DevBuf<uint8_t> slab; Event done; uint32_t const * in = 0; /* the list it read in the last pass */ } st[TIER_NROWS];
 	uint32_t nlong[2] = {0,0};      // windows on the two lists of the second stream in the current pass (pre-scan, first tier's generic-only windows)
 	bool longran[2] = {false,false}; Event evLong[4];      // the long string stage (tier 17): did it run over list i in the current pass, and the events around its two launches on the second stream
 	// launch geometry: set by every batch (dacc_submit_piles); a generic-only batch (DACC_NOFAST, w >= 64, a model table no tier holds) reads retry_grid in its scratch retry

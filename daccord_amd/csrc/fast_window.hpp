@@ -30,7 +30,7 @@
  *  - stretches are looked up by first / last node through small index arrays, the weights of a feasible (stretch,
  *    position) entry carry the weights of its end nodes, candidates are kept as stretch sequences and decoded once.
  *
- * The same code is instantiated for eighteen capacity tiers (FastTier<N> below; the layout FastLds<CT> is a compile time constant,
+ * The same code is instantiated for nineteen capacity tiers (FastTier<N> below; the layout FastLds<CT> is a compile time constant,
  * so every LDS access has an immediate offset).  Which of them a batch runs, in which order and behind which switches, is
  * written down once, in tier_pipeline.hpp.
  *
@@ -53,6 +53,7 @@
  *     15  very deep stage, shallow and deep: 251 ... 1000 strings     gw      16 / 16 bit       no LDS
  *     16  deepest stage, shallow and deep: 1001 ... 2000 strings      gw      16 / 16 bit       no LDS
  *     17  second stream, wide batches: strings of 129 ... 255 bases   gw      16 / 16 bit       no LDS
+ *     18  full-depth stage, shallow and deep: 2001 ... 5001 strings   gw      16 / 16 bit       no LDS
  *
  * processWindowFast returns
  * FW_NEXT when a window overflows a tier (flags say what overflowed: 1 instances, 2 nodes, 8 candidates, 16 walk,
@@ -187,7 +188,7 @@ template<> struct FastTier<12> { typedef uint16_t id_t; typedef uint16_t sid_t; 
 //  - reverse pool: 4096 paths in 256 chunks of 16 (8 bit chunk ids kept: tier 3 has 256 chunks of 8, so an enumeration needs at most as many chunks here);
 //  - 16 bit weight offsets and task offsets kept: 16384 weight records per direction, at most 65535 (stretch, direction, position) tasks per traversal;
 //  - more than 4094 nodes: the stretch sort key takes 13 bit node fields and a 12 bit stretch number (FastEngine: KF, QB).
-// Windows of more than 250 strings go on to tiers 15 and 16; wider than 127 bases or with a string of more than 128 bases they still go to the generic engine.
+// Windows of more than 250 strings go on to tiers 15, 16 and 18; wider than 127 bases or with a string of more than 128 bases they still go to the generic engine.
 template<> struct FastTier<13> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 2000, gw = 1, wcapg = 16384, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 250, precap = 16384, ncap = 4096, scap = 2048, lcap = 8192, wcap = 16384, rccap = 4096, fcap = 1024, siqcap = 512, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 4096, wide = 0, mins = 0, gmem = 1 }; };
 template<> struct FastTier<14> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 1000, gw = 1, wcapg = 16384, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 250, precap = 16384, ncap = 6144, scap = 1024, lcap = 8192, wcap = 16384, rccap = 4096, fcap = 2048, siqcap = 512, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 4096, wide = 1, mins = 0, gmem = 1 }; };
 // tier 15: the VERY DEEP stage, behind the last stage and in front of the generic engine (tier_pipeline.hpp: ID_VDEEP): windows of 251 ... 1000 strings
@@ -226,6 +227,24 @@ static_assert(FastTier<15>::mins == VDEEP_MINS && FastTier<13>::maxs == VDEEP_MI
 // whole scratch (lscrids = 4096 ids), which holds every path of the pool (rccap = 4096), so it never sends a window on by itself.
 template<> struct FastTier<16> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 4000, gw = 1, wcapg = 65536, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 8000, rpstcap = 768, lstr = 128, maxs = 2000, precap = 16384, ncap = 8190, scap = 4096, lcap = 16384, wcap = 65536, rccap = 4096, fcap = 1024, siqcap = 512, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 4096, wide = 0, mins = 250, gmem = 1 }; };
 static_assert(FastTier<16>::mins == VDEEP_MINS && FastTier<15>::maxs == XDEEP_MINS,"the deepest stage takes what the very deep stage hands on with more than 250 strings");
+// tier 18: the FULL-DEPTH stage, behind the deepest stage and in front of the generic engine (tier_pipeline.hpp: ID_FDEEP): windows of 2001 ... 5001 strings
+// -- 5001 is the deepest window a default run submits (-D 5000 overlaps and the A read) -- and the windows of 251 ... 2000 strings that overflowed one of
+// tier 16's tables (mins = 250).  Tier 16's code with twice its node table and capacities sized on the emulation (tests/fdeep_cases.py): 16384 nodes,
+// 12288 stretches, 49152 links, 12000 pool stretches, 131072 weight records per direction -- at k = 8 the deepest pile of a default run needs 9005 stretches
+// and 121390 forward records.  What a string
+// count above 2048 widens (FastLds<CT>::ywides, all other tiers keep their fields bit for bit):
+//  - compact string list: 13 bit string id | 18 bit first slot;
+//  - 262144 k-mer instances (icap = 16 x precap) as 256 ranges by the first FOUR symbols of the k-mer (k >= 4; a window at k = 3 is handed on), every range
+//    sorted with the sort of precap = 16384 keys;
+//  - stretch sort key: 15 bit node fields (FastEngine: KF).  The base sort orders (first, ext) and the stretch number alone -- two stretches that share
+//    (first, ext) send the window on, so length and last node never decide an order that is kept --: 15 + 15 + 14 bits.  The pool key keeps its four
+//    fields, 60 bits, and carries no stretch number;
+//  - key tables (mfirst, mlast, lastk) of 8192 entries, 80016 candidate error bytes, 79 chunks of 64 strings in the instance generation.
+//  - the four words per (stretch, direction) unit of the stretch feasibility live in device memory (the bytes of pregen), not in 4 x 384 registers.
+// Node frequencies stay capped at fqmax = 4095, so the weight widths are tier 16's.  Node ids, stretch ids and link offsets stay 16 bit words: 16384 nodes,
+// 12288 stretches and 49152 links are below 65535 (0xFFFF stays "none").
+template<> struct FastTier<18> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 12000, gw = 1, wcapg = 131072, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 24000, rpstcap = 768, lstr = 128, maxs = 5001, precap = 16384, ncap = 16384, scap = 12288, lcap = 49152, wcap = 131072, rccap = 4096, fcap = 1024, siqcap = 512, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 4096, wide = 0, mins = 250, gmem = 1 }; };
+static_assert(FastTier<18>::mins == VDEEP_MINS && FastTier<16>::maxs == FDEEP_MINS,"the full-depth stage takes what the deepest stage hands on with more than 250 strings");
 // tier 17: the LONG STRING stage of wide batches, on the second stream in front of the generic engine there (tier_pipeline.hpp: ID_LONG): the windows the
 // pre-scan set aside because a B string has more than 128 bases.  Tier 14 with a string stride of 256: FOUR 64 bit words per pattern mask (FastLds<CT>::pw),
 // strings of up to 255 bases -- the lengths and positions of a string are bytes (slen, ipos, irpos, canderr) --, a longer one is FFAIL(4) = FW_GENERIC and
@@ -263,7 +282,7 @@ struct FastLds<CT,false>
 {
 	LDSQ uint8_t * base;
 	static constexpr uint32_t keycap = fcpow2(CT::maxs < 2 ? 2 : CT::maxs);
-	typedef uint16_t toff_t; static constexpr bool wides = false, xwides = false; static constexpr uint32_t fqmax = 255u, icap = CT::precap;      // (more than 256 strings: gw layout only)
+	typedef uint16_t toff_t; static constexpr bool wides = false, xwides = false, ywides = false; static constexpr uint32_t fqmax = 255u, icap = CT::precap;      // (more than 256 strings: gw layout only)
 	static_assert(CT::maxs <= 256,"the legacy layout has 8 bit node frequencies and string ids");
 	static_assert((CT::precap & (CT::precap-1)) == 0,"precap must be a power of two: the bitonic sorts pad to one");
 	static_assert(sizeof(typename CT::id_t) > 1 || (CT::fcap <= 256 && CT::rccap <= 256),"pool slots are recorded as id_t (pout)");
@@ -481,10 +500,12 @@ struct FastLds<CT,true>
 	static constexpr bool wides = CT::maxs > 256;
 	// more than 1024 strings (tier 16): node frequencies up to 4095, 64 instance ranges, 32 bit task offsets
 	static constexpr bool xwides = CT::maxs > 1024;
+	// more than 2048 strings (tier 18): 256 instance ranges, 15 bit node fields in the stretch sort key
+	static constexpr bool ywides = CT::maxs > 2048;
 	static constexpr uint32_t fqmax = xwides ? 4095u : (wides ? 1023u : 255u);
 	// k-mer instances the layout holds: precap, the capacity of one instance sort -- with more than 256 strings four such ranges, with more than
-	// 1024 strings 64 ranges that share eight times precap (buildInstances)
-	static constexpr uint32_t icap = xwides ? 8u*CT::precap : (wides ? 4u*CT::precap : CT::precap);
+	// 1024 strings 64 ranges that share eight times precap, with more than 2048 strings 256 ranges that share sixteen times precap (buildInstances)
+	static constexpr uint32_t icap = ywides ? 16u*CT::precap : (xwides ? 8u*CT::precap : (wides ? 4u*CT::precap : CT::precap));
 	typedef typename FWideSel<xwides,uint32_t,uint16_t>::type toff_t;
 	typedef typename FWideSel<wides,uint16_t,uint8_t>::type nfreq_t;
 	typedef typename FWideSel<wides,uint32_t,uint16_t>::type nps_t;
@@ -1004,10 +1025,11 @@ struct FastEngine
 		enum : bool { GENMARKS = true };
 #endif
 		// compact string list entry: string | first slot << CLB.  8 bit string ids and 24 bit slots; more than 256 strings: 10 bit ids, 16 bit slots
-		// (a first slot is below npre <= 65536); more than 1024 strings: 11 bit ids, 17 bit slots (npre <= 131072)
-		enum : bool { WIDES = FastLds<CT>::wides, XWIDES = FastLds<CT>::xwides };
-		enum : uint32_t { CLB = XWIDES ? 11u : (WIDES ? 10u : 8u), CLMASK = (1u << CLB) - 1u };
-		static_assert(4u*CT::maxs <= FastLds<CT>::icap && CT::maxs <= (1u << CLB) && FastLds<CT>::icap <= (1u << (XWIDES ? 17 : (WIDES ? 16 : 24))),"compact string list: string | first slot << CLB, in the bytes of irpos");
+		// (a first slot is below npre <= 65536); more than 1024 strings: 11 bit ids, 17 bit slots (npre <= 131072); more than 2048 strings: 13 bit ids,
+		// 18 bit slots (npre <= 262144)
+		enum : bool { WIDES = FastLds<CT>::wides, XWIDES = FastLds<CT>::xwides, YWIDES = FastLds<CT>::ywides };
+		enum : uint32_t { CLB = YWIDES ? 13u : (XWIDES ? 11u : (WIDES ? 10u : 8u)), CLSLOTB = YWIDES ? 18u : (XWIDES ? 17u : (WIDES ? 16u : 24u)), CLMASK = (1u << CLB) - 1u };
+		static_assert(4u*CT::maxs <= FastLds<CT>::icap && CT::maxs <= (1u << CLB) && FastLds<CT>::icap <= (1u << CLSLOTB) && CLB + CLSLOTB <= 32u,"compact string list: string | first slot << CLB, in the bytes of irpos");
 		static_assert(!WIDES || GENMARKS,"the two-pass generation of more than 256 strings needs the marks");
 		LDSQ uint8_t * const marks = L.ipos();                                             // free until buildNodes writes the positions
 		LDSQ uint32_t * const clist = reinterpret_cast<LDSQ uint32_t *>(L.irpos());
@@ -1156,11 +1178,14 @@ struct FastEngine
 			// of the generation's marks, which nothing reads any more, bumped by workgroup atomics --, lane 0 turns the counts into first places, and a
 			// second pass takes a place per instance from the same counters: the order inside a range is whatever the atomics gave, the keys are
 			// distinct and the sort settles it.  A range of more than precap keys sends the window on like a full instance array.
-			enum : uint32_t { NR = 64 };
+			// (more than 2048 strings: up to 16 x precap instances in 256 ranges by the first FOUR symbols, k >= 4 -- a k-mer of three symbols has no fourth,
+			// and 5001 strings of it would exceed fqmax anyway: the window goes on)
+			enum : uint32_t { NRB = YWIDES ? 8u : 6u, NR = 1u << NRB };
+			if constexpr ( YWIDES ) { if ( 2u*k < NRB ) { over(1); npre = 0; nlast = 0; return; } }
 			static_assert(NR*8u <= FastLds<CT>::icap && (FastLds<CT>::o_ipos & 3u) == 0,"range counters and places: two 32 bit words per range in the bytes of ipos");
 			static_assert(FastLds<CT>::icap <= NR*CT::precap,"the ranges can hold every instance");
 			LDSQ uint32_t * const rcnt = reinterpret_cast<LDSQ uint32_t *>(L.ipos()), * const rat = rcnt + NR;
-			uint32_t const sh = 32u + 2u*k - 6u;
+			uint32_t const sh = 32u + 2u*k - NRB;
 			for ( uint32_t r = lane; r < 2u*NR; r += WSZ ) rcnt[r] = 0;
 			wv_sync();
 			for ( uint32_t t = lane; t < npre; t += WSZ ) wv_atomic_add(rcnt + (static_cast<uint32_t>(L.pregen()[t] >> sh) & (NR-1u)),1u);
@@ -1529,8 +1554,11 @@ struct FastEngine
 	// (first, ext, len desc, last) packed into 56 bits: Stretch::operator< (node ids ascend with k-mer value)
 	// (8 bit stretch ids: four 14 bit fields = 56 bits next to the id; 16 bit ids: four 12 bit fields = 48 bits)
 	// (16 bit ids and more than 4094 nodes -- the device-memory tiers --: four 13 bit fields = 52 bits next to a 12 bit stretch number, QB)
-	enum : uint32_t { KF = (sizeof(sid_t) == 1 ? 14u : (CT::ncap > 4094u ? 13u : 12u)), KFMAX = (1u<<KF)-1u, QB = (KF == 13u ? 12u : static_cast<uint32_t>(SB)), QMASK = (1u<<QB)-1u };
-	static_assert(4u*KF + QB <= 64u && CT::scap <= (1u<<QB) && CT::ncap <= KFMAX,"stretch sort key: four node fields and the stretch number in 64 bits");
+	// (more than 2048 strings -- FastLds<CT>::ywides --: 15 bit node fields.  The base sort there orders (first, ext, stretch number), 15 + 15 + 14 bits: two
+	// stretches with the same (first, ext) send the window on, so len and last never decide an order that is kept; poolKey, four fields = 60 bits, has no number)
+	enum : bool { KEY2 = FastLds<CT>::ywides };
+	enum : uint32_t { KF = (sizeof(sid_t) == 1 ? 14u : (KEY2 ? 15u : (CT::ncap > 4094u ? 13u : 12u))), KFMAX = (1u<<KF)-1u, QB = (KEY2 ? 14u : (KF == 13u ? 12u : static_cast<uint32_t>(SB))), QMASK = (1u<<QB)-1u };
+	static_assert((KEY2 ? 2u*KF : 4u*KF) + QB <= 64u && 4u*KF <= 64u && CT::scap <= (1u<<QB) && CT::ncap <= KFMAX,"stretch sort key: its node fields and the stretch number in 64 bits");
 	DEV static uint64_t sortKey(uint32_t first, uint32_t ext, uint32_t len, uint32_t last)
 	{
 		return (static_cast<uint64_t>(first)<<(3*KF)) | (static_cast<uint64_t>(ext)<<(2*KF)) | (static_cast<uint64_t>(KFMAX-len)<<KF) | last;
@@ -1604,14 +1632,19 @@ struct FastEngine
 		wv_sync();
 		uint32_t const p2 = next_pow2(ns < 2 ? 2 : ns);
 		for ( uint32_t q = lane; q < p2; q += WSZ )
+		{
+			if constexpr ( KEY2 ) L.skey()[q] = q < ns ? ((((static_cast<uint64_t>(L.tfirst()[q])<<KF) | L.links()[L.tlink()[q]+1])<<QB) | q) : ~0ull;
+			else
 			L.skey()[q] = q < ns ? ((sortKey(L.tfirst()[q],L.links()[L.tlink()[q]+1],L.tslen()[q] < KFMAX ? L.tslen()[q] : KFMAX,L.tlast()[q])<<QB) | q) : ~0ull;
+		}
 		wv_sync();
 		wv_sort_keys<fcpow2(CT::scap)>(L.skey(),ns);
 		// distinct (first,ext) by construction; a duplicate would need stretchesUnique's tie handling -> generic engine
 		uint32_t dup = 0;
 		for ( uint32_t q = lane; q < ns; q += WSZ )
 		{
-			if ( q && (L.skey()[q]>>(QB+2*KF)) == (L.skey()[q-1]>>(QB+2*KF)) ) dup = 1;
+			enum : uint32_t { DUPSH = KEY2 ? QB : QB+2*KF };      // (what stands above it: first, ext)
+			if ( q && (L.skey()[q]>>DUPSH) == (L.skey()[q-1]>>DUPSH) ) dup = 1;
 			uint32_t const raw = L.skey()[q]&QMASK;
 			L.sfirst()[q] = L.tfirst()[raw]; L.slast()[q] = L.tlast()[raw]; L.sslen()[q] = L.tslen()[raw]; L.slink()[q] = L.tlink()[raw];
 		}
@@ -1949,10 +1982,24 @@ struct FastEngine
 		static_assert(sizeof(toff_t) == 2 || 2ull*CT::scap*128ull <= TOFFMAX,"task offsets: every (stretch, direction, position) triple can be named");
 		// (legacy layout: 16 bit records over the bytes of ulo / uhi, at most 511 units; gw layout: 32 bit records)
 		auto const urec = unitRecords();
-		uint32_t ulo_r[NCHU], uw_r[NCHU], ucls_r[NCHU], upos_r[NCHU];
+		// (the four words of unit cc*WSZ + lane: registers, every loop over the chunks is unrolled.  More than 2048 strings -- 384 chunks --: words of device
+		// memory instead, in the bytes of the generation's instance array, which nothing reads between two builds of the instances; a lane reads back
+		// only what it wrote itself)
+		enum : bool { UMEM = FastLds<CT>::ywides };
+		struct UTab { LDSQ uint32_t * p; DEV uint32_t & operator[](uint32_t const cc) const { return p[cc*WSZ]; } };
+		typedef typename FWideSel<UMEM,UTab,uint32_t[NCHU]>::type utab_t;
+		utab_t ulo_r, uw_r, ucls_r, upos_r;
+		if constexpr ( UMEM )
+		{
+			static_assert(!UMEM || 4ull*NCHU*WSZ*sizeof(uint32_t) <= 8ull*FastLds<CT>::icap,"the unit table borrows the generation's instance array");
+			LDSQ uint32_t * const ut = reinterpret_cast<LDSQ uint32_t *>(L.pregen()) + lane;
+			ulo_r.p = ut; uw_r.p = ut + NCHU*WSZ; ucls_r.p = ut + 2*NCHU*WSZ; upos_r.p = ut + 3*NCHU*WSZ;
+		}
+		// (chunks walked: all of them where they are registers, a constant the loops unroll by; the chunks that hold a unit where they are memory)
+		uint32_t const nchu = UMEM ? (nu + WSZ - 1)/WSZ : static_cast<uint32_t>(NCHU);
 		uint32_t allF = 0, allR = 0;          // this lane's tasks without the filter, by direction
 		#pragma unroll
-		for ( uint32_t cc = 0; cc < NCHU; ++cc )
+		for ( uint32_t cc = 0; cc < nchu; ++cc )
 		{
 			uint32_t const u = cc*WSZ + lane;
 			uint32_t w = 0, lo_ = 0, cls = NCLS;
@@ -2000,7 +2047,7 @@ struct FastEngine
 			for ( uint32_t k = 0; k < NCLS; ++k )
 			{
 				#pragma unroll
-				for ( uint32_t cc = 0; cc < NCHU; ++cc )
+				for ( uint32_t cc = 0; cc < nchu; ++cc )
 				{
 					if ( cc*WSZ >= nu ) break;
 					bool const mine = ucls_r[cc] == k;
@@ -2017,7 +2064,7 @@ struct FastEngine
 		if ( !feascount ) feasapplied = filt;
 	#endif
 		#pragma unroll
-		for ( uint32_t cc = 0; cc < NCHU; ++cc )
+		for ( uint32_t cc = 0; cc < nchu; ++cc )
 		{
 			uint32_t const u = cc*WSZ + lane;
 			if ( u < nu )
@@ -2178,7 +2225,8 @@ struct FastEngine
 	static_assert((64ull*static_cast<uint64_t>(FQMAX)*0xFFFFFFFFull) >> (32u+SWHB) == 0,"high part of a stretch weight: 64 nodes");
 	static_assert(SWHB + NWHB <= 32u,"reverse record: both high parts in its third word");
 	static_assert(SWHB == 16u || FastLds<CT>::wides,"a stretch weight of more than 48 bits needs the 32 byte forward record");
-	static_assert(CT::maxs <= 1024 || (FastLds<CT>::fqmax == 4095u && FastLds<CT>::icap == 8u*CT::precap && FastLds<CT>::xwides),"more than 1024 strings: the widths of FastLds<CT>::xwides");
+	static_assert(CT::maxs <= 1024 || (FastLds<CT>::fqmax == 4095u && FastLds<CT>::icap == (FastLds<CT>::ywides ? 16u : 8u)*CT::precap && FastLds<CT>::xwides),"more than 1024 strings: the widths of FastLds<CT>::xwides");
+	static_assert(CT::maxs <= 2048 || (FastLds<CT>::ywides && CT::ncap <= 0xFFFEu && CT::scap <= 0xFFFEu && CT::lcap <= 0xFFFFu && CT::smax <= CT::scap),"more than 2048 strings: node ids, stretch ids and link offsets (links, tlink, slink) are 16 bit words, 0xFFFF is none");
 	static_assert(FastLds<CT>::wides || 16u + 2u*NWHB <= 32u,"forward record: three high parts in its fourth word, or the 32 byte record");
 	struct G8 { G4 a, b; };      // the 32 byte forward record of more than 256 strings: w, w1 | wl, unused (two 16 byte loads)
 	// One record per feasible (stretch, position) entry.  Forward: whole stretch (w), its first node at the start position

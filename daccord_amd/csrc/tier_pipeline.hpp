@@ -10,7 +10,7 @@
  *   shallow and deep  tier 5 on the second stream (k_window_long), in front of the generic engine there
  *   wide batches      the LONG STRING stage on the second stream: tier 17 (strings of 129 ... 255 bases, layout in device memory), in front of the generic engine there
  *   every batch       the TRAILING stages, each once, behind the slots and in front of the generic engine: tier 13 (shallow, deep) / tier 14 (wide), then in
- *                     shallow and deep batches tier 15 and tier 16, each only in a batch with a window deep enough for it
+ *                     shallow and deep batches tier 15, tier 16 and tier 18, each only in a batch with a window deep enough for it
  *
  * (TIER_CHAIN below: one row per stage, one column per batch shape.)
  *
@@ -37,6 +37,10 @@
  *   ID_XDEEP   16 (shallow, deep)          1001 ... 2000 strings, and those of 251 ... 1000   DACC_XDEEP_TIER   DACC_XDEEP_AS_SLOT2 (a wide batch keeps   XDEEP_MINS = 1000
  *                                          that overflowed a table of tier 15; those of at                      tier 9)
  *                                          most 250 passed on
+ *   ID_FDEEP   18 (shallow, deep)          2001 ... 5001 strings (the deepest window of a     DACC_FDEEP_TIER   DACC_FDEEP_AS_SLOT2 (a wide batch keeps   FDEEP_MINS = 2000
+ *                                          default run), and those of 251 ... 2000 that                             tier 9)
+ *                                          overflowed a table of tier 16; those of at most
+ *                                          250 passed on
  *
  * The LONG STRING stage (ID_LONG in a wide batch, ROLE_LONG) runs tier 17 -- tier 14 with four words per pattern mask, strings of up to 255 bases -- over the
  * two lists of the second stream (the pre-scan's: a B string of more than 128 bases; the first tier's generic-only windows) with a kernel of its own,
@@ -67,7 +71,7 @@ enum : uint32_t { T0INST_DEFAULT = 576, T7INST_DEFAULT = 704 };      // a window
                                                // arguments of the pre-pass (DACC_T0INST / DACC_T7INST override them for sweeps)
 
 // The tiers.  KERNEL: those with a kernel of their own (k_window_fast<N>, window_kernels.hpp); tier 5 runs inside k_window_long.
-#define DACC_KERNEL_TIERS(X) X(0) X(1) X(2) X(3) X(4) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17)
+#define DACC_KERNEL_TIERS(X) X(0) X(1) X(2) X(3) X(4) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18)
 #define DACC_ALL_TIERS(X) DACC_KERNEL_TIERS(X) X(5)
 
 // From a run-time tier number to its compile-time capacities: f is called with a TierTag<N>, whose `type` is FastTier<N>
@@ -106,14 +110,21 @@ enum : uint32_t { WORK_SLOT0 = 0, WORK_SLOT1 = 8, WORK_SLOT2 = 16, WORK_DENSE = 
 	WORK_VDEEP_COUNT = 96,     // two words: windows of more than VDEEP_MINS strings the very deep stage read / handed on (for dacc_timing)
 	WORK_XDEEP = 104,
 	WORK_XDEEP_COUNT = 112,    // two words: windows of more than VDEEP_MINS strings the deepest stage read / handed on (for dacc_timing)
-	WORK_LONGSTR = 120,        // the long string stage's launch over the pre-scan list, WORK_LONGSTR + 8: its launch over the first tier's generic-only list
-	WORK_WORDS = 136 };
+	WORK_FDEEP = 120,
+	WORK_FDEEP_COUNT = 128,    // two words: windows of more than VDEEP_MINS strings the full-depth stage read / handed on (for dacc_timing)
+	// (everything above is the first stream's and cleared at the start of every pass; the second stream clears what follows in front of its launches)
+	WORK_LONGSTR = 136,        // the long string stage's launch over the pre-scan list, WORK_LONGSTR + 8: its launch over the first tier's generic-only list
+	WORK_WORDS = 152 };
 
-// The stages, in the order they run; their place in this table is their place in BatchPlan::stageCaps, TierPipeline and dacc_ctx::st.
-enum TierId { ID_T0, ID_T7, ID_SLOT0, ID_SLOT1, ID_DENSE, ID_DEEP, ID_SLOT2, ID_LAST, ID_VDEEP, ID_XDEEP, ID_LONG, TIER_NSTAGES };
+// The stages, in the order they run (ID_FDEEP runs behind ID_XDEEP: the trailing stages run in the order of their rows, and no row between them is one); their
+// place in this table is their place in BatchPlan::stageCaps, TierPipeline and dacc_ctx::st.  TIER_NSTAGES counts the rows up to ID_LONG, which is what a caller
+// that holds one capacity record per stage in an array of TIER_NSTAGES walks (the emulation harness, tests/tiers/tier_resolution.cpp and its recording of one
+// column per stage); the rows added since stand behind it, TIER_NROWS counts all, and resolveTiers resolves them for a caller that says it holds them (`rows`).
+enum TierId { ID_T0, ID_T7, ID_SLOT0, ID_SLOT1, ID_DENSE, ID_DEEP, ID_SLOT2, ID_LAST, ID_VDEEP, ID_XDEEP, ID_LONG, TIER_NSTAGES, ID_FDEEP = TIER_NSTAGES, TIER_NROWS };
 enum { TIER_NSLOTS = 3, TIER_NONE = 255, TIER_SHALLOW_FIRST = 1 };      // (the first slot's main tier of shallow batches: a batch whose windows mostly overflow its strings / instances is deep)
 enum : uint32_t { VDEEP_MINS = 250 };      // the very deep stage takes the windows with more strings than this (= FastTier<15>::mins = FastTier<13>::maxs, fast_window.hpp)
 enum : uint32_t { XDEEP_MINS = 1000 };     // the deepest stage is resolved for a batch with a window of more strings than this (= FastTier<15>::maxs); its tier takes what has more than VDEEP_MINS
+enum : uint32_t { FDEEP_MINS = 2000 };     // the full-depth stage is resolved for a batch with a window of more strings than this (= FastTier<16>::maxs); its tier takes what has more than VDEEP_MINS
 struct TierStage
 {
 	uint8_t tier[3] /* in a shallow, deep, wide batch */, slot, role; int8_t tiersbit /* bit of DACC_TIERS */; uint32_t flags, work;
@@ -123,7 +134,7 @@ struct TierStage
 	uint32_t minstrings = 0;               // resolved only for a batch whose deepest window has more strings than this (0: every batch)
 	bool slot2wide = false;                // does its AS_SLOT2 switch apply to a wide batch (else that keeps tier 9)
 };
-static TierStage const TIER_CHAIN[TIER_NSTAGES] = {
+static TierStage const TIER_CHAIN[TIER_NROWS] = {
 	{ { 0, TIER_NONE, TIER_NONE }, 0, ROLE_FRONT, 3, STAGE_PREPASS, WORK_T0 },
 	{ { 7, TIER_NONE, TIER_NONE }, 0, ROLE_FRONT, 4, STAGE_PREPASS|STAGE_ADAPTIVE|GATE_PREV_FRONT|GATE_T7_ABOVE_T0, WORK_T7 },
 	{ { 1, 4, TIER_NONE }, 0, ROLE_MAIN, 0, GATE_TABFIT, WORK_SLOT0 },
@@ -136,7 +147,9 @@ static TierStage const TIER_CHAIN[TIER_NSTAGES] = {
 	{ { 16, 16, TIER_NONE }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_TRAILING, WORK_XDEEP, "DACC_XDEEP_TIER", "DACC_XDEEP_AS_SLOT2", XDEEP_MINS, false },
 	// (tier 5 holds no wide window and no string of more than 128 bases: a wide batch's second stream runs tier 17, a kernel of its own over a slab in device
 	// memory, and the generic engine behind it)
-	{ { 5, 5, 17 }, 0, ROLE_LONG, 2, GATE_TABFIT|GATE_LONGSTR, WORK_LONGSTR } };
+	{ { 5, 5, 17 }, 0, ROLE_LONG, 2, GATE_TABFIT|GATE_LONGSTR, WORK_LONGSTR },
+	// (behind TIER_NSTAGES; it runs behind ID_XDEEP)
+	{ { 18, 18, TIER_NONE }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_TRAILING, WORK_FDEEP, "DACC_FDEEP_TIER", "DACC_FDEEP_AS_SLOT2", FDEEP_MINS, false } };
 static TierId const TIER_MAIN[TIER_NSLOTS] = { ID_SLOT0, ID_SLOT1, ID_SLOT2 };
 // does the stage run in a batch of this shape, and the tier whose capacities the plan holds for it (a stage that does not run keeps
 // those of the nearest shape: the first slot of a wide batch has tier 1's or tier 4's)
@@ -158,8 +171,8 @@ struct TierSwitches
 	bool widetier;            // DACC_WIDE_TIER=0: wide batches run in the generic engine only, as in rounds 4-5
 	bool dense;               // DACC_DENSE_TIER=0: the second slot hands on to tier 3 directly (before round 6's dense tiers)
 	bool deepwin;             // DACC_DEEP_TIER=0: no deep-window tier (tier 12) in front of tier 3
-	bool off[TIER_NSTAGES];        // a trailing stage's DACC_*_TIER=0: the chain as it was before that stage (its windows run in what stands behind it)
-	bool as_slot2[TIER_NSTAGES];   // a trailing stage's DACC_*_AS_SLOT2=1: its tier as the third slot's main tier, no such stage
+	bool off[TIER_NROWS];        // a trailing stage's DACC_*_TIER=0: the chain as it was before that stage (its windows run in what stands behind it)
+	bool as_slot2[TIER_NROWS];   // a trailing stage's DACC_*_AS_SLOT2=1: its tier as the third slot's main tier, no such stage
 	bool longstr;             // DACC_LONGSTR_TIER=0: no long string stage (tier 17) on the second stream of a wide batch, the generic engine alone as before that stage
 	bool conflict() const { int n = 0; for ( bool const b : as_slot2 ) n += b; return n > 1; }      // more than one wants the third slot: dacc_create refuses
 	bool long128;             // DACC_LONG128=0: windows with a string of 65 ... 128 bases run in tier 5 on the second stream (rounds 3-5)
@@ -175,7 +188,7 @@ static inline TierSwitches readTierSwitches()
 	{ char const * const e = getenv("DACC_NOFAST"); S.nofast = e && e[0] == '1'; }
 	S.tiers = num("DACC_TIERS",31);
 	S.widetier = !off("DACC_WIDE_TIER"); S.dense = !off("DACC_DENSE_TIER"); S.deepwin = !off("DACC_DEEP_TIER"); S.longstr = !off("DACC_LONGSTR_TIER"); S.long128 = !off("DACC_LONG128"); S.hand = !off("DACC_HAND");
-	for ( uint32_t i = 0; i < TIER_NSTAGES; ++i ) { TierStage const & st = TIER_CHAIN[i]; S.off[i] = st.offswitch && off(st.offswitch); S.as_slot2[i] = stageAsSlot2(st); }
+	for ( uint32_t i = 0; i < TIER_NROWS; ++i ) { TierStage const & st = TIER_CHAIN[i]; S.off[i] = st.offswitch && off(st.offswitch); S.as_slot2[i] = stageAsSlot2(st); }
 	S.t0inst = num("DACC_T0INST",T0INST_DEFAULT); S.t7inst = num("DACC_T7INST",T7INST_DEFAULT);
 	S.lds_t1 = num("DACC_LDS_T1",0); S.lds_t0 = num("DACC_LDS_T0",0);
 	return S;
@@ -191,7 +204,7 @@ static inline uint32_t tierGrid(uint32_t const ldsbytes, uint64_t const nwindows
 }
 
 // Launch geometry of a device-memory tier (FastCaps::gmem): no LDS and 512 registers, so up to four workgroups per CU would fit; what bounds the
-// grid is the slab, gbytes per workgroup (tier 13: 1 059 840 B, tier 14: 1 125 632 B, tiers 15 and 16: see DESIGN 3.2), kept to TIER_GMEM_SLAB = 256 MiB per context:
+// grid is the slab, gbytes per workgroup (tier 13: 1 059 840 B, tier 14: 1 125 632 B, tiers 15, 16 and 18: see DESIGN 3.2), kept to TIER_GMEM_SLAB = 256 MiB per context:
 // 256 MiB / 1 059 840 B = 253 -> 248 workgroups (a multiple of 8, one share per XCD), 232 for tier 14 -- about one per CU, whose working sets
 // (1 MB each) then share the L2 of their XCD with no more than 31 others.  The stage sees a few windows per batch, hundreds on high-error data;
 // a small batch gets a workgroup per window and a slab to match.
@@ -208,8 +221,8 @@ struct TierPipeline
 {
 	bool usefast = false;                 // the LDS tiers may run at all
 	bool widetier = false;                // wide windows (w = 64 ... 127) in tiers 8 and 9
-	bool ok[TIER_NSTAGES] = {};
-	uint32_t tier[TIER_NSTAGES] = {};     // the tier of the stage in this batch
+	bool ok[TIER_NROWS] = {};
+	uint32_t tier[TIER_NROWS] = {};     // the tier of the stage in this batch
 	bool late_long = false;               // slots 1 and 2 skip only the windows the second stream has (a string of more than 128 bases), not all with more than 64
 	bool slot1_long = false;              // the pre-scan puts the windows with a string of 65 ... 128 bases on the first slot's hand-over list
 	bool handover = false;                // hand-over slots pay: a wide batch has nothing to hand the sorted instances to
@@ -222,9 +235,10 @@ struct TierPipeline
 // of a stage (BatchPlan::stageCaps); the measurement switches DACC_LDS_T1 / DACC_LDS_T0 raise the LDS sizes in them.
 // maxstrings: strings of the deepest window of the batch (BatchPlan::maxstrings); a trailing stage with a threshold (TierStage::minstrings) is resolved only for a batch that has a
 // window for it -- a caller that walks the slots only (the emulation harness) leaves it out and sees no such stage.
+// rows: the rows of TIER_CHAIN the caller holds capacities for (capsOf is asked for no other): TIER_NSTAGES, or TIER_NROWS with the stages behind ID_LONG.
 template<typename C>
 static inline TierPipeline resolveTiers(TierSwitches const & S, bool const fastpath, bool const deep, bool const wide, uint32_t const nrows, uint32_t const nsup, uint32_t const w, C && capsOf,
-	uint32_t const maxstrings = 0)
+	uint32_t const maxstrings = 0, uint32_t const rows = TIER_NSTAGES)
 {
 	TierPipeline R;
 	// wide windows, w = 64 ... 127 (model table of up to 128 rows): DACC_WIDE_TIER=0 leaves them to the generic engine, w = 128 always
@@ -243,11 +257,11 @@ static inline TierPipeline resolveTiers(TierSwitches const & S, bool const fastp
 	};
 	{ FastCaps & F = capsOf(ID_SLOT0); if ( S.lds_t1 > F.ldsbytes && S.lds_t1 <= TIER_LDS_CU ) F.ldsbytes = S.lds_t1; }
 	{ FastCaps & F = capsOf(ID_T0); if ( S.lds_t0 > F.ldsbytes && S.lds_t0 <= TIER_LDS_CU ) F.ldsbytes = S.lds_t0; }
-	for ( uint32_t i = 0; i < TIER_NSTAGES; ++i ) { R.tier[i] = stageTier(TIER_CHAIN[i],deep,wide); if ( TIER_CHAIN[i].role != ROLE_FRONT ) R.ok[i] = gated(i); }
+	for ( uint32_t i = 0; i < rows; ++i ) { R.tier[i] = stageTier(TIER_CHAIN[i],deep,wide); if ( TIER_CHAIN[i].role != ROLE_FRONT ) R.ok[i] = gated(i); }
 	// a trailing stage reads what a slot handed on: no slot, no such stage (generic-only configurations stay generic-only)
-	for ( uint32_t i = 0; i < TIER_NSTAGES; ++i ) if ( TIER_CHAIN[i].role == ROLE_LAST ) R.ok[i] = R.ok[i] && R.anytier();
+	for ( uint32_t i = 0; i < rows; ++i ) if ( TIER_CHAIN[i].role == ROLE_LAST ) R.ok[i] = R.ok[i] && R.anytier();
 	// the front tiers, in chain order (a front tier stands before the main tier of its slot)
-	for ( uint32_t i = 0; i < TIER_NSTAGES; ++i )
+	for ( uint32_t i = 0; i < rows; ++i )
 	{
 		TierStage const & st = TIER_CHAIN[i];
 		if ( st.role == ROLE_FRONT )

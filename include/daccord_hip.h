@@ -191,8 +191,8 @@ typedef struct dacc_timing {
 	float tier10_ms;         /* round 6, the dense-graph tier of shallow batches: k_window_fast<10> (2 wavefronts per CU) between tier 6 and tier 3, the part of tier_ms[2] in front of k_window_fast<3>; 0 if it did not run */
 	uint32_t tier10_out;     /* windows tier 10 handed on to tier 3 (it ran tier_out[1] windows) */
 	uint32_t tier10_ran;     /* 1: tier 10 ran in this pass (tier_out[1] went to it, not to tier 3) */
-	uint32_t xdeep_out;      /* the deepest stage (below): windows of more than 250 strings it handed on to k_window (more than 2000 strings, a k-mer seen more than 4095 times, a table
-	                            beyond its capacities).  It took the place of a pad word (always 0 before): the record keeps its size */
+	uint32_t xdeep_out;      /* the deepest stage (below): windows of more than 250 strings it handed on (more than 2000 strings, a k-mer seen more than 4095 times, a table
+	                            beyond its capacities): what k_window ran -- where the full-depth stage ran, what that stage read (xdeep_out = fdeep_windows + fdeep_out).  It took the place of a pad word (always 0 before): the record keeps its size */
 	/* ---- everything above: DACC_TIMING_SIZE_V1 bytes, what dacc_last_timing fills ---- */
 	float deep_ms;           /* the deep-window tier: k_window_fast<12> (1 wavefront per CU; windows of 97 ... 250 strings) in front of k_window_fast<3>, a part of tier_ms[2]; 0 if it did not run */
 	uint32_t deep_windows;   /* windows of more than 96 strings that finished in tier 12 */
@@ -224,14 +224,24 @@ typedef struct dacc_timing {
 	uint32_t longstr_out;    /* windows it handed on to the generic engine of the second stream (a string of more than 255 bases, a table beyond its capacities);
 	                            where it ran, longstr_windows + longstr_out == long_windows */
 	uint32_t pad2_;
+	/* ---- everything above: 192 bytes, the record before the full-depth stage ---- */
+	/* the full-depth stage: k_window_fast<18> (layout in device memory, windows of 2001 ... 5001 strings and what <16> overflowed on), behind the deepest stage and in front of
+	   k_window; launched only in a shallow or deep batch whose deepest window has more than 2000 strings; not a part of tier_ms[] */
+	float fdeep_ms;          /* its kernel; 0 if it did not run (no window of more than 2000 strings in the batch, a wide batch, DACC_FDEEP_TIER=0, DACC_FDEEP_AS_SLOT2=1, no slot ran, no memory
+	                            for its slab) */
+	uint32_t fdeep_windows;  /* windows of more than 250 strings that finished in it */
+	uint32_t fdeep_out;      /* windows of more than 250 strings it handed on to k_window (more than 5001 strings, a k-mer seen more than 4095 times, k = 3, a table beyond its capacities) */
+	uint32_t pad3_;
 } dacc_timing;
 #define DACC_TIMING_SIZE_V1 128
 #define DACC_TIMING_SIZE_V2 176   /* the record in front of longstr_ms */
+#define DACC_TIMING_SIZE_V3 192   /* the record in front of fdeep_ms */
 /* dacc_last_timing fills the first DACC_TIMING_SIZE_V1 bytes only (the record as it was when the call was introduced: a caller built against
  * an older header is never overrun).  dacc_last_timing2 copies min(size, sizeof(dacc_timing)) bytes: pass sizeof(dacc_timing) of the header
  * the caller was compiled with; fields the library does not know stay as the caller set them.  The 16 bytes behind emit_ms (the long string
- * stage) are copied only when size covers all of them: a size between DACC_TIMING_SIZE_V2 and sizeof(dacc_timing) copies DACC_TIMING_SIZE_V2
- * bytes, so that a caller of the 176 byte record who passes the size of a larger buffer of its own gets what it got before. */
+ * stage) are copied only when size covers all of them: a size in [DACC_TIMING_SIZE_V2, DACC_TIMING_SIZE_V3) copies DACC_TIMING_SIZE_V2
+ * bytes, so that a caller of the 176 byte record who passes the size of a larger buffer of its own gets what it got before.  The same rule holds
+ * for the 16 bytes behind pad2_ (the full-depth stage): a size in [DACC_TIMING_SIZE_V3, sizeof(dacc_timing)) copies DACC_TIMING_SIZE_V3 bytes. */
 int  dacc_last_timing(dacc_ctx *ctx, dacc_timing *t);
 int  dacc_last_timing2(dacc_ctx *ctx, dacc_timing *t, size_t size);
 
