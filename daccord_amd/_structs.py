@@ -56,10 +56,17 @@ class DaccTimingLong(C.Structure):
 
 
 class DaccTimingFull(C.Structure):
-    """dacc_timing as it is since the full-depth stage: DaccTimingLong (192 bytes, unchanged) and the 16 bytes appended behind pad2_"""
+    """dacc_timing as it was with the full-depth stage: DaccTimingLong (192 bytes, unchanged) and the 16 bytes appended behind pad2_"""
     _fields_ = DaccTimingLong._fields_ + [
         # the full-depth stage (k_window_fast<18>: windows of 2001 ... 5001 strings, behind the deepest stage and in front of k_window)
         ("fdeep_ms", C.c_float), ("fdeep_windows", C.c_uint32), ("fdeep_out", C.c_uint32), ("pad3_", C.c_uint32)]
+
+
+class DaccTimingWide(C.Structure):
+    """dacc_timing as it is since the wide deep stage: DaccTimingFull (208 bytes, unchanged) and the 16 bytes appended behind pad3_"""
+    _fields_ = DaccTimingFull._fields_ + [
+        # the wide deep stage (k_window_fast<19>: windows of 251 ... 1000 strings of a wide batch, behind the last stage and in front of k_window)
+        ("wdeep_ms", C.c_float), ("wdeep_windows", C.c_uint32), ("wdeep_out", C.c_uint32), ("pad4_", C.c_uint32)]
 
 
 TIMING_SIZE_V1 = 128

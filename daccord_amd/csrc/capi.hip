@@ -484,14 +484,15 @@ static int dacc_load_db_body(dacc_ctx * c, uint8_t const * bps, uint64_t bps_byt
 // `mins` strings on the list it read (windows + out) and on the list it handed on (out), counted by k_count_deeper into two words of d_work from the final
 // window records (behind the scratch retries of the generic engine); else everything on its list is its own: the difference of the two list lengths -- what the
 // last stage handed on is what k_window ran, or what the very deep stage read.  The deepest stage and the full-depth stage count with the very deep stage's threshold:
-// what the deepest stage read with more than VDEEP_MINS strings is vdeep_out where that stage ran, what the full-depth stage read is xdeep_out where the deepest ran.  `ms`: a trailing stage's kernel time (the deep-window tier's has a start event of its own)
+// what the deepest stage read with more than VDEEP_MINS strings is vdeep_out where that stage ran, what the full-depth stage read is xdeep_out where the deepest ran.  The wide deep stage (wide batches, where none of those three runs) reads what the last stage handed on.  `ms`: a trailing stage's kernel time (the deep-window tier's has a start event of its own)
 struct StageCounters { TierId id; float dacc_timing::* ms; uint32_t dacc_timing::* windows, dacc_timing::* out; bool deeper; uint32_t mins, countwords; };
 static StageCounters const STAGE_COUNTERS[] = {
 	{ ID_DEEP, nullptr, &dacc_timing::deep_windows, &dacc_timing::deep_out, true, FastTier<12>::mins, WORK_DEEP_COUNT },
 	{ ID_LAST, &dacc_timing::last_ms, &dacc_timing::last_windows, &dacc_timing::last_out, false, 0, 0 },
 	{ ID_VDEEP, &dacc_timing::vdeep_ms, &dacc_timing::vdeep_windows, &dacc_timing::vdeep_out, true, VDEEP_MINS, WORK_VDEEP_COUNT },
 	{ ID_XDEEP, &dacc_timing::xdeep_ms, &dacc_timing::xdeep_windows, &dacc_timing::xdeep_out, true, VDEEP_MINS, WORK_XDEEP_COUNT },
-	{ ID_FDEEP, &dacc_timing::fdeep_ms, &dacc_timing::fdeep_windows, &dacc_timing::fdeep_out, true, VDEEP_MINS, WORK_FDEEP_COUNT } };
+	{ ID_FDEEP, &dacc_timing::fdeep_ms, &dacc_timing::fdeep_windows, &dacc_timing::fdeep_out, true, VDEEP_MINS, WORK_FDEEP_COUNT },
+	{ ID_WDEEP, &dacc_timing::wdeep_ms, &dacc_timing::wdeep_windows, &dacc_timing::wdeep_out, true, VDEEP_MINS, WORK_WDEEP_COUNT } };
 
 // ---- the device pass (runDevice): one function per phase, in the order they run; they share the context and the state of the pass
 // DACC_DEBUG_SYNC=1: wait for every kernel of the generic-only path and say so on stderr (a device fault then names its kernel)
@@ -885,7 +886,7 @@ static int fetchStageCounters(dacc_ctx * c)
 		if ( K.ms ) { float sms = 0; hipEventElapsedTime(&sms,from,S.done); c->timing.*K.ms = sms; from = S.done; }
 	}
 	// the long string stage (wide batches, second stream): what it read is what the second stream read (long_windows), what it handed on is what k_window_long ran
-	c->timing.longstr_ms = 0; c->timing.longstr_windows = 0; c->timing.longstr_out = 0; c->timing.pad2_ = 0; c->timing.pad3_ = 0;
+	c->timing.longstr_ms = 0; c->timing.longstr_windows = 0; c->timing.longstr_out = 0; c->timing.pad2_ = 0; c->timing.pad3_ = 0; c->timing.pad4_ = 0;
 	if ( !(TP.usefast && BP.nwindows && TP.anytier()) ) c->longran[0] = c->longran[1] = false;
 	for ( int i = 0; i < 2; ++i )
 		if ( c->longran[i] )
@@ -1088,13 +1089,14 @@ static int dacc_submit_piles_body(dacc_ctx * c, dacc_pile const * piles, uint64_
 		for ( uint32_t i = 0; i < TIER_NROWS; ++i )
 		{
 			FastCaps const & F = BP.stageCaps(i);
-			c->st[i].grid = F.gmem ? tierGridGmem(F.gbytes,BP.nwindows) : tierGrid(F.ldsbytes,BP.nwindows);
+			c->st[i].grid = F.gmem ? tierGridGmem(F.gbytes,BP.nwindows,TIER_CHAIN[i].slab) : tierGrid(F.ldsbytes,BP.nwindows);
 			if ( !TP.ok[i] || TIER_CHAIN[i].role == ROLE_LONG ) continue;
 			if ( TIER_CHAIN[i].role == ROLE_LAST )
 			{
-				// a trailing stage: its own hand-on list (what the next one or k_window reads) and its own slab, grid x gbytes <= TIER_GMEM_SLAB.  Both are optional
+				// a trailing stage: its own hand-on list (what the next one or k_window reads) and its own slab, grid x gbytes <= TIER_GMEM_SLAB (or the row's own budget, TierStage::slab).  Both are optional
 				// like the hand-over buffer: a device that cannot spare them runs the batch without the stage, on the route it had before
 				DevBuf<uint8_t> & slab = c->st[i].slab;
+				if ( TIER_CHAIN[i].slab && c->noslab ) { slab.release(); c->TP.ok[i] = false; continue; }      // a retry after an allocation failure: no slab budget beyond the common one (dacc_drop_hand)
 				hipError_t e = c->st[i].handon.ensure(BP.nwindows+2);
 				if ( e == hipSuccess ) e = slab.ensure(static_cast<size_t>(c->st[i].grid)*F.gbytes + 256);
 				if ( e == hipErrorOutOfMemory ) { (void)hipGetLastError(); slab.release(); c->TP.ok[i] = false; }
@@ -1176,7 +1178,7 @@ void dacc_release(dacc_ctx * c) { if ( c ) { c->frags.clear(); c->bases.clear();
 // dacc_last_timing: the record as it was when the call got its signature (everything in front of deep_ms), so that a caller compiled against
 // that header is not overrun; dacc_last_timing2 copies as much of today's record as the caller says it has room for
 static_assert(offsetof(dacc_timing,deep_ms) == DACC_TIMING_SIZE_V1,"dacc_last_timing fills the record in front of deep_ms");
-static_assert(offsetof(dacc_timing,vdeep_ms) == 160 && offsetof(dacc_timing,longstr_ms) == DACC_TIMING_SIZE_V2 && DACC_TIMING_SIZE_V2 == 176 && offsetof(dacc_timing,fdeep_ms) == DACC_TIMING_SIZE_V3 && DACC_TIMING_SIZE_V3 == 192 && sizeof(dacc_timing) == 208,"the very deep stage's fields are appended behind last_*, the long string stage's 16 bytes behind emit_ms, the full-depth stage's 16 bytes behind those");
+static_assert(offsetof(dacc_timing,vdeep_ms) == 160 && offsetof(dacc_timing,longstr_ms) == DACC_TIMING_SIZE_V2 && DACC_TIMING_SIZE_V2 == 176 && offsetof(dacc_timing,fdeep_ms) == DACC_TIMING_SIZE_V3 && DACC_TIMING_SIZE_V3 == 192 && offsetof(dacc_timing,wdeep_ms) == DACC_TIMING_SIZE_V4 && DACC_TIMING_SIZE_V4 == 208 && offsetof(dacc_timing,wdeep_windows) == 212 && offsetof(dacc_timing,wdeep_out) == 216 && sizeof(dacc_timing) == 224,"the very deep stage's fields are appended behind last_*, the long string stage's 16 bytes behind emit_ms, the full-depth stage's 16 bytes behind those, the wide deep stage's 16 bytes behind those");
 static_assert(offsetof(dacc_timing,xdeep_ms) == 140 && offsetof(dacc_timing,xdeep_windows) == 156 && offsetof(dacc_timing,xdeep_out) == 124,"the deepest stage's fields take the pad words: the record keeps its size");
 static_assert(offsetof(dacc_timing,emit_ms) == 172,"emit_ms is the last word of the first 176 bytes, where the very deep stage's pad word was");
 int dacc_last_timing(dacc_ctx * c, dacc_timing * t)
@@ -1190,8 +1192,8 @@ int dacc_last_timing2(dacc_ctx * c, dacc_timing * t, size_t size)
 	if ( !c || !t ) return DACC_EINVAL;
 	// the long string stage's 16 bytes behind emit_ms go only to a caller that has room for all of them: a caller built with the 176 byte record that
 	// passes a larger size (its record inside a larger buffer) gets the 176 bytes it knows, as before the record grew; the full-depth stage's 16 bytes behind
-	// those follow the same rule: a size in [192, 208) copies 192 bytes
-	size_t const n = size >= sizeof(dacc_timing) ? sizeof(dacc_timing) : (size >= DACC_TIMING_SIZE_V3 ? static_cast<size_t>(DACC_TIMING_SIZE_V3) : (size < DACC_TIMING_SIZE_V2 ? size : static_cast<size_t>(DACC_TIMING_SIZE_V2)));
+	// those follow the same rule: a size in [192, 208) copies 192 bytes; so do the wide deep stage's 16 bytes behind pad3_: a size in [208, 224) copies 208 bytes
+	size_t const n = size >= sizeof(dacc_timing) ? sizeof(dacc_timing) : (size >= DACC_TIMING_SIZE_V4 ? static_cast<size_t>(DACC_TIMING_SIZE_V4) : (size >= DACC_TIMING_SIZE_V3 ? static_cast<size_t>(DACC_TIMING_SIZE_V3) : (size < DACC_TIMING_SIZE_V2 ? size : static_cast<size_t>(DACC_TIMING_SIZE_V2))));
 	std::memcpy(static_cast<void *>(t),&c->timing,n);
 	return DACC_OK;
 }
@@ -1306,13 +1308,22 @@ int dacc_plan_only(dacc_params const * par, uint32_t const * rlen, uint64_t nrea
 // starved: give the buffer back and run the call once more without it -- the context keeps `nohand` set, so neither the planner of the
 // retried call nor growHandOver's "second use" allocation brings the buffer back.  Other failures (a device fault, internal error
 // flags, host allocation) are not retried: a second pass would only overwrite the first error's text.
+// The same holds for the slab of a trailing stage whose row names a budget of its own (TierStage::slab: the wide deep stage's, up to 2.1 GB): it is given back
+// with the hand-over buffer, the stage is off for the retried call (`noslab`) and for the rest of the context, and its windows run in k_window as before the stage.
 static bool dacc_drop_hand(dacc_ctx * c)
 {
 	if ( !c || !c->oom ) return false;
 	c->oom = false;
-	if ( !c->d_hand.p ) return false;
+	bool slabs = false;
+	for ( uint32_t i = 0; i < TIER_NROWS; ++i ) slabs = slabs || (TIER_CHAIN[i].slab && c->st[i].slab.p);
+	if ( !c->d_hand.p && !slabs ) return false;
 	(void)hipGetLastError(); hipSetDevice(c->device); (void)hipDeviceSynchronize(); (void)hipGetLastError();
-	c->d_hand.release(); c->handcap = 0; c->handwant = 0; c->nohand = true;
+	if ( c->d_hand.p ) { c->d_hand.release(); c->handcap = 0; c->handwant = 0; c->nohand = true; }
+	if ( slabs )
+	{
+		for ( uint32_t i = 0; i < TIER_NROWS; ++i ) if ( TIER_CHAIN[i].slab ) { c->st[i].slab.release(); c->TP.ok[i] = false; }
+		c->noslab = true;
+	}
 	return true;
 }
 int dacc_submit_piles(dacc_ctx * c, dacc_pile const * piles, uint64_t npiles, dacc_overlap const * ovl, uint64_t novl, void const * trace, uint64_t ntrace, int trace_bytes)

@@ -99,6 +99,7 @@ struct Context
 	DevBuf<uint32_t> d_longhand[2];     // what that stage hands on to k_window_long, one list per list of the second stream
 	// the hand-over buffer (dacc_submit_piles): slots it has, slots the batch wants, passes of this context so far; nohand: given up after an allocation failure
 	DevBuf<uint64_t> d_hand; DevBuf<uint32_t> d_handctr; uint32_t handcap = 0; uint64_t handwant = 0, nruns = 0; bool nohand = false, oom = false;
+	bool noslab = false;      // given up after an allocation failure: the slab of a trailing stage with a budget of its own (TierStage::slab)
 	bool tier7_adapt_off = false;
 	// the LDS tiers (tier_pipeline.hpp): their switches, the resolved chain of the current batch (capacities: BP.stageCaps), by TierId and the launch state of its stages.
 	// A main tier hands on through d_retry[slot] and is done at evslot[slot]; `handon` and `done` are those of the front tiers and of the trailing stages.

@@ -30,7 +30,7 @@
  *  - stretches are looked up by first / last node through small index arrays, the weights of a feasible (stretch,
  *    position) entry carry the weights of its end nodes, candidates are kept as stretch sequences and decoded once.
  *
- * The same code is instantiated for nineteen capacity tiers (FastTier<N> below; the layout FastLds<CT> is a compile time constant,
+ * The same code is instantiated for twenty capacity tiers (FastTier<N> below; the layout FastLds<CT> is a compile time constant,
  * so every LDS access has an immediate offset).  Which of them a batch runs, in which order and behind which switches, is
  * written down once, in tier_pipeline.hpp.
  *
@@ -54,6 +54,7 @@
  *     16  deepest stage, shallow and deep: 1001 ... 2000 strings      gw      16 / 16 bit       no LDS
  *     17  second stream, wide batches: strings of 129 ... 255 bases   gw      16 / 16 bit       no LDS
  *     18  full-depth stage, shallow and deep: 2001 ... 5001 strings   gw      16 / 16 bit       no LDS
+ *     19  wide deep stage, wide batches: 251 ... 1000 strings         gw      16 / 16 bit       no LDS
  *
  * processWindowFast returns
  * FW_NEXT when a window overflows a tier (flags say what overflowed: 1 instances, 2 nodes, 8 candidates, 16 walk,
@@ -254,6 +255,22 @@ static_assert(FastTier<18>::mins == VDEEP_MINS && FastTier<16>::maxs == FDEEP_MI
 // oneslab: the whole working set of a workgroup is ONE buffer whose first byte is the layout's (L.base); the weights, the spill image and the instance
 // image follow the layout (FastLds<CT>::g_base) instead of preceding it, so a caller that has one buffer of FastCaps::ldsbytes for a stage and no slab
 // (the emulation's ROLE_LONG stage) runs the tier as it is.  Tiers 13 ... 16 keep their addressing.
+// tier 19: the WIDE DEEP stage of wide batches, behind the last stage (tier 14) and in front of the generic engine (tier_pipeline.hpp: ID_WDEEP): the windows of
+// 251 ... 1000 strings at w = 64 ... 127, which tiers 8, 9 and 14 refuse at their string count (mins = 250: what tier 14 could have held is passed on as it came).
+// Tier 14's code -- two words per position mask, 128 symbol consensus, the consensus -> A alignment inside the kernel -- under tier 15's compile-time widths
+// (FastLds<CT>::wides: 10 bit string ids, 16 bit node frequencies capped at 1023, 32 bit nps, the 32 byte forward record, the two-pass instance generation, key
+// tables of 1024 entries).  What the combination widens: a feasible stretch has up to 128 nodes here, 128 x 1023 table words < 2^49, so the high part of a stretch
+// weight has 17 bits (FastEngine: SROWS, SWHB) and the reverse record's third word 17 + 10; path weights are sums of at most seqcap = 96 stretches, < 2^56, and
+// live in whole 64 bit words.  What else the wide windows of several hundred strings need, sized on the emulation (tests/wdeep_cases.py):
+//  - 131072 k-mer instances (FastLds<CT>::hranges: icap = 8 x precap in tier 16's 64 ranges by the first three symbols, each sorted with the sort of
+//    precap = 16384 keys that tiers 13 ... 18 have; 17 bit first slots in the compact string list): 1000 strings of 100 bases carry 73800 at k = 10;
+//  - 32 bit task and weight offsets (FastLds<CT>::toff32): 3000 stretches with up to 128 start positions are far more than 65535 tasks; 98304 weight records per direction;
+//  - 8190 nodes, 4096 stretches (the 13 bit node fields and the 12 bit stretch number of the stretch sort key), 16384 links;
+//  - reverse pool of 16384 paths in 256 chunks of rch = 64: an enumeration's 32 chunk ids then name 2048 paths, where 512 sent 71 of 77 windows of a pile on;
+//    lscrids = 16384, so that the retry of a pending-path heap on the whole scratch holds every path of the pool;
+//  - the per-unit words of the stretch feasibility in device memory, as in tier 18 (128 chunks would be 512 registers).
+template<> struct FastTier<19> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 4000, gw = 1, wcapg = 98304, rch = 64, fch = 16, fnw = 4, fnc = 72, idmax = 8000, rpstcap = 768, lstr = 128, maxs = 1000, precap = 16384, ncap = 8190, scap = 4096, lcap = 16384, wcap = 98304, rccap = 16384, fcap = 2048, siqcap = 512, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 16384, wide = 1, mins = 250, gmem = 1 }; };
+static_assert(FastTier<19>::mins == VDEEP_MINS && FastTier<14>::maxs == VDEEP_MINS && FastTier<19>::maxs == FastTier<15>::maxs,"the wide deep stage takes what the last stage of a wide batch refuses at its string count");
 template<> struct FastTier<17> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 1000, gw = 1, wcapg = 16384, rch = 16, fch = 16, fnw = 8, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 256, maxs = 250, precap = 16384, ncap = 6144, scap = 1024, lcap = 8192, wcap = 16384, rccap = 4096, fcap = 4096, siqcap = 512, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 4096, wide = 1, mins = 0, gmem = 1, oneslab = 1 }; };
 // (only tier 17 names the enumerator: for every other tier FastOneSlab<CT>::value is 0)
 template<typename CT, typename = void> struct FastOneSlab { enum : uint32_t { value = 0 }; };
@@ -282,7 +299,7 @@ struct FastLds<CT,false>
 {
 	LDSQ uint8_t * base;
 	static constexpr uint32_t keycap = fcpow2(CT::maxs < 2 ? 2 : CT::maxs);
-	typedef uint16_t toff_t; static constexpr bool wides = false, xwides = false, ywides = false; static constexpr uint32_t fqmax = 255u, icap = CT::precap;      // (more than 256 strings: gw layout only)
+	typedef uint16_t toff_t; static constexpr bool wides = false, xwides = false, ywides = false, hranges = false; static constexpr uint32_t fqmax = 255u, icap = CT::precap;      // (more than 256 strings: gw layout only)
 	static_assert(CT::maxs <= 256,"the legacy layout has 8 bit node frequencies and string ids");
 	static_assert((CT::precap & (CT::precap-1)) == 0,"precap must be a power of two: the bitonic sorts pad to one");
 	static_assert(sizeof(typename CT::id_t) > 1 || (CT::fcap <= 256 && CT::rccap <= 256),"pool slots are recorded as id_t (pout)");
@@ -504,9 +521,14 @@ struct FastLds<CT,true>
 	static constexpr bool ywides = CT::maxs > 2048;
 	static constexpr uint32_t fqmax = xwides ? 4095u : (wides ? 1023u : 255u);
 	// k-mer instances the layout holds: precap, the capacity of one instance sort -- with more than 256 strings four such ranges, with more than
-	// 1024 strings 64 ranges that share eight times precap, with more than 2048 strings 256 ranges that share sixteen times precap (buildInstances)
-	static constexpr uint32_t icap = ywides ? 16u*CT::precap : (xwides ? 8u*CT::precap : (wides ? 4u*CT::precap : CT::precap));
-	typedef typename FWideSel<xwides,uint32_t,uint16_t>::type toff_t;
+	// 1024 strings 64 ranges that share eight times precap, with more than 2048 strings 256 ranges that share sixteen times precap (buildInstances).
+	// hranges: the ranges are counted by a histogram pass.  The wide tier of more than 256 strings as well: its strings are up to twice as long, and
+	// 792 strings of 100 bases have more than precap instances in each of four ranges
+	static constexpr bool hranges = xwides || (wides && CT::wide != 0);
+	static constexpr uint32_t icap = ywides ? 16u*CT::precap : (hranges ? 8u*CT::precap : (wides ? 4u*CT::precap : CT::precap));
+	// (the wide tier of more than 256 strings as well: a traversal of 1300 stretches has 2 x 1300 x up to 128 (stretch, direction, position) tasks)
+	static constexpr bool toff32 = xwides || (wides && CT::wide != 0);
+	typedef typename FWideSel<toff32,uint32_t,uint16_t>::type toff_t;
 	typedef typename FWideSel<wides,uint16_t,uint8_t>::type nfreq_t;
 	typedef typename FWideSel<wides,uint32_t,uint16_t>::type nps_t;
 	static_assert(fqmax <= (1u << (8u*sizeof(nfreq_t))) - 1u,"a node frequency holds fqmax");
@@ -1025,10 +1047,10 @@ struct FastEngine
 		enum : bool { GENMARKS = true };
 #endif
 		// compact string list entry: string | first slot << CLB.  8 bit string ids and 24 bit slots; more than 256 strings: 10 bit ids, 16 bit slots
-		// (a first slot is below npre <= 65536); more than 1024 strings: 11 bit ids, 17 bit slots (npre <= 131072); more than 2048 strings: 13 bit ids,
-		// 18 bit slots (npre <= 262144)
-		enum : bool { WIDES = FastLds<CT>::wides, XWIDES = FastLds<CT>::xwides, YWIDES = FastLds<CT>::ywides };
-		enum : uint32_t { CLB = YWIDES ? 13u : (XWIDES ? 11u : (WIDES ? 10u : 8u)), CLSLOTB = YWIDES ? 18u : (XWIDES ? 17u : (WIDES ? 16u : 24u)), CLMASK = (1u << CLB) - 1u };
+		// (a first slot is below npre <= 65536; the wide tier of more than 256 strings, npre <= 131072: 17 bit slots); more than 1024 strings: 11 bit ids,
+		// 17 bit slots (npre <= 131072); more than 2048 strings: 13 bit ids, 18 bit slots (npre <= 262144)
+		enum : bool { WIDES = FastLds<CT>::wides, XWIDES = FastLds<CT>::xwides, YWIDES = FastLds<CT>::ywides, HRANGES = FastLds<CT>::hranges };
+		enum : uint32_t { CLB = YWIDES ? 13u : (XWIDES ? 11u : (WIDES ? 10u : 8u)), CLSLOTB = YWIDES ? 18u : ((XWIDES || FastLds<CT>::icap > 65536u) ? 17u : (WIDES ? 16u : 24u)), CLMASK = (1u << CLB) - 1u };
 		static_assert(4u*CT::maxs <= FastLds<CT>::icap && CT::maxs <= (1u << CLB) && FastLds<CT>::icap <= (1u << CLSLOTB) && CLB + CLSLOTB <= 32u,"compact string list: string | first slot << CLB, in the bytes of irpos");
 		static_assert(!WIDES || GENMARKS,"the two-pass generation of more than 256 strings needs the marks");
 		LDSQ uint8_t * const marks = L.ipos();                                             // free until buildNodes writes the positions
@@ -1171,7 +1193,7 @@ struct FastEngine
 		SITE(31)      // buildInstances: generation of the k-mer instances (lane = instance)
 		wv_sort_keys<FastLds<CT>::keycap>(L.lastk(),nlast);
 		SITE(32)      // buildInstances: sort of the last k-mers
-		if constexpr ( XWIDES )
+		if constexpr ( HRANGES )
 		{
 			// Up to 8 x precap instances in 64 ranges by the first three symbols of the k-mer (the six highest bits of the key; k >= 3), range r behind
 			// range r-1, each sorted on its own with the sort of precap keys.  A histogram pass counts the ranges -- a counter per range in the bytes
@@ -1985,7 +2007,8 @@ struct FastEngine
 		// (the four words of unit cc*WSZ + lane: registers, every loop over the chunks is unrolled.  More than 2048 strings -- 384 chunks --: words of device
 		// memory instead, in the bytes of the generation's instance array, which nothing reads between two builds of the instances; a lane reads back
 		// only what it wrote itself)
-		enum : bool { UMEM = FastLds<CT>::ywides };
+		// (the wide tier of more than 256 strings, 4096 stretches of up to 128 start positions: device memory as well -- 128 chunks would be 512 registers)
+		enum : bool { UMEM = FastLds<CT>::ywides || (FastLds<CT>::wides && CT::wide != 0) };
 		struct UTab { LDSQ uint32_t * p; DEV uint32_t & operator[](uint32_t const cc) const { return p[cc*WSZ]; } };
 		typedef typename FWideSel<UMEM,UTab,uint32_t[NCHU]>::type utab_t;
 		utab_t ulo_r, uw_r, ucls_r, upos_r;
@@ -2219,10 +2242,15 @@ struct FastEngine
 	// word: a path has at most FSEQCAP stretches (< 2^54).
 	// (more than 1024 strings, fqmax = 4095: node weight < 2^44, 12 bit high part; stretch weight < 2^50, 18 bit high part -- SWHB; the forward record
 	// of that tier holds whole 64 bit words, the reverse record's third word 18 + 12 bits)
+	// (the nodes of a feasible stretch: one per row of the model table the tier admits -- nrows <= 128 in a wide tier, 64 otherwise (resolveTiers).  A wide tier of
+	// more than 256 strings, fqmax = 1023 at 128 nodes: stretch weight < 2^49, 17 bit high part, the reverse record's third word 17 + 10 bits; the wide tiers of
+	// up to 250 strings, fqmax = 255 at 128 nodes, stay below 2^47 and keep their 16 bits)
 	enum : uint32_t { FQMAX = FastLds<CT>::fqmax, NWHB = FQMAX <= 255u ? 8u : (FQMAX <= 1023u ? 10u : 12u), NWHMASK = (1u << NWHB) - 1u,
-		SWHB = FQMAX <= 1023u ? 16u : 18u, SWHMASK = (1u << SWHB) - 1u };
+		SROWS = CT::wide ? 128u : 64u,
+		SWHB = FQMAX <= 1023u ? ((SROWS*FQMAX) >> 16 ? 17u : 16u) : 18u, SWHMASK = (1u << SWHB) - 1u };
 	static_assert((static_cast<uint64_t>(FQMAX)*0xFFFFFFFFull) >> (32u+NWHB) == 0,"high part of a node weight: fqmax table words");
-	static_assert((64ull*static_cast<uint64_t>(FQMAX)*0xFFFFFFFFull) >> (32u+SWHB) == 0,"high part of a stretch weight: 64 nodes");
+	static_assert((static_cast<uint64_t>(SROWS)*static_cast<uint64_t>(FQMAX)*0xFFFFFFFFull) >> (32u+SWHB) == 0,"high part of a stretch weight: SROWS nodes of fqmax table words each, SROWS = 128 rows of the model table in a wide tier and 64 otherwise");
+	static_assert(!FastLds<CT>::xwides || CT::wide == 0,"more than 1024 strings in a wide tier: 128 x 4095 table words need a 19 bit high part");
 	static_assert(SWHB + NWHB <= 32u,"reverse record: both high parts in its third word");
 	static_assert(SWHB == 16u || FastLds<CT>::wides,"a stretch weight of more than 48 bits needs the 32 byte forward record");
 	static_assert(CT::maxs <= 1024 || (FastLds<CT>::fqmax == 4095u && FastLds<CT>::icap == (FastLds<CT>::ywides ? 16u : 8u)*CT::precap && FastLds<CT>::xwides),"more than 1024 strings: the widths of FastLds<CT>::xwides");

@@ -10,7 +10,7 @@
  *   shallow and deep  tier 5 on the second stream (k_window_long), in front of the generic engine there
  *   wide batches      the LONG STRING stage on the second stream: tier 17 (strings of 129 ... 255 bases, layout in device memory), in front of the generic engine there
  *   every batch       the TRAILING stages, each once, behind the slots and in front of the generic engine: tier 13 (shallow, deep) / tier 14 (wide), then in
- *                     shallow and deep batches tier 15, tier 16 and tier 18, each only in a batch with a window deep enough for it
+ *                     shallow and deep batches tier 15, tier 16 and tier 18 and in wide batches tier 19, each only in a batch with a window deep enough for it
  *
  * (TIER_CHAIN below: one row per stage, one column per batch shape.)
  *
@@ -41,6 +41,9 @@
  *                                          default run), and those of 251 ... 2000 that                             tier 9)
  *                                          overflowed a table of tier 16; those of at most
  *                                          250 passed on
+ *   ID_WDEEP   19 (wide)                   251 ... 1000 strings of a wide batch, which tiers  DACC_WDEEP_TIER   DACC_WDEEP_AS_SLOT2 (19 for 9; a shallow  VDEEP_MINS = 250
+ *                                          8, 9 and 14 refuse at their string count; those                      or deep batch keeps tier 3)
+ *                                          of at most 250 passed on
  *
  * The LONG STRING stage (ID_LONG in a wide batch, ROLE_LONG) runs tier 17 -- tier 14 with four words per pattern mask, strings of up to 255 bases -- over the
  * two lists of the second stream (the pre-scan's: a B string of more than 128 bases; the first tier's generic-only windows) with a kernel of its own,
@@ -71,7 +74,7 @@ enum : uint32_t { T0INST_DEFAULT = 576, T7INST_DEFAULT = 704 };      // a window
                                                // arguments of the pre-pass (DACC_T0INST / DACC_T7INST override them for sweeps)
 
 // The tiers.  KERNEL: those with a kernel of their own (k_window_fast<N>, window_kernels.hpp); tier 5 runs inside k_window_long.
-#define DACC_KERNEL_TIERS(X) X(0) X(1) X(2) X(3) X(4) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18)
+#define DACC_KERNEL_TIERS(X) X(0) X(1) X(2) X(3) X(4) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19)
 #define DACC_ALL_TIERS(X) DACC_KERNEL_TIERS(X) X(5)
 
 // From a run-time tier number to its compile-time capacities: f is called with a TierTag<N>, whose `type` is FastTier<N>
@@ -112,19 +115,27 @@ enum : uint32_t { WORK_SLOT0 = 0, WORK_SLOT1 = 8, WORK_SLOT2 = 16, WORK_DENSE = 
 	WORK_XDEEP_COUNT = 112,    // two words: windows of more than VDEEP_MINS strings the deepest stage read / handed on (for dacc_timing)
 	WORK_FDEEP = 120,
 	WORK_FDEEP_COUNT = 128,    // two words: windows of more than VDEEP_MINS strings the full-depth stage read / handed on (for dacc_timing)
+	WORK_WDEEP = 136,
+	WORK_WDEEP_COUNT = 144,    // two words: windows of more than VDEEP_MINS strings the wide deep stage read / handed on (for dacc_timing)
 	// (everything above is the first stream's and cleared at the start of every pass; the second stream clears what follows in front of its launches)
-	WORK_LONGSTR = 136,        // the long string stage's launch over the pre-scan list, WORK_LONGSTR + 8: its launch over the first tier's generic-only list
-	WORK_WORDS = 152 };
+	WORK_LONGSTR = 152,        // the long string stage's launch over the pre-scan list, WORK_LONGSTR + 8: its launch over the first tier's generic-only list
+	WORK_WORDS = 168 };
 
-// The stages, in the order they run (ID_FDEEP runs behind ID_XDEEP: the trailing stages run in the order of their rows, and no row between them is one); their
+// The stages, in the order they run (ID_FDEEP runs behind ID_XDEEP and ID_WDEEP behind that: the trailing stages run in the order of their rows, and no row between them is one; in a
+// wide batch ID_WDEEP stands directly behind ID_LAST, the rows between them have no wide tier); their
 // place in this table is their place in BatchPlan::stageCaps, TierPipeline and dacc_ctx::st.  TIER_NSTAGES counts the rows up to ID_LONG, which is what a caller
 // that holds one capacity record per stage in an array of TIER_NSTAGES walks (the emulation harness, tests/tiers/tier_resolution.cpp and its recording of one
 // column per stage); the rows added since stand behind it, TIER_NROWS counts all, and resolveTiers resolves them for a caller that says it holds them (`rows`).
-enum TierId { ID_T0, ID_T7, ID_SLOT0, ID_SLOT1, ID_DENSE, ID_DEEP, ID_SLOT2, ID_LAST, ID_VDEEP, ID_XDEEP, ID_LONG, TIER_NSTAGES, ID_FDEEP = TIER_NSTAGES, TIER_NROWS };
+enum TierId { ID_T0, ID_T7, ID_SLOT0, ID_SLOT1, ID_DENSE, ID_DEEP, ID_SLOT2, ID_LAST, ID_VDEEP, ID_XDEEP, ID_LONG, TIER_NSTAGES, ID_FDEEP = TIER_NSTAGES, ID_WDEEP, TIER_NROWS };
 enum { TIER_NSLOTS = 3, TIER_NONE = 255, TIER_SHALLOW_FIRST = 1 };      // (the first slot's main tier of shallow batches: a batch whose windows mostly overflow its strings / instances is deep)
 enum : uint32_t { VDEEP_MINS = 250 };      // the very deep stage takes the windows with more strings than this (= FastTier<15>::mins = FastTier<13>::maxs, fast_window.hpp)
 enum : uint32_t { XDEEP_MINS = 1000 };     // the deepest stage is resolved for a batch with a window of more strings than this (= FastTier<15>::maxs); its tier takes what has more than VDEEP_MINS
 enum : uint32_t { FDEEP_MINS = 2000 };     // the full-depth stage is resolved for a batch with a window of more strings than this (= FastTier<16>::maxs); its tier takes what has more than VDEEP_MINS
+enum : uint64_t { TIER_GMEM_SLAB = 256ull << 20 };      // device memory the slabs of a device-memory tier's workgroups take together (tierGridGmem below)
+// The wide deep stage's budget: tier 19's slab is 8 884 992 B per workgroup, 24 workgroups in 256 MiB -- measured on an MI355X, 24 wavefronts are slower than the wavefront per
+// window k_window gives the same windows (profiles/wdeep_measurements.md).  2 GiB hold 240 workgroups, about one per CU; a batch that has such windows is one whose generic
+// engine asks for arenas of 200 MB per wavefront.  The slab is allocated for the grid, a workgroup per window of the batch up to that, and is optional like the others.
+enum : uint64_t { WDEEP_GMEM_SLAB = 2048ull << 20 };
 struct TierStage
 {
 	uint8_t tier[3] /* in a shallow, deep, wide batch */, slot, role; int8_t tiersbit /* bit of DACC_TIERS */; uint32_t flags, work;
@@ -133,6 +144,8 @@ struct TierStage
 	char const * slot2switch = nullptr;    // DACC_*_AS_SLOT2: 1 makes its tier the main tier of the third slot and switches the stage off
 	uint32_t minstrings = 0;               // resolved only for a batch whose deepest window has more strings than this (0: every batch)
 	bool slot2wide = false;                // does its AS_SLOT2 switch apply to a wide batch (else that keeps tier 9)
+	bool slot2narrow = true;               // does it apply to a shallow or deep batch (else that keeps tier 3)
+	uint64_t slab = 0;                     // bytes of device memory its workgroups' slabs may take together (0: TIER_GMEM_SLAB)
 };
 static TierStage const TIER_CHAIN[TIER_NROWS] = {
 	{ { 0, TIER_NONE, TIER_NONE }, 0, ROLE_FRONT, 3, STAGE_PREPASS, WORK_T0 },
@@ -149,7 +162,9 @@ static TierStage const TIER_CHAIN[TIER_NROWS] = {
 	// memory, and the generic engine behind it)
 	{ { 5, 5, 17 }, 0, ROLE_LONG, 2, GATE_TABFIT|GATE_LONGSTR, WORK_LONGSTR },
 	// (behind TIER_NSTAGES; it runs behind ID_XDEEP)
-	{ { 18, 18, TIER_NONE }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_TRAILING, WORK_FDEEP, "DACC_FDEEP_TIER", "DACC_FDEEP_AS_SLOT2", FDEEP_MINS, false } };
+	{ { 18, 18, TIER_NONE }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_TRAILING, WORK_FDEEP, "DACC_FDEEP_TIER", "DACC_FDEEP_AS_SLOT2", FDEEP_MINS, false },
+	// (the wide batches' very deep stage: behind ID_LAST's tier 14 there.  The wide column of ID_VDEEP stays empty: a caller that walks TIER_NSTAGES rows resolves what it resolved)
+	{ { TIER_NONE, TIER_NONE, 19 }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_TRAILING, WORK_WDEEP, "DACC_WDEEP_TIER", "DACC_WDEEP_AS_SLOT2", VDEEP_MINS, true, false, WDEEP_GMEM_SLAB } };
 static TierId const TIER_MAIN[TIER_NSLOTS] = { ID_SLOT0, ID_SLOT1, ID_SLOT2 };
 // does the stage run in a batch of this shape, and the tier whose capacities the plan holds for it (a stage that does not run keeps
 // those of the nearest shape: the first slot of a wide batch has tier 1's or tier 4's)
@@ -159,8 +174,9 @@ static inline bool stageAsSlot2(TierStage const & st) { char const * const e = s
 static inline uint32_t stageTier(TierStage const & st, bool const deep, bool const wide)
 {
 	TierStage const * t = &st;
-	if ( &st == &TIER_CHAIN[ID_SLOT2] ) for ( TierStage const & r : TIER_CHAIN ) if ( stageAsSlot2(r) && (!wide || r.slot2wide) ) { t = &r; break; }
-	return (wide && t->tier[2] != TIER_NONE) ? t->tier[2] : (t->tier[deep] != TIER_NONE ? t->tier[deep] : t->tier[0]);
+	if ( &st == &TIER_CHAIN[ID_SLOT2] ) for ( TierStage const & r : TIER_CHAIN ) if ( stageAsSlot2(r) && (wide ? r.slot2wide : r.slot2narrow) ) { t = &r; break; }
+	// (a row with a wide tier only -- ID_WDEEP -- keeps that tier's capacities in the other shapes, where it does not run)
+	return (wide && t->tier[2] != TIER_NONE) ? t->tier[2] : (t->tier[deep] != TIER_NONE ? t->tier[deep] : (t->tier[0] != TIER_NONE ? t->tier[0] : t->tier[2]));
 }
 
 // the environment switches of the chain, read once per context
@@ -204,15 +220,15 @@ static inline uint32_t tierGrid(uint32_t const ldsbytes, uint64_t const nwindows
 }
 
 // Launch geometry of a device-memory tier (FastCaps::gmem): no LDS and 512 registers, so up to four workgroups per CU would fit; what bounds the
-// grid is the slab, gbytes per workgroup (tier 13: 1 059 840 B, tier 14: 1 125 632 B, tiers 15, 16 and 18: see DESIGN 3.2), kept to TIER_GMEM_SLAB = 256 MiB per context:
+// grid is the slab, gbytes per workgroup (tier 13: 1 059 840 B, tier 14: 1 125 632 B, tiers 15, 16, 18 and 19: see DESIGN 3.2), kept to TIER_GMEM_SLAB = 256 MiB per context:
 // 256 MiB / 1 059 840 B = 253 -> 248 workgroups (a multiple of 8, one share per XCD), 232 for tier 14 -- about one per CU, whose working sets
 // (1 MB each) then share the L2 of their XCD with no more than 31 others.  The stage sees a few windows per batch, hundreds on high-error data;
 // a small batch gets a workgroup per window and a slab to match.
-enum : uint64_t { TIER_GMEM_SLAB = 256ull << 20 };
-static inline uint32_t tierGridGmem(uint32_t const gbytes, uint64_t const nwindows)
+// (a row of TIER_CHAIN may name a budget of its own, TierStage::slab: the wide deep stage's 2 GiB, see WDEEP_GMEM_SLAB)
+static inline uint32_t tierGridGmem(uint32_t const gbytes, uint64_t const nwindows, uint64_t const slab = TIER_GMEM_SLAB)
 {
 	uint64_t g = std::min<uint64_t>(1024,std::max<uint64_t>(8,((nwindows+7)/8)*8));
-	uint64_t const fit = (TIER_GMEM_SLAB / (gbytes ? gbytes : 1)) & ~7ull;
+	uint64_t const fit = ((slab ? slab : static_cast<uint64_t>(TIER_GMEM_SLAB)) / (gbytes ? gbytes : 1)) & ~7ull;
 	return static_cast<uint32_t>(std::max<uint64_t>(8,std::min<uint64_t>(g,fit)));
 }
 

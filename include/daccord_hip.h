@@ -232,16 +232,27 @@ typedef struct dacc_timing {
 	uint32_t fdeep_windows;  /* windows of more than 250 strings that finished in it */
 	uint32_t fdeep_out;      /* windows of more than 250 strings it handed on to k_window (more than 5001 strings, a k-mer seen more than 4095 times, k = 3, a table beyond its capacities) */
 	uint32_t pad3_;
+	/* ---- everything above: 208 bytes, the record before the wide deep stage ---- */
+	/* the wide deep stage: k_window_fast<19> (layout in device memory, windows of 251 ... 1000 strings at -w 64 ... 127), behind the last stage (<14>) and in front of
+	   k_window; launched only in a wide batch whose deepest window has more than 250 strings; not a part of tier_ms[] */
+	float wdeep_ms;          /* its kernel; 0 if it did not run (no window of more than 250 strings in the batch, a shallow or deep batch, DACC_WDEEP_TIER=0, DACC_WDEEP_AS_SLOT2=1, no slot ran,
+	                            no memory for its slab) */
+	uint32_t wdeep_windows;  /* windows of more than 250 strings that finished in it */
+	uint32_t wdeep_out;      /* windows of more than 250 strings it handed on to k_window (more than 1000 strings, a k-mer seen more than 1023 times, a table beyond its capacities);
+	                            where it ran, wdeep_windows + wdeep_out are the windows of more than 250 strings the last stage handed on: those the second stream does not have */
+	uint32_t pad4_;
 } dacc_timing;
 #define DACC_TIMING_SIZE_V1 128
 #define DACC_TIMING_SIZE_V2 176   /* the record in front of longstr_ms */
 #define DACC_TIMING_SIZE_V3 192   /* the record in front of fdeep_ms */
+#define DACC_TIMING_SIZE_V4 208   /* the record in front of wdeep_ms */
 /* dacc_last_timing fills the first DACC_TIMING_SIZE_V1 bytes only (the record as it was when the call was introduced: a caller built against
  * an older header is never overrun).  dacc_last_timing2 copies min(size, sizeof(dacc_timing)) bytes: pass sizeof(dacc_timing) of the header
  * the caller was compiled with; fields the library does not know stay as the caller set them.  The 16 bytes behind emit_ms (the long string
  * stage) are copied only when size covers all of them: a size in [DACC_TIMING_SIZE_V2, DACC_TIMING_SIZE_V3) copies DACC_TIMING_SIZE_V2
  * bytes, so that a caller of the 176 byte record who passes the size of a larger buffer of its own gets what it got before.  The same rule holds
- * for the 16 bytes behind pad2_ (the full-depth stage): a size in [DACC_TIMING_SIZE_V3, sizeof(dacc_timing)) copies DACC_TIMING_SIZE_V3 bytes. */
+ * for the 16 bytes behind pad2_ (the full-depth stage): a size in [DACC_TIMING_SIZE_V3, DACC_TIMING_SIZE_V4) copies DACC_TIMING_SIZE_V3 bytes; and for
+ * the 16 bytes behind pad3_ (the wide deep stage): a size in [DACC_TIMING_SIZE_V4, sizeof(dacc_timing)) copies DACC_TIMING_SIZE_V4 bytes. */
 int  dacc_last_timing(dacc_ctx *ctx, dacc_timing *t);
 int  dacc_last_timing2(dacc_ctx *ctx, dacc_timing *t, size_t size);
 
