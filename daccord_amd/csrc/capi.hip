@@ -396,6 +396,7 @@ int dacc_create(dacc_ctx ** out, dacc_params const * p)
 	char const * ta = getenv("DACC_T7_ADAPT"); c->env_t7adapt = !(ta && ta[0] == '0');      // 0: tier 7 stays on whatever it hands on
 	char const * dr = getenv("DACC_DEBUG_RETRY"); c->env_dbgretry = (dr && dr[0] == '1');
 	{ char const * fn = getenv("DACC_FEAS_NEED"); c->env_feasneed = (fn && fn[0] == '0') ? 0u : 1u; }
+	{ char const * tf = getenv("DACC_TIE_FAST"); c->env_tiefast = (tf && tf[0] == '0') ? 0u : 1u; }
 	// (a failure from here on: `delete c` destroys what has been created)
 	if ( hipStreamCreate(&c->stream.h) != hipSuccess ) { delete c; return DACC_EHIP; }
 	{ int lo = 0, hi = 0; hipDeviceGetStreamPriorityRange(&lo,&hi); if ( hipStreamCreateWithPriority(&c->stream2.h,hipStreamNonBlocking,hi) != hipSuccess ) { delete c; return DACC_EHIP; } }
@@ -525,7 +526,7 @@ static WindowBatch windowBatch(dacc_ctx * c)
 // slots and the ledger mask.  What differs from launch to launch (hand-on list, early list, slab and stride, pregen map, arena) is stated where the launch is
 static FastBatch stageBatch(dacc_ctx * c, WindowBatch const & WB, uint32_t const id, bool const chain = true)
 {
-	FastBatch FB; FB.W = WB; FB.F = c->BP.stageCaps(id); FB.dpsq_vst = c->d_vst.p; FB.tab32 = c->d_tab32.p; FB.feasneed = c->env_feasneed;
+	FastBatch FB; FB.W = WB; FB.F = c->BP.stageCaps(id); FB.dpsq_vst = c->d_vst.p; FB.tab32 = c->d_tab32.p; FB.feasneed = c->env_feasneed; FB.tiefast = c->env_tiefast;
 	if ( !chain ) return FB;
 	// (a wide batch has handcap == 0, dacc_submit_piles: its hand-overs go to the generic engine, which sorts for itself)
 	FB.hand = c->handcap ? c->d_hand.p : static_cast<uint64_t *>(0); FB.handctr = c->d_handctr.p; FB.handcap = c->handcap; FB.handwords = c->TP.handwords;

@@ -113,6 +113,7 @@ struct Context
 	uint32_t tr_grid = 0, tr_lds = 0, tr_words = 0, tr_lanes = 0, trace_bytes = 0, win_grid = 0;
 	int env_sched = 1, env_dbgretry = 0, env_t7adapt = 1, env_trdyn = 1;     // debugging knobs, read once in dacc_create
 	uint32_t env_feasneed = 1;       // DACC_FEAS_NEED=0: stretch feasibility of every (stretch, direction, position) instead of what the enumerations can read (A/B runs, tests)
+	uint32_t env_tiefast = 1;        // DACC_TIE_FAST=0: kept candidates of equal weight always take lane 0's two heaps (A/B runs, tests)
 	std::vector<uint32_t> retry_flags;                      // DACC_DEBUG_RETRY: (window, flags) of what the last LDS tier handed on
 	std::vector<dacc_fragment> frags; std::string bases;
 	std::vector<int32_t> pile_status; std::vector<std::string> pile_errors; std::string pile_errors_joined;

@@ -746,6 +746,7 @@ struct FastBatch
 	// the window up loads them instead of generating and sorting them again.  hand == 0: every hand-over restarts from the strings.
 	uint64_t * hand = 0; uint32_t * handctr = 0; uint32_t handcap = 0, handwords = 0;
 	uint32_t feasneed = 1;          // the product default; 0: stretch feasibility of every (stretch, direction, position), as before the filter (DACC_FEAS_NEED=0: A/B runs and tests)
+	uint32_t tiefast = 1;           // the product default; 0: every window with two kept candidates of one weight orders them with lane 0's two heaps, as before the lane-parallel tie rank (DACC_TIE_FAST=0: A/B runs and tests)
 #if defined(DACC_LEDGER)
 	uint32_t ledger = 0;            // instruction ledger build (scripts/ledger.py): bit p set = phase p of every window runs twice
 #endif
@@ -779,13 +780,13 @@ DEV void fast_load_tables(FastLds<CT> const & L, uint32_t const nrows, uint32_t 
 
 #if defined(DACC_EMUL)
 // emulation only: per-window maxima of the variable-size structures (design aid, DACC_EMUL_STATS=<file>)
-struct FastStats { uint32_t v[32]; void clear() { for ( int i = 0; i < 32; ++i ) v[i] = 0; } void mx(int i, uint32_t x) { if ( x > v[i] ) v[i] = x; } void add(int i, uint32_t x) { v[i] += x; } };
+struct FastStats { enum { N = 33 }; uint32_t v[N]; void clear() { for ( int i = 0; i < N; ++i ) v[i] = 0; } void mx(int i, uint32_t x) { if ( x > v[i] ) v[i] = x; } void add(int i, uint32_t x) { v[i] += x; } };
 static FastStats g_fstats;
 static inline void fstats_dump(int const tier)
 {
 	static FILE * sf = 0; static bool tried = false;
 	if ( !tried ) { tried = true; char const * fn = getenv("DACC_EMUL_STATS"); if ( fn ) sf = fopen(fn,"w"); }
-	if ( sf ) { fprintf(sf,"%d",tier); for ( int i = 0; i < 32; ++i ) fprintf(sf," %u",g_fstats.v[i]); fprintf(sf,"\n"); fflush(sf); }
+	if ( sf ) { fprintf(sf,"%d",tier); for ( int i = 0; i < FastStats::N; ++i ) fprintf(sf," %u",g_fstats.v[i]); fprintf(sf,"\n"); fflush(sf); }
 }
 static inline FILE * ftrav_file() { static FILE * f = 0; static bool tried = false; if ( !tried ) { tried = true; char const * fn = getenv("DACC_EMUL_TRAV"); if ( fn ) f = fopen(fn,"w"); } return f; }
 #define FSTAT_MX(i,x) g_fstats.mx(i,x)
@@ -956,15 +957,18 @@ struct FastEngine
 	uint32_t n0, npool, nlinks, nwF, nwR;
 	uint32_t nF, nL;
 	uint32_t feasneed;           // FastBatch::feasneed
+	uint32_t tiefast;            // FastBatch::tiefast
 
 #if defined(DACC_EMUL)
 	// emulation only: the filter's switch is read from the environment at every traversal (a test runs both settings in one process); feascount marks
 	// the count-only pass of computeStretchFeasLanes that gives the traversal trace (DACC_EMUL_TRAV) its unfiltered numbers of weight records
 	bool feascount, feasapplied; uint32_t nwFall, nwRall;
 	DEV bool feasNeedOn() const { char const * e = getenv("DACC_FEAS_NEED"); return !(e && e[0] == '0'); }
+	DEV bool tieFastOn() const { char const * e = getenv("DACC_TIE_FAST"); return !(e && e[0] == '0'); }
 #else
 	static constexpr bool feascount = false;
 	DEV bool feasNeedOn() const { return feasneed != 0; }
+	DEV bool tieFastOn() const { return tiefast != 0; }
 #endif
 #if defined(DACC_EMUL)
 	// emulation only: DACC_EMUL_OVER=1 reports where a tier overflowed
@@ -1673,7 +1677,14 @@ struct FastEngine
 		if ( wv_any(dup) ) { over(32); n0 = 0; return; }
 		n0 = ns;
 		wv_sync();
-		// lookup by first node (base order is sorted by it) and by last node (ordered by (last, id))
+	}
+	// lookup of the base stretches by first node (base order is sorted by it) and by last node (ordered by (last, id)).  Nothing in front
+	// of the reachability test of traverse() reads them, nor do the over() checks: a state without a first -> last walk never gets them.
+	DEV void computeStretchLookups()
+	{
+		uint32_t const ns = n0, p2 = next_pow2(ns < 2 ? 2 : ns);
+		LEDGER_REP(20)
+		{
 		for ( uint32_t z = lane; z < nn; z += WSZ ) { L.npred()[z] = SNONE; L.lhead()[z] = SNONE; }
 		for ( uint32_t q = lane; q < p2; q += WSZ ) L.skey()[q] = q < ns ? ((static_cast<uint64_t>(L.slast()[q])<<SB) | q) : ~0ull;
 		wv_sync();
@@ -1686,6 +1697,7 @@ struct FastEngine
 			if ( q == 0 || (L.skey()[q-1]>>SB) != (e>>SB) ) L.lhead()[e>>SB] = q;
 		}
 		wv_sync();
+		}
 	}
 
 	// pool stretch id = nodes [a,b] of parent stretch par
@@ -1757,30 +1769,8 @@ struct FastEngine
 			for ( uint32_t c = 0; c < nF; ++c ) cnt += (L.parF()[c] != SNONE);
 			for ( uint32_t c = 0; c < nL; ++c ) cnt += (L.parL()[c] != SNONE);
 			if ( n0 + 2*cnt + 1 > CT::scap || n0 + 2*cnt + 1 > SMAX ) { over(32); return; }
+			npool = n0 + 2*cnt;      // two pool ids per candidate that splits a stretch: makePieces()
 		}
-		{
-			// pieces of the candidates that split a stretch, one lane per candidate (first k-mers, then last k-mers): two
-			// pool ids each, numbered in candidate order
-			uint32_t id = n0;
-			for ( uint32_t c0 = 0; c0 < nF + nL; c0 += WSZ )
-			{
-				uint32_t const c = c0 + lane;
-				bool const isF = c < nF, act = c < nF + nL;
-				uint32_t const ci = isF ? c : c - nF;
-				uint32_t const par = act ? (isF ? L.parF()[ci] : L.parL()[ci]) : static_cast<uint32_t>(SNONE);
-				bool const has = act && par != SNONE;
-				uint32_t tot; uint32_t const pre = wv_scan_flag(has,tot);
-				if ( has )
-				{
-					uint32_t const pid = id + 2*pre, pos = isF ? L.posF()[ci] : L.posL()[ci];
-					if ( isF ) L.pieF()[ci] = pid; else L.pieL()[ci] = pid;
-					makePiece(pid,par,0,pos); makePiece(pid+1,par,pos,L.sslen()[par]-1);
-				}
-				id += 2*tot;
-			}
-			npool = id;
-		}
-		wv_sync();
 		// Middle pieces.  A first and a last k-mer candidate that lie strictly inside the SAME stretch at different nodes make a
 		// pair whose stretch set holds three parts of that stretch (split at first, then at last: splitStretches :2772-2841 applied
 		// twice); the part between the two nodes belongs to no candidate alone.  Every such pair is replayed on its exact stretch
@@ -1821,14 +1811,43 @@ struct FastEngine
 				wv_sync();
 				nm = wv_bcast(nm,0);
 				if ( nm > MIDCAP || npool + nm > CT::scap || npool + nm > SMAX ) { over(32); return; }
-				for ( uint32_t m = lane; m < nm; m += WSZ ) makePiece(npool+m,L.midpar()[m],L.midA()[m],L.midB()[m]);      // (nm <= MIDCAP < 64: one round on the device; the 1-lane emulation needs the loop)
-				nmid = nm; npool += nm;
-				wv_sync();
+				nmid = nm; npool += nm;      // (their nodes: makePieces())
 			}
 		}
+	}
+	// The pieces of the pool: what findCandidatesAndPieces() counted and listed, for a state that has a first -> last walk
+	// (traverse(): behind the reachability test, which reads the candidates' parents and positions only).
+	DEV void makePieces()
+	{
+		LEDGER_REP(20)
+		{
+		{
+			// pieces of the candidates that split a stretch, one lane per candidate (first k-mers, then last k-mers): two
+			// pool ids each, numbered in candidate order
+			uint32_t id = n0;
+			for ( uint32_t c0 = 0; c0 < nF + nL; c0 += WSZ )
+			{
+				uint32_t const c = c0 + lane;
+				bool const isF = c < nF, act = c < nF + nL;
+				uint32_t const ci = isF ? c : c - nF;
+				uint32_t const par = act ? (isF ? L.parF()[ci] : L.parL()[ci]) : static_cast<uint32_t>(SNONE);
+				bool const has = act && par != SNONE;
+				uint32_t tot; uint32_t const pre = wv_scan_flag(has,tot);
+				if ( has )
+				{
+					uint32_t const pid = id + 2*pre, pos = isF ? L.posF()[ci] : L.posL()[ci];
+					if ( isF ) L.pieF()[ci] = pid; else L.pieL()[ci] = pid;
+					makePiece(pid,par,0,pos); makePiece(pid+1,par,pos,L.sslen()[par]-1);
+				}
+				id += 2*tot;
+			}
+		}
+		wv_sync();
+		for ( uint32_t m = lane; m < nmid; m += WSZ ) makePiece(midbase+m,L.midpar()[m],L.midA()[m],L.midB()[m]);      // (nmid <= MIDCAP < 64: one round on the device; the 1-lane emulation needs the loop)
+		wv_sync();
 		for ( uint32_t id = n0 + lane; id < npool; id += WSZ ) L.ppos()[id] = basePos(id);
 		wv_sync();
-
+		}
 	}
 
 	// Can any (first, last) candidate pair of this activation state offer a candidate at all?  A candidate is a chain of
@@ -3997,6 +4016,11 @@ struct FastEngine
 			if ( !reach ) { FSTAT_ADD(23,1); PROF(*this,16) return false; }
 		}
 #endif
+		// what only a state with a first -> last walk reads: the by-first / by-last lookups of the base stretches, the pieces and their positions
+		// (every over() check of the two functions stands in front of the reachability test, so flags and the tier that finishes a window are
+		// what they were; the lookups' sort key area and the pieces lie outside the weight arrays the test borrows)
+		computeStretchLookups();
+		makePieces();
 		PROF(*this,16)
 		loadTab();
 		PROF(*this,17)
@@ -4266,83 +4290,134 @@ struct FastEngine
 		PROF(*this,12)
 		// CDH -> CH -> ACC (:5099-5136) leaves the kept candidates in descending weight order.  With pairwise distinct
 		// weights that order does not depend on the heaps: one lane per candidate counts the heavier ones and stores its
-		// candidate at that rank.  Equal weights (rare) take the two heaps, whose mechanics decide their order.
+		// candidate at that rank.  Equal weights are common (35 % of the windows of a 20x batch: one path reached through two
+		// (first, last) pairs has one weight) and the heaps' mechanics decide their order, but that order reaches the window
+		// only through entry 0 of the final sort: the heaviest candidate among those with the smallest error sum.  So equal
+		// weights are ranked by their index in CDH first, and lane 0 runs the two heaps -- and decode, errors and sort once
+		// more from their order -- only if a candidate ties entry 0 in error sum AND weight and spells another string
+		// (0.7 % of the windows; in 0.36 % the heaps' order does change the consensus).  CDH and the stretch sequences are not written in between; CH, the temporary of the
+		// final sort, is free again when the heaps need it.  tiefast == 0: every tie takes the heaps, as before.
 		wv_sync();
 		uint32_t const nkept = wv_bcast(ncdh,0);
+		bool const tiefast = tieFastOn();
+		bool exact = false;
+		uint32_t tie = 0;
+		while ( true )
 		{
-			uint32_t tie = 0;
+			if ( !exact )
+			{
+				LEDGER_REP(18)
+				{
+				tie = 0;
+				for ( uint32_t c = lane; c < nkept; c += WSZ )
+				{
+					FCC const e = ldget(L.cdh()+c);
+					uint32_t rank = 0;
+					for ( uint32_t j = 0; j < nkept; ++j ) { uint64_t const wj = L.cdh()[j].w; rank += (wj > e.w || (wj == e.w && j < c)) ? 1u : 0u; tie |= (wj == e.w && j != c) ? 1u : 0u; }
+					ldput(L.acc()+rank,e);
+				}
+				tie = wv_any(tie);
+				}
+				FSTAT_ADD(21,tie ? 1u : 0u); FSTAT_ADD(22,nkept ? 1u : 0u);
+				if ( tie && !tiefast ) exact = true;
+				wv_sync();
+			}
+			if ( exact )
+			{
+#if defined(DACC_LEDGER)
+				// (the heaps consume CDH: the second run of a ledger build gets it back from the lanes' registers)
+				FCC keep_[WSZ >= 16 ? 1 : 16]; for ( uint32_t c = lane; c < nkept; c += WSZ ) keep_[c/WSZ] = ldget(L.cdh()+c);
+#endif
+				LEDGER_REP(18)
+				{
+#if defined(DACC_LEDGER)
+				wv_sync(); for ( uint32_t c = lane; c < nkept; c += WSZ ) ldput(L.cdh()+c,keep_[c/WSZ]); wv_sync();
+#endif
+				if ( lane == 0 )
+				{
+					uint32_t nh = nkept, nch = 0, na = 0;
+					while ( nh ) { FCC const c = ldget(L.cdh()); spop<FCC,true>(L.cdh(),nh); spush<FCC,false>(L.ch(),nch,c); }
+					while ( nch ) { ldput(L.acc()+na,ldget(L.ch())); ++na; spop<FCC,false>(L.ch(),nch); }
+				}
+				}
+				if ( lane == 0 ) FSTAT_ADD(32,tiefast ? 1u : 0u);      // audit aid: the exact route behind the fast one (not where the switch sends every tie here)
+				wv_sync();
+			}
+			// decode the kept candidates, one lane each
 			for ( uint32_t c = lane; c < nkept; c += WSZ )
 			{
-				FCC const e = ldget(L.cdh()+c);
-				uint32_t rank = 0;
-				for ( uint32_t j = 0; j < nkept; ++j ) { uint64_t const wj = L.cdh()[j].w; rank += (wj > e.w) ? 1u : 0u; tie |= (wj == e.w && j != c) ? 1u : 0u; }
-				ldput(L.acc()+rank,e);
+				uint32_t const slot = L.acc()[c].o, n = L.acc()[c].l & 0xFF;
+				uint32_t len = 0;
+				LEDGER_REP(19) len = decodeSeq(L.cseq()+FSEQCAP*slot,n,L.consL()+c*CONSROW);
+				L.acc()[c].o = c*CONSROW; L.acc()[c].l = len;
 			}
-			tie = wv_any(tie);
-			FSTAT_ADD(21,tie ? 1u : 0u); FSTAT_ADD(22,nkept ? 1u : 0u);
 			wv_sync();
-			if ( lane == 0 )
+			LEDGER_REP(14)
+			for ( uint32_t t = lane; t < nkept*mao; t += WSZ )
 			{
-				if ( tie )
+				uint32_t const c = t / mao, j = t - c*mao;
+				L.canderr()[t] = myersDistance(j,L.consL() + L.acc()[c].o,L.acc()[c].l);
+			}
+			wv_sync();
+			// error sum of candidate c on lane c, then the stable sort by error as a rank computation, one lane per candidate
+			for ( uint32_t c = lane; c < nkept; c += WSZ )
+			{
+				uint32_t s = 0;
+				for ( uint32_t j = 0; j < mao; ++j ) s += L.canderr()[c*mao+j];
+				L.accerr()[c] = s;
+			}
+			wv_sync();
+			// std::sort of at most 16 candidates by error (:5156) = insertion sort = a stable sort: candidate c goes to the
+			// number of candidates with a smaller error or the same error and a smaller index (through CH, which is free now;
+			// the error sums travel in the bytes of canderr, which have been summed up)
+			{
+				LDSQ uint32_t * const serr = reinterpret_cast<LDSQ uint32_t *>(L.canderr());
+				static_assert(16*CT::maxs >= 64 && (FastLds<CT>::o_canderr & 3) == 0,"sorted error sums borrow the candidate error bytes");
+				for ( uint32_t c = lane; c < nkept; c += WSZ )
 				{
-					uint32_t nch = 0;
-					while ( ncdh ) { FCC const c = ldget(L.cdh()); spop<FCC,true>(L.cdh(),ncdh); spush<FCC,false>(L.ch(),nch,c); }
-					while ( nch ) { ldput(L.acc()+nacc,ldget(L.ch())); ++nacc; spop<FCC,false>(L.ch(),nch); }
+					uint32_t const e = L.accerr()[c];
+					uint32_t rank = 0;
+					for ( uint32_t j = 0; j < nkept; ++j ) { uint32_t const ej = L.accerr()[j]; rank += (ej < e || (ej == e && j < c)) ? 1u : 0u; }
+					ldput(L.ch()+rank,ldget(L.acc()+c));
+					serr[rank] = e;
 				}
-				else { nacc = nkept; ncdh = 0; }
-			}
-		}
-		wv_sync();
-		uint32_t const nc = wv_bcast(nacc,0);
-		nacc = nc;
-		// decode the kept candidates, one lane each
-		for ( uint32_t c = lane; c < nc; c += WSZ )
-		{
-			uint32_t const slot = L.acc()[c].o, n = L.acc()[c].l & 0xFF;
-			uint32_t const len = decodeSeq(L.cseq()+FSEQCAP*slot,n,L.consL()+c*CONSROW);
-			L.acc()[c].o = c*CONSROW; L.acc()[c].l = len;
-		}
-		wv_sync();
-		LEDGER_REP(14)
-		for ( uint32_t t = lane; t < nc*mao; t += WSZ )
-		{
-			uint32_t const c = t / mao, j = t - c*mao;
-			L.canderr()[t] = myersDistance(j,L.consL() + L.acc()[c].o,L.acc()[c].l);
-		}
-		wv_sync();
-		// error sum of candidate c on lane c, then the stable insertion sort by error on lane 0
-		for ( uint32_t c = lane; c < nc; c += WSZ )
-		{
-			uint32_t s = 0;
-			for ( uint32_t j = 0; j < mao; ++j ) s += L.canderr()[c*mao+j];
-			L.accerr()[c] = s;
-		}
-		wv_sync();
-		// std::sort of at most 16 candidates by error (:5156) = insertion sort = a stable sort: candidate c goes to the
-		// number of candidates with a smaller error or the same error and a smaller index (through CH, which is free now;
-		// the error sums travel in the bytes of canderr, which have been summed up)
-		{
-			LDSQ uint32_t * const serr = reinterpret_cast<LDSQ uint32_t *>(L.canderr());
-			static_assert(16*CT::maxs >= 64 && (FastLds<CT>::o_canderr & 3) == 0,"sorted error sums borrow the candidate error bytes");
-			for ( uint32_t c = lane; c < nc; c += WSZ )
-			{
-				uint32_t const e = L.accerr()[c];
-				uint32_t rank = 0;
-				for ( uint32_t j = 0; j < nc; ++j ) { uint32_t const ej = L.accerr()[j]; rank += (ej < e || (ej == e && j < c)) ? 1u : 0u; }
-				ldput(L.ch()+rank,ldget(L.acc()+c));
-				serr[rank] = e;
+				wv_sync();
+				for ( uint32_t c = lane; c < nkept; c += WSZ ) { ldput(L.acc()+c,ldget(L.ch()+c)); L.accerr()[c] = serr[c]; }
 			}
 			wv_sync();
-			for ( uint32_t c = lane; c < nc; c += WSZ ) { ldput(L.acc()+c,ldget(L.ch()+c)); L.accerr()[c] = serr[c]; }
+			if ( exact || !tie ) break;
+			// ambiguous: a candidate behind entry 0 with its error sum and its weight that is another string
+			uint32_t amb = 0;
+			{
+				uint32_t const e0 = L.accerr()[0], l0 = L.acc()[0].l; uint64_t const w0 = L.acc()[0].w;
+				LDSQ uint64_t const * const r0 = reinterpret_cast<LDSQ uint64_t const *>(L.consL() + L.acc()[0].o);
+				for ( uint32_t c = lane; c < nkept; c += WSZ )
+					if ( c != 0 && L.accerr()[c] == e0 && L.acc()[c].w == w0 )
+					{
+						if ( L.acc()[c].l != l0 ) amb = 1;
+						else
+						{
+							LDSQ uint64_t const * const rc = reinterpret_cast<LDSQ uint64_t const *>(L.consL() + L.acc()[c].o);
+							uint64_t x = 0;
+							for ( uint32_t i = 0; i < (l0 >> 3); ++i ) x |= r0[i] ^ rc[i];
+							if ( l0 & 7u ) x |= (r0[l0 >> 3] ^ rc[l0 >> 3]) & ((1ull << (8u*(l0 & 7u))) - 1ull);
+							amb |= x ? 1u : 0u;
+						}
+					}
+			}
+			if ( !wv_any(amb) ) break;
+			exact = true;
+			wv_sync();
 		}
-		wv_sync();
+		if ( lane == 0 ) ncdh = 0;
+		nacc = nkept;
 		PROF(*this,13)
 		FSTAT_MX(0,mao); FSTAT_MX(1,npre); FSTAT_MX(2,nn); FSTAT_MX(3,n0); FSTAT_MX(4,npool); FSTAT_MX(5,nlinks); FSTAT_MX(6,nwF); FSTAT_MX(7,nwR);
-		FSTAT_MX(8,rstop); FSTAT_MX(9,nF); FSTAT_MX(10,nL); FSTAT_ADD(11,1); FSTAT_MX(12,nc); FSTAT_ADD(24,nc ? 0u : 1u);
+		FSTAT_MX(8,rstop); FSTAT_MX(9,nF); FSTAT_MX(10,nL); FSTAT_ADD(11,1); FSTAT_MX(12,nkept); FSTAT_ADD(24,nkept ? 0u : 1u);
 #if defined(DACC_EMUL)
-		if ( lane == 0 ) { FILE * f = ftrav_file(); if ( f ) { uint32_t nlv = 0; for ( uint32_t i = 0; i < nL; ++i ) nlv += L.lnode()[i] != 0xFFFF; fprintf(f,"%d %u %u %u %u %u %u %u %u %u %u %u %u\n",int(CT::maxs),mao,npre,nn,n0,npool,nF,nL,nlv,rstop,nwFall,nwRall,nc); fflush(f); } }
+		if ( lane == 0 ) { FILE * f = ftrav_file(); if ( f ) { uint32_t nlv = 0; for ( uint32_t i = 0; i < nL; ++i ) nlv += L.lnode()[i] != 0xFFFF; fprintf(f,"%d %u %u %u %u %u %u %u %u %u %u %u %u\n",int(CT::maxs),mao,npre,nn,n0,npool,nF,nL,nlv,rstop,nwFall,nwRall,nkept); fflush(f); } }
 #endif
-		return nc != 0;
+		return nkept != 0;
 	}
 
 	DEV int32_t estimateLength()
@@ -4592,7 +4667,7 @@ DEV int processWindowFast(FastBatch const & FB, uint64_t const widx, LDSQ uint8_
 		// (one-slab tier: the weights, the spill image and the instance image follow the layout in the buffer the caller passed as `lds`)
 		if constexpr ( FastOneSlab<CT>::value != 0 ) E.gslab = (uint8_t *)(lds) + FastLds<CT>::g_base;
 	}
-	E.lane = wv_lane(); E.flags = 0; E.prof = B.prof; E.feasneed = FB.feasneed;
+	E.lane = wv_lane(); E.flags = 0; E.prof = B.prof; E.feasneed = FB.feasneed; E.tiefast = FB.tiefast;
 #if defined(DACC_EMUL)
 	E.feascount = false; E.feasapplied = false; E.nwFall = E.nwRall = 0;
 #endif

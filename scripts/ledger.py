@@ -7,7 +7,7 @@ cost: instructions by class and wave time (SQ_WAVE_CYCLES counts quad-cycles: x 
 cannot run twice -- the lane 0 replay of the pairs into the candidate heap, candidate ranking / decoding, addNextFromHeap, hand-over
 slots -- is the remainder (total minus the phases).
 
-usage: python scripts/ledger.py <outdir> [reads=1500] [extra bench.py args...]        (needs rocprofv3; ~25 s per pass, 19 passes)
+usage: python scripts/ledger.py <outdir> [reads=1500] [extra bench.py args...]        (needs rocprofv3; ~25 s per pass, 22 passes)
 LEDGER_BITS=8,11 restricts the passes to these phases (the remainder line is then everything else); LEDGER_LIB=<path> measures another
 -DDACC_LEDGER build than daccord_amd/libvar_ledger.so (say the parent's, for a before / after of one phase).
 The library: python -c "from daccord_amd import build; build.build_variant('ledger', ['-DDACC_LEDGER'])"   (here, before the GPU call)"""
@@ -16,11 +16,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PHASES = [(0, "gather: overlap selection, string descriptors, bases -> pattern masks"), (1, "estimateLength (f64 products over the strings)"),
           (2, "buildInstances: k-mer instances + register bitonic sorts"), (3, "buildNodes: nodes, positions, support ranges, first / last k-mer lists"),
           (16, "passIsDead"), (17, "saveInstances (sorted instances -> slab)"), (4, "buildSuccessors"),
-          (5, "computeBaseStretches: predecessor counts, walks, links, two sorts"), (6, "findCandidatesAndPieces"), (7, "pairReachable (exact prune)"),
+          (5, "computeBaseStretches: predecessor counts, walks, links, the sort by (first, ext) (the by-last sort and the lookups: phase 20)"),
+          (6, "findCandidatesAndPieces: candidates, parents, piece counts, middle piece list (the pieces' nodes and ppos: phase 20)"), (7, "pairReachable (exact prune)"),
           (8, "computeStretchFeasLanes: stretch feasibility + weight records"), (9, "spillS (build-phase arrays -> slab)"),
           (10, "reverse enumerations of all last k-mers + block copy / sort / rank"), (11, "forward trees of a batch of first k-mers + finish"),
           (12, "pairs, lane-parallel part: classify, matchPops, interval tasks, heaps + pops"), (13, "restoreS (slab -> build-phase arrays)"),
-          (14, "candidate errors: Myers distance of every (candidate, string)"), (15, "window record: pending store (the alignment is k_emit's); wide windows: alignAndEmitWide (lane 0) + emitRecordWide")]
+          (14, "candidate errors: Myers distance of every (candidate, string)"), (15, "window record: pending store (the alignment is k_emit's); wide windows: alignAndEmitWide (lane 0) + emitRecordWide"),
+          (18, "kept candidates: lane-parallel rank; lane 0's two heaps where they run (DACC_TIE_FAST=0: at every tie)"),
+          (19, "decodeSeq of the kept candidates"), (20, "computeStretchLookups + makePieces: by-last sort, by-first table, nodes of the pieces, ppos (only behind a successful pairReachable)")]
+# Phases 5 and 6 of ledgers taken before computeStretchLookups() / makePieces() existed (profiles/r06_instr_ledger.md, feas_*_measurements.md) include what is now
+# phase 20, in every traversal; since then it runs only in traversals that pass pairReachable().  In a -DDACC_PROFILE build computeStretchLookups() moved from
+# PROF slot 8 (computeBaseStretches) to slot 16 (candidates, pieces, reachability): compare phases 5 + 6 + 20 and slots 8 + 16 across that change, not each alone.
 COUNTERS = ["SQ_WAVE_CYCLES", "SQ_WAIT_ANY", "SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_BRANCH", "SQ_INSTS_LDS", "SQ_INSTS_VMEM_RD", "SQ_INSTS_VMEM_WR"]
 
 
