@@ -19,7 +19,7 @@
 #include <cstdint>
 #include "../../include/daccord_hip.h"
 #include "dev_types.hpp"
-#include "fast_window.hpp"
+#include "fast_layout.hpp"
 
 namespace dacc {
 
@@ -321,7 +321,7 @@ struct BatchPlan
 		caps.lstr = static_cast<uint32_t>(std::min<uint64_t>(LSTRMAX,std::max<uint64_t>(LSTR,(maxspan+63)&~static_cast<uint64_t>(63))));
 		if ( caps.lstr > LSTR ) caps.blcap = caps.lstr + 128;    // a stretch runs as far as a string does, a path half a window further
 		caps.bytes = 0;
-		// LDS fast path capacity tiers (compile time, fast_window.hpp); windows beyond them are re-run by the generic engine
+		// LDS fast path capacity tiers (compile time, fast_tiers.hpp); windows beyond them are re-run by the generic engine
 		// A batch whose windows are mostly too deep for tier 1 (coverage of 40x and more) starts in the deep tier instead
 		deep = 2*ndeepwin > nwindows;
 		// (round 6) wide windows: tier 8 (second slot, no hand-over list in front of it = all windows), tier 9, then the generic engine

@@ -30,39 +30,11 @@
  *  - stretches are looked up by first / last node through small index arrays, the weights of a feasible (stretch,
  *    position) entry carry the weights of its end nodes, candidates are kept as stretch sequences and decoded once.
  *
- * The same code is instantiated for twenty capacity tiers (FastTier<N> below; the layout FastLds<CT> is a compile time constant,
- * so every LDS access has an immediate offset).  Which of them a batch runs, in which order and behind which switches, is
- * written down once, in tier_pipeline.hpp.
- *
- *   tier  role                                                        layout  path/stretch ids  wavefronts per CU
- *      0  front of slot 0, shallow: the small size class              gw       8 /  8 bit       8
- *      7  front of slot 0, shallow: the middle size class             gw       8 /  8 bit       7
- *      1  slot 0 of shallow batches                                   gw       8 /  8 bit       6
- *      4  slot 0 of deep batches (many strings, small graph)          gw       8 /  8 bit       5
- *      6  slot 1 of shallow batches (strings of up to 128 bases)      gw       8 /  8 bit       4
- *      2  slot 1 of deep batches                                      gw       8 /  8 bit       3
- *     10  front of slot 2, shallow: dense graphs                      gw      16 /  8 bit       2
- *     11  front of slot 2, deep: many instances                       gw      16 /  8 bit       2
- *     12  front of slot 2, shallow and deep: 97 ... 250 strings       gw      16 / 16 bit       1
- *      3  slot 2 of shallow and deep batches                          gw      16 / 16 bit       1
- *      8  slot 1 of wide batches (w = 64 ... 127)                     gw      16 /  8 bit       2
- *      9  slot 2 of wide batches                                      gw      16 / 16 bit       1
- *      5  second stream (k_window_long): strings of up to 128 bases   legacy  16 /  8 bit       1
- *     13  last stage, shallow and deep (layout in device memory)      gw      16 / 16 bit       no LDS
- *     14  last stage, wide batches (layout in device memory)          gw      16 / 16 bit       no LDS
- *     15  very deep stage, shallow and deep: 251 ... 1000 strings     gw      16 / 16 bit       no LDS
- *     16  deepest stage, shallow and deep: 1001 ... 2000 strings      gw      16 / 16 bit       no LDS
- *     17  second stream, wide batches: strings of 129 ... 255 bases   gw      16 / 16 bit       no LDS
- *     18  full-depth stage, shallow and deep: 2001 ... 5001 strings   gw      16 / 16 bit       no LDS
- *     19  wide deep stage, wide batches: 251 ... 1000 strings         gw      16 / 16 bit       no LDS
- *
- * processWindowFast returns
- * FW_NEXT when a window overflows a tier (flags say what overflowed: 1 instances, 2 nodes, 8 candidates, 16 walk,
- * 32 stretches, 64 links, 128 weights, 512 pools (0x4000 reverse cache, 0x8000 path ids, 0x10000 forward pool,
- * 0x20000 popped paths, 0x40000 score intervals), 1024 introsort's depth limit reached in the replayed std::sort (the tiers
- * stop there; the generic engine finishes such a range with libstdc++'s heapsort fallback), 2048 base length, 4096 candidate
- * length / sequence, 8192 gap filling) and FW_GENERIC for shapes the tier does not support (a window wider than it holds, a string
- * longer than its string stride lstr: 64 or 128 bases, tier 17: longer than 255); those go to tier 5 / tier 17 / the generic engine (dbg_window.hpp).
+ * The same code is instantiated once per capacity tier.  The tiers -- the rows FastTier<N>, the table of their roles and the meaning of the
+ * overflow flags that processWindowFast reports with FW_NEXT / FW_GENERIC -- are in fast_tiers.hpp; the layout FastLds<CT> of a tier's working
+ * state, a compile time constant so that every LDS access has an immediate offset, and fastCapsOf are in fast_layout.hpp; the emulation's
+ * design aids (FSTAT_*, FEAS_*) are in fast_diag.hpp.  Which tiers a batch runs, in which order and behind which switches, is written down
+ * once, in tier_pipeline.hpp.  This file holds the batch record, the engine FastEngine<CT> and its entry points classifyWindow and processWindowFast.
  */
 #ifndef DACC_FAST_WINDOW_HPP
 #define DACC_FAST_WINDOW_HPP
@@ -71,6 +43,9 @@
 #include "arena.hpp"
 #include "window_main.hpp"
 #include "tier_pipeline.hpp"
+#include "fast_tiers.hpp"
+#include "fast_layout.hpp"
+#include "fast_diag.hpp"
 #include "emit_record.hpp"
 
 namespace dacc {
@@ -79,657 +54,6 @@ enum { WS_RETRY = 4 };
 enum { FNOPAR = 0xFF };
 enum { FSEQCAP = 48 };      // max stretches of one candidate path
 // (FastCaps, the run time description of a tier, and FSUPCAP / FSUPCAPW: tier_pipeline.hpp)
-
-struct FSI { uint64_t w; uint16_t left, right, current, path; };   // ScoreInterval (left/right/current: sorted reverse entries, path: forward pop index)
-struct FCC { uint64_t w; uint32_t o, l; };                                       // ConsensusCandidate
-
-// compile time capacities of the tiers: every LDS offset below is an instruction immediate
-template<int TIER> struct FastTier;
-// gw: the weights of the feasible (stretch, position) pairs and the model table live in global memory (a scratch slab per
-// workgroup / the padded 32 bit table), the build-phase arrays are overlaid by the enumeration pools (spilled to the slab
-// while the enumerations run): layout FastLds<CT,true>.  Round 3 measured that a second wavefront per SIMD hides the LDS
-// round trips of the first almost completely (profiles/r03a_occupancy_experiment.md), so LDS bytes per window decide the
-// throughput: tier 1 is 26.3 KB = 6 wavefronts per CU with (almost) the capacities it had at 53.8 KB = 3 per CU.
-// (round 6) reverse pool of tiers 0 and 1 in chunks of TWO paths: a lane takes pool entries a chunk at a time, and with one lane per last
-// k-mer candidate (9 on average, up to 24) most chunks of four were half empty -- the reverse pool had become what sent tier 0's windows on
-// (82 % of its hand-overs, each after the whole build phase and the feasibility; emulation, 8 piles of config 2: 261 of 5251 windows -> 14)
-#if !defined(DACC_RCH01)
-#define DACC_RCH01 2
-#endif
-template<> struct FastTier<1> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 1024, rch = DACC_RCH01, fch = 4, fnw = 2, fnc = 40, idmax = 250, rpstcap = 256, lstr = 64, maxs = 32, precap = 1024, ncap = 776, scap = 112, lcap = 960, wcap = 1024, rccap = 144, fcap = 192, siqcap = 56, blcap = 96, seqcap = 32, psiq = 8, consrow = 64, lscrids = 2048, wide = 0, mins = 0, gmem = 0 }; };
-// tier 0 (size classes): the windows a pre-pass (classifyWindow, k_classify) finds small -- few strings, at most T0INST k-mer
-// instances -- in 20 KB = 8 wavefronts per CU (two on every SIMD).  What overflows it joins the other windows in tier 1.
-template<> struct FastTier<0> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 768, rch = DACC_RCH01, fch = 4, fnw = 2, fnc = 32, idmax = 250, rpstcap = 256, lstr = 64, maxs = 28, precap = 576, ncap = 524, scap = 88, lcap = 640, wcap = 768, rccap = 96, fcap = 128, siqcap = 56, blcap = 96, seqcap = 32, psiq = 8, consrow = 64, lscrids = 2048, wide = 0, mins = 0, gmem = 0 }; };
-// tier 7 (round 6, the MIDDLE size class of shallow batches): 22.9 KB = 7 wavefronts per CU.  Four fifths of the windows tier 1 (6 per CU)
-// used to run have at most 28 strings, 704 k-mer instances, 640 nodes and 800 links (emulation, 16 piles of config 2: 4244 of 5295); the
-// pre-pass sends them here, what overflows joins tier 1's list like tier 0's hand-overs join this one.
-template<> struct FastTier<7> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 896, rch = DACC_RCH01, fch = 4, fnw = 2, fnc = 32, idmax = 250, rpstcap = 256, lstr = 64, maxs = 28, precap = 704, ncap = 640, scap = 104, lcap = 800, wcap = 896, rccap = 112, fcap = 148, siqcap = 56, blcap = 96, seqcap = 32, psiq = 8, consrow = 64, lscrids = 2048, wide = 0, mins = 0, gmem = 0 }; };
-// (the size-class thresholds of the pre-pass, T0INST_DEFAULT / T7INST_DEFAULT = the instance capacities of tiers 0 and 7: tier_pipeline.hpp)
-// tier 2: gw layout as well since round 3 (43 KB: 3 wavefronts per CU; the legacy layout was 80.5 KB: 2 per CU)
-// (round 4: 76 KB = 2 wavefronts per CU instead of 46.5 KB = 3, with tier 3's node capacity: at 54x more than half of what the deep tier
-// hands on has more than 1024 nodes at filter frequency 1 and used to go through this tier only to be handed on again to tier 3, which
-// runs one wavefront per CU)
-// (round 6: 53 744 B = 42 LDS granules = THREE wavefronts per CU instead of 63.9 KB = two, with 1536 nodes and 2032 links instead of 2048 / 2304:
-// of the 65 903 windows the deep tier hands on in 1000 piles of the 54x shape 3045 went on to tier 3 before and 3329 do now, and the tier's
-// time falls from 96 to 66 ms -- 27.4 -> 30.1 Mbase/s, profiles/r06s; the node tables are 20 of its bytes per node)
-#if !defined(DACC_T2_NCAP)
-#define DACC_T2_NCAP 1536
-#endif
-#if !defined(DACC_T2_LCAP)
-#define DACC_T2_LCAP 2032
-#endif
-template<> struct FastTier<2> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 3072, rch = 4, fch = 4, fnw = 4, fnc = 64, idmax = 250, rpstcap = 256, lstr = 64, maxs = 96, precap = 2048, ncap = DACC_T2_NCAP, scap = 232, lcap = DACC_T2_LCAP, wcap = 3072, rccap = 256, fcap = 192, siqcap = 96, blcap = 96, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0, gmem = 0 }; };
-// tier 6 (second slot of SHALLOW batches since round 3, gw layout, 36 KB = 4 wavefronts per CU): what tier 1 hands on at 20x
-// are windows with more than its 608 nodes (82 % of the hand-overs) or fuller pools, not more strings or instances, so this
-// tier keeps tier 1's string / instance capacities and spends its LDS on nodes, stretches and pools.  Deep batches keep
-// tier 2 (64 strings, 2048 instances) behind the deep tier.
-// (round 6: the tier sat at 34 720 B, 6 KB below what four wavefronts per CU allow (40 960 B): the bytes went to what sends its windows on to
-// tier 3 -- ONE wavefront per CU -- on the ONT mix at small k (emulation, 6 piles of config 5 at k = 10 / 12: reverse pool 73 / 130, weights 53 / 1,
-// forward pool 45 / 7 of about 200 hand-overs): reverse pool 192 -> 256 paths in chunks of two, 248 stretches, 2048 weight records)
-template<> struct FastTier<6> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 2048, rch = 2, fch = 8, fnw = 3, fnc = 40, idmax = 250, rpstcap = 256, lstr = 128, maxs = 40, precap = 1024, ncap = 1024, scap = 248, lcap = 1280, wcap = 2048, rccap = 256, fcap = 256, siqcap = 96, blcap = 96, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0, gmem = 0 }; };
-
-// tier 3 (one wavefront per CU): 16 bit path ids, so that an enumeration may hold more than 250 paths; sized for deep piles
-// too (BASELINE config 4, 54x: up to 96 strings with 4096 k-mer instances, 72 first / last k-mer candidates)
-// gw layout and 16 bit STRETCH ids since round 3: what the legacy tier 3 handed to the generic engine at 54x were windows with
-// more than 250 stretches (13 of 19 per 60 000 windows) or more than 2112 feasible weights (5 of 19), and each of them cost the
-// generic engine seconds (685 such windows were 92 % of a 2000-pile 54x batch, profiles/r03c_bench_54x_2000piles.log)
-template<> struct FastTier<3> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 1000, gw = 1, wcapg = 8192, rch = 8, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 96, precap = 4096, ncap = 2048, scap = 1024, lcap = 4096, wcap = 8192, rccap = 2048, fcap = 512, siqcap = 256, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0, gmem = 0 }; };
-
-// tier 4 (three wavefronts per CU, takes the place of tier 1 in batches of deep piles): many strings and k-mer instances,
-// small graph.  At 54x (BASELINE config 4) 96 % of the windows find their consensus at filter frequency 2, where the graph
-// has about a hundred nodes, while the 55 strings of a window carry 1500 k-mer instances.
-template<> struct FastTier<4> { typedef uint8_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 608, rch = 4, fch = 4, fnw = 2, fnc = 40, idmax = 250, rpstcap = 256, lstr = 64, maxs = 96, precap = 2048, ncap = 256, scap = 48, lcap = 256, wcap = 608, rccap = 128, fcap = 96, siqcap = 56, blcap = 96, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0, gmem = 0 }; };
-
-// tier 5 (one wavefront per CU, only for the windows the pre-scan found): B strings of up to 128 bases (string stride 128,
-// two words per pattern mask); everything else as tier 3 with 64 strings.  Window strings of more than 64 bases are rare
-// at the default window (a few per ten million windows of config 2) but each of them costs the generic engine seconds.
-template<> struct FastTier<5> { typedef uint16_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 0, wcapg = 0, rch = 8, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 64, precap = 4096, ncap = 1792, scap = 250, lcap = 2048, wcap = 2040, rccap = 512, fcap = 512, siqcap = 256, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0, gmem = 0 }; };
-
-// tier 8 (round 6, two wavefronts per CU): WIDE windows, -w 64 ... 127 (the reference takes any -w, daccord.cpp:1282-1305; rounds 4-5 ran them in the generic
-// engine, two orders of magnitude slower per window).  What a wide window needs beyond tier 6's two-word pattern masks: feasible start positions
-// of a stretch up to nrows = w+1 <= 128 (two words per position mask: maskF / maskFh), candidates and a consensus of up to 128 symbols, the
-// two-word consensus -> A alignment and the wide window record (dev_types.hpp: WRECW).  A batch with w > 63 runs this tier alone in front of the
-// generic engine (BatchPlan::wide); sized for 20x piles at w = 64 ... 96 (20 strings of 83 k-mers at w = 96, k = 14).
-template<> struct FastTier<8> { typedef uint16_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 6144, rch = 4, fch = 8, fnw = 4, fnc = 64, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 40, precap = 3072, ncap = 2304, scap = 248, lcap = 3072, wcap = 6144, rccap = 640, fcap = 512, siqcap = 96, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 2560, wide = 1, mins = 0, gmem = 0 }; };
-
-// tier 9 (round 6, one wavefront per CU): what overflows tier 8 -- its reverse pool (512 paths), forward pool, score intervals -- before the generic
-// engine, which recomputes both enumerations for every (first, last) k-mer pair and takes seconds for such a window (30 of 37 000 windows at
-// w = 64 were 6.2 of a step's 6.7 s, profiles/r06v).  Tier 3's pools with the wide tier's masks, alignment and record.
-template<> struct FastTier<9> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 500, gw = 1, wcapg = 8192, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 64, precap = 4096, ncap = 3072, scap = 512, lcap = 4096, wcap = 8192, rccap = 2048, fcap = 1024, siqcap = 256, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 2560, wide = 1, mins = 0, gmem = 0 }; };
-
-// tier 10 (round 6, two wavefronts per CU): the DENSE-graph tier of shallow batches, between tier 6 (four per CU, 8 bit path ids: 256 reverse
-// paths) and tier 3 (ONE per CU).  On the ONT error mix at k = 10 tier 6 hands 1.4 % of the windows on -- reverse pools of more than 256 paths,
-// forward pools, more than 1024 k-mer instances -- and tier 3 needs 17 % of the step for them (profiles/r06k/bench_ont_k10.log; VERDICT r05 task 4:
-// "more than 1 % in tier 3: add a dense-graph tier").  Tier 8's pools and 16 bit ids without its wide parts.
-template<> struct FastTier<10> { typedef uint16_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 6144, rch = 4, fch = 8, fnw = 4, fnc = 64, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 64, precap = 2560, ncap = 2048, scap = 248, lcap = 3072, wcap = 6144, rccap = 896, fcap = 512, siqcap = 128, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0, gmem = 0 }; };
-
-// tier 11 (round 6, two wavefronts per CU): tier 10's place in batches of DEEP piles, between tier 2 (three per CU, 2048 k-mer instances) and tier 3 (one per CU).
-// At 54x what tier 2 hands on are windows of more than 2048 k-mer instances (75 strings and more: 186 of 208 hand-overs in 12 piles of config 4), a few node
-// tables and pools; tier 3 needs 6.8 % of the step for them (profiles/r06zz/bench_54x_2000piles.log).  Tier 3's string / instance capacities with tier 10's pools.
-template<> struct FastTier<11> { typedef uint16_t id_t; typedef uint8_t sid_t; enum : uint32_t { smax = 250, gw = 1, wcapg = 4096, rch = 4, fch = 8, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 96, precap = 4096, ncap = 1536, scap = 248, lcap = 2048, wcap = 4096, rccap = 640, fcap = 384, siqcap = 128, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 0, gmem = 0 }; };
-
-// tier 12 (one wavefront per CU): the DEEP-WINDOW tier, windows of 97 ... 250 strings (repeat piles: the rRNA operons of a bacterial genome at 20x
-// are about 140 deep, a low-copy repeat at 54x 100 ... 220), which every other tier refuses at its string count and which used to run in the
-// generic engine at a few dozen wavefronts (its scratch arenas grow with the deepest pile of the batch).  Tier 3's graph and pools with 250 strings
-// and 8192 k-mer instances, 157 856 B of LDS.  Such a window finds its consensus at filter frequency 2, but its graph is not small: with tier 4's
-// graph capacities (256 nodes, 101 088 B) 977 of 997 windows of a 150x pile overflow the node table, with tier 11's (1536 nodes, 129 568 B) 644 of
-// 997 at k = 8; only tier 3's held every window, so a lighter variant with more than one wavefront per CU does not pay.
-// mins: the tier takes only the windows with MORE strings than that and passes the others on untouched (tier 3 runs what it ran before).
-// String ids stay 8 bits in the compact string list of the instance generation (maxs <= 256); a k-mer seen more than 255 times does not fit
-// the node frequency byte and sends the window on (buildNodes: overflow bit 2), nothing wraps.
-template<> struct FastTier<12> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 1000, gw = 1, wcapg = 8192, rch = 8, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 250, precap = 8192, ncap = 2048, scap = 1024, lcap = 4096, wcap = 8192, rccap = 2048, fcap = 512, siqcap = 256, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 2560, wide = 0, mins = 96, gmem = 0 }; };
-
-// tiers 13 and 14: the LAST stage, behind the slots and in front of the generic engine (tier_pipeline.hpp: ID_LAST).  gmem: the whole layout FastLds<CT>
-// lives in the workgroup's slab in device memory instead of LDS (k_fast_13.hip / k_fast_14.hip compile this header with LDSQ = the global address
-// space; nothing else changes -- the emulation has always run the tiers over a plain buffer).  A dependent load that hits L2 costs 180 ... 225 cycles
-// against about 50 for ds_read, so a window costs a few times what it costs in tier 3 -- and not the seconds of the generic engine, which recomputes
-// stretches, feasibility and both enumerations for every (first, last) k-mer pair.  Without the 160 KiB of a CU as a bound every table is at least
-// as large as the largest of tiers 3, 6, 9, 10, 11 and 12, and the tables that have sent windows to the generic engine are twice tier 3's (tier 9's
-// in the wide tier 14): nodes, stretches, links, weights, both pools, score intervals; 16384 k-mer instances.
-//  - reverse pool: 4096 paths in 256 chunks of 16 (8 bit chunk ids kept: tier 3 has 256 chunks of 8, so an enumeration needs at most as many chunks here);
-//  - 16 bit weight offsets and task offsets kept: 16384 weight records per direction, at most 65535 (stretch, direction, position) tasks per traversal;
-//  - more than 4094 nodes: the stretch sort key takes 13 bit node fields and a 12 bit stretch number (FastEngine: KF, QB).
-// Windows of more than 250 strings go on to tiers 15, 16 and 18; wider than 127 bases or with a string of more than 128 bases they still go to the generic engine.
-template<> struct FastTier<13> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 2000, gw = 1, wcapg = 16384, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 250, precap = 16384, ncap = 4096, scap = 2048, lcap = 8192, wcap = 16384, rccap = 4096, fcap = 1024, siqcap = 512, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 4096, wide = 0, mins = 0, gmem = 1 }; };
-template<> struct FastTier<14> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 1000, gw = 1, wcapg = 16384, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 250, precap = 16384, ncap = 6144, scap = 1024, lcap = 8192, wcap = 16384, rccap = 4096, fcap = 2048, siqcap = 512, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 4096, wide = 1, mins = 0, gmem = 1 }; };
-// tier 15: the VERY DEEP stage, behind the last stage and in front of the generic engine (tier_pipeline.hpp: ID_VDEEP): windows of 251 ... 1000 strings
-// (a repeat pile of several hundred overlaps), which every other tier refuses at its string count and the generic engine runs at a handful of
-// wavefronts (its arena is 200 MB per wavefront at depth 1000).  Tier 13's graph, pool, weight and interval capacities with 1000 strings and 65536
-// k-mer instances (FastLds<CT>::icap = 4 x precap: the instances are split by their first symbol into four ranges, each sorted on its own with the sort
-// of 16384 keys that tier 13 has -- precap stays the capacity of one sort); mins = 250: what tier 13 could have held is passed on as it came.  What a string count above 256 widens (FastLds<CT>::wides, all
-// other tiers keep their fields bit for bit):
-//  - compact string list of the instance generation: 10 bit string id | 16 bit first slot (4 x 1000 bytes <= the 65536 bytes of irpos);
-//  - node frequency: 16 bits, capped at fqmax = 1023 -- a k-mer seen more often sets overflow bit 2 and the window goes on, nothing wraps;
-//  - node weight: at most 1023 table words of < 2^32, so < 2^42 (10 bit high part); a feasible stretch has at most nrows <= 64 nodes, so < 2^48
-//    (16 bit high part, as before): the reverse record packs 16 + 10 bits into its third word, the forward record (16 + 10 + 10 = 36 bits) becomes
-//    32 bytes of three 64 bit words; path weights (rc_w, f_w, score intervals, candidates) are 64 bit sums of at most FSEQCAP stretches, < 2^54;
-//  - first instance of a node (nps): 32 bits, 1000 strings carry up to 65536 instances;
-//  - the 16 chunks of 64 strings of the instance generation are walked twice (count, then place) instead of being kept in 48 registers;
-//  - key tables (mfirst, mlast, lastk) of 1024 entries, 16000 candidate error bytes.
-// One capacity is not tier 13's: 32768 weight records per direction instead of 16384 (the 16 bit weight offsets hold that).  At k = 8 a window of
-// 700 strings has a graph of 2100 nodes in 1200 stretches at filter frequency 2, and 24 of the 197 windows of such a pile have more than 16384
-// feasible (stretch, position) pairs in one direction (emulation, tests/vdeep_cases.py shape D); the slab is device memory, the records cost 1.5 MB.
-template<> struct FastTier<15> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 2000, gw = 1, wcapg = 32768, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 128, maxs = 1000, precap = 16384, ncap = 4096, scap = 2048, lcap = 8192, wcap = 32768, rccap = 4096, fcap = 1024, siqcap = 512, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 4096, wide = 0, mins = 250, gmem = 1 }; };
-
-static_assert(FastTier<15>::mins == VDEEP_MINS && FastTier<13>::maxs == VDEEP_MINS,"the very deep stage takes what the last stage refuses at its string count");
-// tier 16: the DEEPEST stage, behind the very deep stage and in front of the generic engine (tier_pipeline.hpp: ID_XDEEP): windows of 1001 ... 2000 strings
-// and the windows of 251 ... 1000 strings that overflowed one of tier 15's tables (mins = 250: everything else is passed on as it came).  Tier 15's code
-// with twice its graph: 8190 nodes (the most the 13 bit node fields of the stretch sort key name), 4096 stretches (its 12 bit stretch number), 16384
-// links, 4000 pool stretches.  What a string count above 1024 widens (FastLds<CT>::xwides, all other tiers keep their fields bit for bit):
-//  - compact string list: 11 bit string id | 17 bit first slot;
-//  - node frequency capped at fqmax = 4095: node weight < 2^44 (12 bit high part), stretch weight < 2^50 (18 bit high part), the reverse record's third
-//    word holds 18 + 12 bits; the forward record is the three 64 bit words of tier 15;
-//  - 131072 k-mer instances (icap = 8 x precap) as 64 ranges by the first three symbols of the k-mer: a histogram pass counts them, every range is sorted
-//    with the sort of precap = 16384 keys (a uniform window of 2000 strings has 5200 in its largest range); a range of more than precap hands the window on;
-//  - 32 bit task offsets and weight offsets (FastLds<CT>::toff_t): a traversal of 3400 stretches at k = 8 has more than 65535 (stretch, direction,
-//    position) tasks and up to 45324 feasible ones in a direction, so 65536 weight records per direction (with tier 15's 32768, 19 of the 37 windows of
-//    tests/xdeep_cases.py shape P overflow at k = 8; with 65536 none).
-// Pools, intervals and the lane scratch are tier 15's: the pending-path heap of a reverse enumeration that outgrows its lane's 32 ids is run again on the
-// whole scratch (lscrids = 4096 ids), which holds every path of the pool (rccap = 4096), so it never sends a window on by itself.
-template<> struct FastTier<16> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 4000, gw = 1, wcapg = 65536, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 8000, rpstcap = 768, lstr = 128, maxs = 2000, precap = 16384, ncap = 8190, scap = 4096, lcap = 16384, wcap = 65536, rccap = 4096, fcap = 1024, siqcap = 512, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 4096, wide = 0, mins = 250, gmem = 1 }; };
-static_assert(FastTier<16>::mins == VDEEP_MINS && FastTier<15>::maxs == XDEEP_MINS,"the deepest stage takes what the very deep stage hands on with more than 250 strings");
-// tier 18: the FULL-DEPTH stage, behind the deepest stage and in front of the generic engine (tier_pipeline.hpp: ID_FDEEP): windows of 2001 ... 5001 strings
-// -- 5001 is the deepest window a default run submits (-D 5000 overlaps and the A read) -- and the windows of 251 ... 2000 strings that overflowed one of
-// tier 16's tables (mins = 250).  Tier 16's code with twice its node table and capacities sized on the emulation (tests/fdeep_cases.py): 16384 nodes,
-// 12288 stretches, 49152 links, 12000 pool stretches, 131072 weight records per direction -- at k = 8 the deepest pile of a default run needs 9005 stretches
-// and 121390 forward records.  What a string
-// count above 2048 widens (FastLds<CT>::ywides, all other tiers keep their fields bit for bit):
-//  - compact string list: 13 bit string id | 18 bit first slot;
-//  - 262144 k-mer instances (icap = 16 x precap) as 256 ranges by the first FOUR symbols of the k-mer (k >= 4; a window at k = 3 is handed on), every range
-//    sorted with the sort of precap = 16384 keys;
-//  - stretch sort key: 15 bit node fields (FastEngine: KF).  The base sort orders (first, ext) and the stretch number alone -- two stretches that share
-//    (first, ext) send the window on, so length and last node never decide an order that is kept --: 15 + 15 + 14 bits.  The pool key keeps its four
-//    fields, 60 bits, and carries no stretch number;
-//  - key tables (mfirst, mlast, lastk) of 8192 entries, 80016 candidate error bytes, 79 chunks of 64 strings in the instance generation.
-//  - the four words per (stretch, direction) unit of the stretch feasibility live in device memory (the bytes of pregen), not in 4 x 384 registers.
-// Node frequencies stay capped at fqmax = 4095, so the weight widths are tier 16's.  Node ids, stretch ids and link offsets stay 16 bit words: 16384 nodes,
-// 12288 stretches and 49152 links are below 65535 (0xFFFF stays "none").
-template<> struct FastTier<18> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 12000, gw = 1, wcapg = 131072, rch = 16, fch = 16, fnw = 4, fnc = 72, idmax = 24000, rpstcap = 768, lstr = 128, maxs = 5001, precap = 16384, ncap = 16384, scap = 12288, lcap = 49152, wcap = 131072, rccap = 4096, fcap = 1024, siqcap = 512, blcap = 128, seqcap = 48, psiq = 10, consrow = 96, lscrids = 4096, wide = 0, mins = 250, gmem = 1 }; };
-static_assert(FastTier<18>::mins == VDEEP_MINS && FastTier<16>::maxs == FDEEP_MINS,"the full-depth stage takes what the deepest stage hands on with more than 250 strings");
-// tier 17: the LONG STRING stage of wide batches, on the second stream in front of the generic engine there (tier_pipeline.hpp: ID_LONG): the windows the
-// pre-scan set aside because a B string has more than 128 bases.  Tier 14 with a string stride of 256: FOUR 64 bit words per pattern mask (FastLds<CT>::pw),
-// strings of up to 255 bases -- the lengths and positions of a string are bytes (slen, ipos, irpos, canderr) --, a longer one is FFAIL(4) = FW_GENERIC and
-// goes on to the generic engine.  Tables, pools and the wide fields (two words per position mask, 128 symbol consensus, base lengths up to 191) are tier
-// 14's: what a long string can make longer than those hold -- a forward base length, a candidate, a consensus -- is refused by the checks that refuse it in
-// tier 14 (extendPath: over(2048), buildSeq: over(4096), FFAIL(9)) and the window goes on, nothing wraps (DESIGN 3.5 lists the audit).
-// oneslab: the whole working set of a workgroup is ONE buffer whose first byte is the layout's (L.base); the weights, the spill image and the instance
-// image follow the layout (FastLds<CT>::g_base) instead of preceding it, so a caller that has one buffer of FastCaps::ldsbytes for a stage and no slab
-// (the emulation's ROLE_LONG stage) runs the tier as it is.  Tiers 13 ... 16 keep their addressing.
-// tier 19: the WIDE DEEP stage of wide batches, behind the last stage (tier 14) and in front of the generic engine (tier_pipeline.hpp: ID_WDEEP): the windows of
-// 251 ... 1000 strings at w = 64 ... 127, which tiers 8, 9 and 14 refuse at their string count (mins = 250: what tier 14 could have held is passed on as it came).
-// Tier 14's code -- two words per position mask, 128 symbol consensus, the consensus -> A alignment inside the kernel -- under tier 15's compile-time widths
-// (FastLds<CT>::wides: 10 bit string ids, 16 bit node frequencies capped at 1023, 32 bit nps, the 32 byte forward record, the two-pass instance generation, key
-// tables of 1024 entries).  What the combination widens: a feasible stretch has up to 128 nodes here, 128 x 1023 table words < 2^49, so the high part of a stretch
-// weight has 17 bits (FastEngine: SROWS, SWHB) and the reverse record's third word 17 + 10; path weights are sums of at most seqcap = 96 stretches, < 2^56, and
-// live in whole 64 bit words.  What else the wide windows of several hundred strings need, sized on the emulation (tests/wdeep_cases.py):
-//  - 131072 k-mer instances (FastLds<CT>::hranges: icap = 8 x precap in tier 16's 64 ranges by the first three symbols, each sorted with the sort of
-//    precap = 16384 keys that tiers 13 ... 18 have; 17 bit first slots in the compact string list): 1000 strings of 100 bases carry 73800 at k = 10;
-//  - 32 bit task and weight offsets (FastLds<CT>::toff32): 3000 stretches with up to 128 start positions are far more than 65535 tasks; 98304 weight records per direction;
-//  - 8190 nodes, 4096 stretches (the 13 bit node fields and the 12 bit stretch number of the stretch sort key), 16384 links;
-//  - reverse pool of 16384 paths in 256 chunks of rch = 64: an enumeration's 32 chunk ids then name 2048 paths, where 512 sent 71 of 77 windows of a pile on;
-//    lscrids = 16384, so that the retry of a pending-path heap on the whole scratch holds every path of the pool;
-//  - the per-unit words of the stretch feasibility in device memory, as in tier 18 (128 chunks would be 512 registers).
-template<> struct FastTier<19> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 4000, gw = 1, wcapg = 98304, rch = 64, fch = 16, fnw = 4, fnc = 72, idmax = 8000, rpstcap = 768, lstr = 128, maxs = 1000, precap = 16384, ncap = 8190, scap = 4096, lcap = 16384, wcap = 98304, rccap = 16384, fcap = 2048, siqcap = 512, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 16384, wide = 1, mins = 250, gmem = 1 }; };
-static_assert(FastTier<19>::mins == VDEEP_MINS && FastTier<14>::maxs == VDEEP_MINS && FastTier<19>::maxs == FastTier<15>::maxs,"the wide deep stage takes what the last stage of a wide batch refuses at its string count");
-template<> struct FastTier<17> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 1000, gw = 1, wcapg = 16384, rch = 16, fch = 16, fnw = 8, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 256, maxs = 250, precap = 16384, ncap = 6144, scap = 1024, lcap = 8192, wcap = 16384, rccap = 4096, fcap = 4096, siqcap = 512, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 4096, wide = 1, mins = 0, gmem = 1, oneslab = 1 }; };
-// (only tier 17 names the enumerator: for every other tier FastOneSlab<CT>::value is 0)
-template<typename CT, typename = void> struct FastOneSlab { enum : uint32_t { value = 0 }; };
-template<typename CT> struct FastOneSlab<CT,decltype(void(CT::oneslab))> { enum : uint32_t { value = (CT::oneslab != 0) ? 1u : 0u }; };
-
-HDEV constexpr uint32_t fcpow2(uint32_t v) { uint32_t p = 1; while ( p < v ) p <<= 1; return p; }
-HDEV constexpr uint32_t fcmax(uint32_t a, uint32_t b) { return a > b ? a : b; }
-template<bool W, typename A, typename B> struct FWideSel { typedef A type; };
-template<typename A, typename B> struct FWideSel<false,A,B> { typedef B type; };
-
-/*
- * LDS layout of one wavefront.  FLD(name,type,count,start) declares an array at byte offset `start` (a constant
- * expression), its end offset e_name (8 byte aligned) and an accessor returning an LDS (address space 3) pointer, so
- * that every access compiles to ds_read/ds_write with a constant offset.
- */
-#define FLD(name,type,count,start) \
-	static constexpr uint32_t o_##name = (start); \
-	static constexpr uint32_t e_##name = (o_##name + static_cast<uint32_t>(sizeof(type))*static_cast<uint32_t>(count) + 7u) & ~7u; \
-	HDEV LDSQ type * name() const { return reinterpret_cast<LDSQ type *>(base + o_##name); }
-
-template<typename CT, bool GW = (CT::gw != 0)> struct FastLds;
-
-// legacy layout: everything in LDS (tiers 2-5)
-template<typename CT>
-struct FastLds<CT,false>
-{
-	LDSQ uint8_t * base;
-	static constexpr uint32_t keycap = fcpow2(CT::maxs < 2 ? 2 : CT::maxs);
-	typedef uint16_t toff_t; static constexpr bool wides = false, xwides = false, ywides = false, hranges = false; static constexpr uint32_t fqmax = 255u, icap = CT::precap;      // (more than 256 strings: gw layout only)
-	static_assert(CT::maxs <= 256,"the legacy layout has 8 bit node frequencies and string ids");
-	static_assert((CT::precap & (CT::precap-1)) == 0,"precap must be a power of two: the bitonic sorts pad to one");
-	static_assert(sizeof(typename CT::id_t) > 1 || (CT::fcap <= 256 && CT::rccap <= 256),"pool slots are recorded as id_t (pout)");
-	static_assert(CT::blcap <= 128 && (CT::blcap & 7) == 0,"base length buckets: two 64 bit occupancy words, cleared 8 at a time");
-	// ---- live during the whole window ----
-	static_assert(CT::lstr == 64 || CT::lstr == 128 || CT::lstr == 256,"string stride: one, two or four 64 bit words per pattern mask");
-	static constexpr uint32_t pw = CT::lstr/64;      // words per pattern mask
-	static constexpr uint32_t maxlen = CT::lstr < 256u ? static_cast<uint32_t>(CT::lstr) : 255u;      // longest string the layout holds
-	typedef uint8_t sid_t;      // stretch ids are 8 bits in the legacy layout
-	static_assert(sizeof(typename CT::sid_t) == 1,"16 bit stretch ids need the gw layout");
-	FLD(str,uint8_t,CT::maxs*CT::lstr,0)
-	FLD(slen,uint8_t,CT::maxs,e_str)
-	FLD(peq,uint64_t,CT::maxs*4*pw,e_slen)      // pattern masks of string j: words 4*pw*j + pw*symbol + word
-	FLD(ipos,uint8_t,CT::precap,e_peq)
-	FLD(irpos,uint8_t,CT::precap,e_ipos)
-	FLD(nv,uint32_t,CT::ncap,e_irpos)
-	FLD(nps,uint16_t,CT::ncap+1,e_nv)
-	FLD(nfreq,uint8_t,CT::ncap,e_nps)
-	FLD(succ0,uint16_t,CT::ncap,e_nfreq)
-	FLD(sinfo,uint16_t,CT::ncap,e_succ0)
-	FLD(npred,uint8_t,CT::ncap,e_sinfo)
-	FLD(nrange,uint32_t,CT::ncap,e_npred)   // feasible position range of a node: pfrom | pto<<8 | cpfrom<<16 | cpto<<24
-	FLD(mfirst,uint64_t,keycap,e_nrange)
-	FLD(mlast,uint64_t,keycap,e_mfirst)
-	FLD(suplo8,uint8_t,FSUPCAP,e_mlast)
-	FLD(suphi8,uint8_t,FSUPCAP,e_suplo8)
-	// small scratch of the serial code (dynamically indexed, so it must not live in registers)
-	FLD(vrem,uint8_t,8,e_suphi8)
-	FLD(vadd,uint8_t,8,e_vrem)
-	FLD(vapos,uint8_t,8,e_vadd)
-	FLD(vfn,uint16_t,8,e_vapos)
-	FLD(vln,uint16_t,8,e_vfn)
-	FLD(sstack,uint16_t,3*24,e_vln)
-	FLD(chain,uint8_t,64,e_sstack)
-	FLD(midpar,uint16_t,8,e_chain)          // middle pieces of twice-split stretches: parent stretch, node range [midA,midB]
-	FLD(midA,uint8_t,8,e_midpar)
-	FLD(midB,uint8_t,8,e_midA)
-	static constexpr uint32_t ubase = e_midB;
-	// ---- overlay A: build phase ----
-	FLD(pre,uint64_t,CT::precap,ubase)
-	FLD(lastk,uint64_t,keycap,e_pre)
-	static constexpr uint32_t uA = e_lastk;
-	// ---- overlay B: traversal phase ----
-	FLD(sfirst,uint16_t,CT::scap,ubase)
-	FLD(slast,uint16_t,CT::scap,e_sfirst)
-	FLD(sslen,uint16_t,CT::scap,e_slast)
-	FLD(slink,uint16_t,CT::scap,e_sslen)
-	FLD(maskF,uint64_t,CT::scap,e_slink)
-	FLD(maskR,uint64_t,CT::scap,e_maskF)
-	FLD(woffF,uint16_t,CT::scap,e_maskR)
-	FLD(woffR,uint16_t,CT::scap,e_woffF)
-	FLD(links,uint16_t,CT::lcap,e_woffR)
-	// weights of the feasible (stretch, position) pairs: whole stretch (48 bit), its first node in walking direction and,
-	// forward only, its last node (40 bit each), split into 32 bit low words and high parts
-	FLD(wF_lo,uint32_t,CT::wcap,e_links)
-	FLD(wF1_lo,uint32_t,CT::wcap,e_wF_lo)
-	FLD(wFl_lo,uint32_t,CT::wcap,e_wF1_lo)
-	FLD(wR_lo,uint32_t,CT::wcap,e_wFl_lo)
-	FLD(wR1_lo,uint32_t,CT::wcap,e_wR_lo)
-	FLD(wF_hi,uint16_t,CT::wcap,e_wR1_lo)
-	FLD(wR_hi,uint16_t,CT::wcap,e_wF_hi)
-	FLD(wF1_hi,uint8_t,CT::wcap,e_wR_hi)
-	FLD(wFl_hi,uint8_t,CT::wcap,e_wF1_hi)
-	FLD(wR1_hi,uint8_t,CT::wcap,e_wFl_hi)
-	// lookup of stretches by first / last node: head index per node, base stretches ordered by (last node, id)
-	FLD(lhead,uint8_t,CT::ncap,e_wR1_hi)
-	FLD(lord,uint32_t,CT::scap,e_lhead)
-	FLD(ppos,uint8_t,CT::scap,e_lord)      // pieces: number of base stretches sorting before them
-	FLD(fkmer,uint32_t,CT::fnc,e_ppos)
-	FLD(lkmer,uint32_t,CT::fnc,e_fkmer)
-	FLD(fnode,uint16_t,CT::fnc,e_lkmer)
-	FLD(lnode,uint16_t,CT::fnc,e_fnode)
-	FLD(parF,uint8_t,CT::fnc,e_lnode)
-	FLD(posF,uint8_t,CT::fnc,e_parF)
-	FLD(parL,uint8_t,CT::fnc,e_posF)
-	FLD(posL,uint8_t,CT::fnc,e_parL)
-	FLD(pieF,uint8_t,CT::fnc,e_posL)      // first piece id of candidate i (second = +1), FNOPAR if none
-	FLD(pieL,uint8_t,CT::fnc,e_pieF)
-	static constexpr uint32_t consmax = MAXCONS;
-	static_assert(CT::wide == 0,"the wide tier needs the gw layout");
-	FLD(bestL,uint8_t,MAXCONS,e_pieL)      // best consensus so far (survives the tries)
-	FLD(cdh,FCC,16,e_bestL)
-	static_assert(uA <= o_cdh,"the model table copy (from o_cdh on) is loaded for gap filling while the instance array is live");
-	FLD(cseq,uint8_t,18*CT::seqcap,e_cdh)      // stretch sequences of the kept candidates (16 slots) + current + previous
-	// dead until the kept candidates are decoded: shared with the lane scratch of the enumerations (lscr: per lane a
-	// heap of 32 path ids / of 12 path ids / of PSIQ score intervals; all of it for an enumeration on lane 0 alone)
-	FLD(ch,FCC,16,e_cseq)
-	FLD(acc,FCC,16,e_ch)
-	FLD(accerr,uint32_t,16,e_acc)
-	FLD(canderr,uint8_t,16*CT::maxs,e_accerr)
-	FLD(consL,uint8_t,16*CT::consrow,e_canderr)   // decoded candidates
-	static constexpr uint32_t lscrbytes = static_cast<uint32_t>(CT::lscrids)*static_cast<uint32_t>(sizeof(typename CT::id_t));
-	FLD(lscr,uint8_t,lscrbytes,e_cseq)
-	FLD(siq,FSI,CT::siqcap,e_cseq)          // score intervals of a pair combined on lane 0
-	static_assert(sizeof(FSI)*CT::siqcap <= lscrbytes,"the serial score interval heap shares the lane scratch");
-	static constexpr uint32_t pbase = fcmax(e_consL,e_lscr);
-	// reverse pool: paths by pool id
-	FLD(rc_w,uint64_t,CT::rccap,pbase)
-	FLD(rc_parent,typename CT::id_t,CT::rccap,e_rc_w)
-	FLD(rc_stretch,uint8_t,CT::rccap,e_rc_parent)
-	FLD(rc_pos,uint8_t,CT::rccap,e_rc_stretch)
-	FLD(rc_len,uint8_t,CT::rccap,e_rc_pos)
-	FLD(rc_baselen,uint8_t,CT::rccap,e_rc_len)
-	FLD(rc_acc,typename CT::id_t,CT::rccap,e_rc_baselen)     // accepted paths of an enumeration, in its own slots
-	// sorted blocks of the reverse enumerations
-	FLD(rc_ord,typename CT::id_t,CT::rccap,e_rc_acc)
-	FLD(rc_arw,typename CT::id_t,CT::rccap,e_rc_ord)
-	FLD(rc_sbl,uint8_t,CT::rccap,e_rc_arw)         // base length of the i-th entry in sorted order
-	FLD(rc_front,uint32_t,CT::rccap,e_rc_sbl)      // front k-mer of the i-th entry in sorted order
-	FLD(rbase,uint16_t,CT::fnc+1,e_rc_front)
-	FLD(rn,uint16_t,CT::fnc+1,e_rbase)
-	FLD(rmaxw,uint64_t,CT::fnc+1,e_rn)
-	FLD(rtmask,uint64_t,CT::fnc+1,e_rmaxw)
-	FLD(rfmask,uint64_t,CT::fnc+1,e_rtmask)    // one bit per front k-mer (value mod 64) of the accepted reverse paths
-	// forward pool: paths by pool id
-	FLD(f_w,uint64_t,CT::fcap,e_rfmask)
-	FLD(f_parent,typename CT::id_t,CT::fcap,e_f_w)
-	FLD(f_stretch,uint8_t,CT::fcap,e_f_parent)
-	FLD(f_pos,uint8_t,CT::fcap,e_f_stretch)
-	FLD(f_baselen,uint8_t,CT::fcap,e_f_pos)
-	FLD(f_len,uint8_t,CT::fcap,e_f_baselen)
-	// popped paths of a tree (pop order, in the tree's own slots): path, candidate length, k-mer of its last node, weight
-	// minus the junction node
-	FLD(fp_id,typename CT::id_t,CT::fcap,e_f_len)
-	FLD(fp_cl,uint8_t,CT::fcap,e_fp_id)
-	FLD(fp_front,uint32_t,CT::fcap,e_fp_cl)
-	FLD(fp_adj,uint64_t,CT::fcap,e_fp_front)
-	// per first k-mer candidate: chunk list of its tree, popped paths, junction k-mer bits, scan target bits, heaviest path
-	FLD(fchb,uint8_t,8*CT::fnw*(CT::fnc+1),e_fp_adj)   // chunk ids of the forward trees: 8*fnw per first k-mer candidate (+ one exact tree)
-	FLD(fnp,uint16_t,CT::fnc+1,e_fchb)
-	FLD(ffm,uint64_t,CT::fnc+1,e_fnp)
-	FLD(ftm,uint64_t,CT::fnc+1,e_ffm)
-	FLD(fmx,uint64_t,CT::fnc+1,e_ftm)
-	// recorded (path, entry) sequences of the pairs of a round
-	FLD(pout,typename CT::id_t,32*32,e_fmx)
-	FLD(poutn,uint8_t,64,e_pout)
-	FLD(ctr,uint32_t,4,e_poutn)
-	FLD(rchx,uint8_t,32,e_ctr)              // chunk ids of a reverse enumeration on lane 0 alone
-	static constexpr uint32_t upool = e_rchx;
-	// chunk ids of the reverse enumerations of all last k-mers (32 per lane, lanes < min(fnc,64)): over the per first k-mer tables, which are
-	// written after those enumerations have been copied to their blocks
-	FLD(rchb,uint8_t,(CT::fnc < 64 ? CT::fnc : 64u)*32,o_fchb)
-	static_assert(e_rchb <= o_pout,"reverse chunk lists must fit the per first k-mer tables");
-	// raw stretches (overlay of the caches)
-	FLD(tfirst,uint16_t,CT::scap,pbase)
-	FLD(tlast,uint16_t,CT::scap,e_tfirst)
-	FLD(tslen,uint16_t,CT::scap,e_tlast)
-	FLD(tlink,uint16_t,CT::scap,e_tslen)
-	FLD(skey,uint64_t,fcpow2(CT::scap),e_tlink)
-	static constexpr uint32_t uraw = e_skey;
-	// final alignment (overlay of the caches)
-	FLD(alpv,uint64_t,MAXCONS+1,pbase)
-	FLD(almv,uint64_t,MAXCONS+1,e_alpv)
-	FLD(albot,uint16_t,MAXCONS+1,e_almv)
-	FLD(alops,uint8_t,2*MAXCONS+2*64+8,e_albot)
-	static constexpr uint32_t ualn = e_alops;
-	static constexpr uint32_t uend = fcmax(fcmax(uA,uraw),fcmax(upool,ualn));
-	// scratch behind the build overlay (gap filling)
-	FLD(gfbuf,uint64_t,(pbase-uA)/8,uA)
-	static constexpr uint32_t gfcap = (pbase-uA)/8;
-	// fixed-point model table [pos][row], row stride nrows+1.  It shares the bytes of the enumeration pools: it is
-	// (re)loaded from HBM/L2 for gap filling and for the stretch feasibility of a traverse call, both of which are over
-	// before the pools are used.
-	// feasibility tasks (with the table, dead before the pools are used): first task, first and end start position of
-	// every (stretch, direction)
-	static constexpr uint32_t taskbytes = ((2*CT::scap+2)*2 + 2*(2*CT::scap) + 15u) & ~15u;
-	FLD(toff,uint16_t,2*CT::scap+2,upool-taskbytes)
-	FLD(ulo,uint8_t,2*CT::scap,e_toff)
-	FLD(uhi,uint8_t,2*CT::scap,e_ulo)
-	FLD(tab,uint32_t,(upool-taskbytes-o_cdh)/4,o_cdh)   // also over the candidate buffers, which are dead at that time
-	static constexpr uint32_t tabcap = (upool-taskbytes-o_cdh)/4;
-	HDEV static uint32_t bytes(uint32_t const, uint32_t const) { return (uend + 15u) & ~15u; }
-	// scratch of the stretch construction, the candidate search and the reachability test: borrowed from the weight arrays,
-	// which are written after them.  Walk slots (wtmp) of 64 node ids each in front, the walking table behind them.
-	static_assert(6u*CT::ncap + 16u <= e_wR1_hi - o_wF_lo,"scratch tables of the stretch walk must fit the weight arrays");
-	static_assert(CT::wcap*4 >= CT::ncap*2,"interior node table must fit the weight array it borrows");
-	static_assert(2u*CT::ncap + CT::scap + 8u <= 4u*CT::wcap,"reachability scratch must fit the first weight array");
-	HDEV LDSQ uint32_t * xcnt32() const { return reinterpret_cast<LDSQ uint32_t *>(base + o_wF_lo); }
-	HDEV LDSQ uint16_t * xstep() const { return reinterpret_cast<LDSQ uint16_t *>(base + ((e_wR1_hi - 2u*CT::ncap) & ~7u)); }
-	HDEV LDSQ uint16_t * xwtmp() const { return reinterpret_cast<LDSQ uint16_t *>(base + o_wF_lo); }
-	static constexpr uint32_t xnslot = (((e_wR1_hi - 2u*CT::ncap) & ~7u) - o_wF_lo) / 128u;
-	HDEV LDSQ uint16_t * xsid() const { return reinterpret_cast<LDSQ uint16_t *>(base + o_wR_lo); }
-	HDEV LDSQ uint8_t * xspos() const { return reinterpret_cast<LDSQ uint8_t *>(base + o_wR1_lo); }
-	HDEV LDSQ uint8_t * xreach() const { return reinterpret_cast<LDSQ uint8_t *>(base + o_wF_lo); }
-};
-
-/*
- * gw layout (tier 1 since round 3).  Three regions:
- *   P  live during the whole window: string lengths, support bounds, serial scratch, node keys, fhead, best consensus;
- *   S  results of the build phase that the first phases of a traversal (stretches, candidates, feasibility) and its last
- *      ones (candidate errors, next activation state) need, but not the enumerations and the pairs in between: the
- *      enumeration pools are laid over S, whose bytes are spilled to the workgroup's global slab before the
- *      enumerations and restored after the pairs (two bulk copies of 12 KB per traversal);
- *   X  overlay A (sorted instances, build phase) / overlay B (stretches, candidates, candidate heap, lane scratch).
- * The weights of the feasible (stretch, position) pairs (16 of the 54 KB of the legacy tier 1) live in the global slab,
- * the model table is read from its padded 32 bit copy in global memory (both stay in L1/L2).  The scratch tables of the
- * stretch construction sit in parts of overlay B that are written later (pattern masks: raw stretches; candidate heap,
- * sequences and lane scratch: predecessor counts, walking table, interior nodes, reachability, feasibility tasks).
- */
-template<typename CT>
-struct FastLds<CT,true>
-{
-	LDSQ uint8_t * base;
-	static constexpr uint32_t keycap = fcpow2(CT::maxs < 2 ? 2 : CT::maxs);
-	// (precap need not be a power of two in this layout: the sorts touch only the n keys there are; the padding of the overlap
-	// sort at the start of a window is checked against it)
-	static_assert(sizeof(typename CT::id_t) > 1 || (CT::fcap <= 256 && CT::rccap <= 256),"pool slots are recorded as id_t (pout)");
-	static_assert(CT::blcap <= 128 && (CT::blcap & 7) == 0,"base length buckets: two 64 bit occupancy words, cleared 8 at a time");
-	static_assert(CT::lstr == 64 || CT::lstr == 128 || CT::lstr == 256,"the gw layout holds strings of up to 64 bases in one word per pattern mask, of up to 128 in two (round 6), of up to 255 in four (tier 17)");
-	static constexpr uint32_t pw = CT::lstr/64;
-	static constexpr uint32_t maxlen = CT::lstr < 256u ? static_cast<uint32_t>(CT::lstr) : 255u;      // longest string the layout holds: its length is a byte
-	static constexpr bool oneslab = FastOneSlab<CT>::value != 0;      // FastTier<17>: layout and slab in one buffer, the layout first
-	typedef typename CT::sid_t sid_t;      // stretch ids: 8 bits (at most 250 stretches) or 16 bits
-	// more than 256 strings (tier 15): 16 bit node frequencies capped at fqmax, 32 bit first-instance offsets, a 32 byte forward weight record
-	static constexpr bool wides = CT::maxs > 256;
-	// more than 1024 strings (tier 16): node frequencies up to 4095, 64 instance ranges, 32 bit task offsets
-	static constexpr bool xwides = CT::maxs > 1024;
-	// more than 2048 strings (tier 18): 256 instance ranges, 15 bit node fields in the stretch sort key
-	static constexpr bool ywides = CT::maxs > 2048;
-	static constexpr uint32_t fqmax = xwides ? 4095u : (wides ? 1023u : 255u);
-	// k-mer instances the layout holds: precap, the capacity of one instance sort -- with more than 256 strings four such ranges, with more than
-	// 1024 strings 64 ranges that share eight times precap, with more than 2048 strings 256 ranges that share sixteen times precap (buildInstances).
-	// hranges: the ranges are counted by a histogram pass.  The wide tier of more than 256 strings as well: its strings are up to twice as long, and
-	// 792 strings of 100 bases have more than precap instances in each of four ranges
-	static constexpr bool hranges = xwides || (wides && CT::wide != 0);
-	static constexpr uint32_t icap = ywides ? 16u*CT::precap : (hranges ? 8u*CT::precap : (wides ? 4u*CT::precap : CT::precap));
-	// (the wide tier of more than 256 strings as well: a traversal of 1300 stretches has 2 x 1300 x up to 128 (stretch, direction, position) tasks)
-	static constexpr bool toff32 = xwides || (wides && CT::wide != 0);
-	typedef typename FWideSel<toff32,uint32_t,uint16_t>::type toff_t;
-	typedef typename FWideSel<wides,uint16_t,uint8_t>::type nfreq_t;
-	typedef typename FWideSel<wides,uint32_t,uint16_t>::type nps_t;
-	static_assert(fqmax <= (1u << (8u*sizeof(nfreq_t))) - 1u,"a node frequency holds fqmax");
-	static_assert(icap <= (sizeof(nps_t) == 2 ? 65535u : 0xFFFFFFFFu),"nps[nn] = npre <= icap must fit a first-instance offset");
-	// ---- P ----
-	FLD(slen,uint8_t,CT::maxs,0)
-	static_assert(maxlen <= 255u,"slen: a string's length is a byte");
-	static constexpr uint32_t supcap = CT::wide ? static_cast<uint32_t>(FSUPCAPW) : static_cast<uint32_t>(FSUPCAP);
-	FLD(suplo8,uint8_t,supcap,e_slen)
-	FLD(suphi8,uint8_t,supcap,e_suplo8)
-	FLD(vrem,uint8_t,8,e_suphi8)
-	FLD(vadd,uint8_t,8,e_vrem)
-	FLD(vapos,uint8_t,8,e_vadd)
-	FLD(vfn,uint16_t,8,e_vapos)
-	FLD(vln,uint16_t,8,e_vfn)
-	FLD(sstack,uint16_t,3*24,e_vln)
-	FLD(chain,uint8_t,64,e_sstack)
-	FLD(midpar,uint16_t,8,e_chain)          // middle pieces of twice-split stretches: parent stretch, node range [midA,midB]
-	FLD(midA,uint8_t,8,e_midpar)
-	FLD(midB,uint8_t,8,e_midA)
-	FLD(nv,uint32_t,CT::ncap,e_midB)
-	FLD(npred,sid_t,CT::ncap,e_nv)
-	// longest consensus / candidate of this tier: MAXCONS, 128 in the wide tier (consensus of a window of up to 127 bases)
-	static constexpr uint32_t consmax = CT::wide ? 128u : static_cast<uint32_t>(MAXCONS);
-	static constexpr uint32_t alw = CT::wide ? 2u : 1u;      // 64 bit words per column of the consensus -> A alignment
-	FLD(bestL,uint8_t,consmax,e_npred)
-	static constexpr uint32_t sbase = (e_bestL + 15u) & ~15u;
-	// ---- S (spilled while the pools are live) ----
-	// (round 5: no string array -- the pattern masks ARE the strings: symbol c at position p of string j <=> bit p of peq[4*j+c]; they are
-	// built by ballots while the bases are gathered and the k-mers are cut from them; the 64 bytes per string went into the node tables)
-	FLD(peq,uint64_t,CT::maxs*4*pw,sbase)
-	FLD(ipos,uint8_t,icap,e_peq)
-	FLD(irpos,uint8_t,icap,e_ipos)
-	static_assert(supcap <= 255u && maxlen <= 255u,"ipos / irpos: the position of a k-mer in its string, from either end, is stored as min(position,nsup) <= supcap in a byte");
-	FLD(nps,nps_t,CT::ncap+1,e_irpos)
-	FLD(nfreq,nfreq_t,CT::ncap,e_nps)
-	FLD(succ0,uint16_t,CT::ncap,e_nfreq)
-	FLD(sinfo,uint16_t,CT::ncap,e_succ0)
-	FLD(nrange,uint32_t,CT::ncap,e_sinfo)
-	FLD(mfirst,uint64_t,keycap,e_nrange)
-	FLD(mlast,uint64_t,keycap,e_mfirst)
-	static constexpr uint32_t send = (e_mlast + 15u) & ~15u;
-	static constexpr uint32_t sbytes = send - sbase;
-	// ---- enumeration pools: overlay of S ----
-	FLD(rc_w,uint64_t,CT::rccap,sbase)
-	FLD(rc_parent,typename CT::id_t,CT::rccap,e_rc_w)
-	FLD(rc_stretch,sid_t,CT::rccap,e_rc_parent)
-	FLD(rc_pos,uint8_t,CT::rccap,e_rc_stretch)
-	FLD(rc_len,uint8_t,CT::rccap,e_rc_pos)
-	FLD(rc_baselen,uint8_t,CT::rccap,e_rc_len)
-	FLD(rc_acc,typename CT::id_t,CT::rccap,e_rc_baselen)
-	FLD(rc_ord,typename CT::id_t,CT::rccap,e_rc_acc)
-	FLD(rc_arw,typename CT::id_t,CT::rccap,e_rc_ord)
-	FLD(rc_sbl,uint8_t,CT::rccap,e_rc_arw)
-	FLD(rc_front,uint32_t,CT::rccap,e_rc_sbl)
-	FLD(rbase,uint16_t,CT::fnc+1,e_rc_front)
-	FLD(rn,uint16_t,CT::fnc+1,e_rbase)
-	FLD(rmaxw,uint64_t,CT::fnc+1,e_rn)
-	FLD(rtmask,uint64_t,CT::fnc+1,e_rmaxw)
-	FLD(rfmask,uint64_t,CT::fnc+1,e_rtmask)
-	FLD(f_w,uint64_t,CT::fcap,e_rfmask)
-	FLD(f_parent,typename CT::id_t,CT::fcap,e_f_w)
-	FLD(f_stretch,sid_t,CT::fcap,e_f_parent)
-	FLD(f_pos,uint8_t,CT::fcap,e_f_stretch)
-	FLD(f_baselen,uint8_t,CT::fcap,e_f_pos)
-	FLD(f_len,uint8_t,CT::fcap,e_f_baselen)
-	FLD(fp_id,typename CT::id_t,CT::fcap,e_f_len)
-	FLD(fp_cl,uint8_t,CT::fcap,e_fp_id)
-	FLD(fp_front,uint32_t,CT::fcap,e_fp_cl)
-	FLD(fp_adj,uint64_t,CT::fcap,e_fp_front)
-	FLD(fchb,uint8_t,8*CT::fnw*(CT::fnc+1),e_fp_adj)
-	FLD(fnp,uint16_t,CT::fnc+1,e_fchb)
-	FLD(ffm,uint64_t,CT::fnc+1,e_fnp)
-	FLD(ftm,uint64_t,CT::fnc+1,e_ffm)
-	FLD(fmx,uint64_t,CT::fnc+1,e_ftm)
-	FLD(pout,typename CT::id_t,32*32,e_fmx)
-	FLD(poutn,uint8_t,64,e_pout)
-	FLD(ctr,uint32_t,4,e_poutn)
-	FLD(rchx,uint8_t,32,e_ctr)
-	static constexpr uint32_t upool = e_rchx;
-	// (pools larger than the build-phase arrays run on into a gap in front of the overlays: tier 3, whose reverse pool is sized
-	// for the 72 last k-mer candidates of a 54x pile -- 256 chunks of 8 paths, the most an 8 bit chunk id can name)
-	FLD(rchb,uint8_t,(CT::fnc < 64 ? CT::fnc : 64u)*32,o_fchb)
-	static_assert(e_rchb <= o_pout,"reverse chunk lists must fit the per first k-mer tables");
-	static constexpr uint32_t ubase = fcmax(send,(upool + 15u) & ~15u);
-	// ---- overlay A: build phase ----
-	FLD(pre,uint64_t,icap,ubase)
-	FLD(lastk,uint64_t,keycap,e_pre)
-	static constexpr uint32_t uA = e_lastk;
-	// ---- overlay B: traversal ----
-	FLD(sfirst,uint16_t,CT::scap,ubase)
-	FLD(slast,uint16_t,CT::scap,e_sfirst)
-	FLD(sslen,uint16_t,CT::scap,e_slast)
-	FLD(slink,uint16_t,CT::scap,e_sslen)
-	FLD(maskF,uint64_t,CT::scap,e_slink)
-	FLD(maskR,uint64_t,CT::scap,e_maskF)
-	FLD(maskFh,uint64_t,(CT::wide ? CT::scap : 0u),e_maskR)      // wide tier: start positions 64 ... 127
-	FLD(maskRh,uint64_t,(CT::wide ? CT::scap : 0u),e_maskFh)
-	FLD(woffF,toff_t,CT::scap,e_maskRh)      // (toff_t: 16 bits, wcap <= 65535; more than 1024 strings: 32 bits)
-	FLD(woffR,toff_t,CT::scap,e_woffF)
-	static_assert(sizeof(toff_t) == 4 || CT::wcap <= 65535u,"weight offsets of 16 bits");
-	FLD(links,uint16_t,CT::lcap,e_woffR)
-	FLD(lhead,sid_t,CT::ncap,e_links)
-	FLD(lord,uint32_t,CT::scap,e_lhead)
-	FLD(ppos,sid_t,CT::scap,e_lord)
-	FLD(fkmer,uint32_t,CT::fnc,e_ppos)
-	FLD(lkmer,uint32_t,CT::fnc,e_fkmer)
-	FLD(fnode,uint16_t,CT::fnc,e_lkmer)
-	FLD(lnode,uint16_t,CT::fnc,e_fnode)
-	FLD(parF,sid_t,CT::fnc,e_lnode)
-	FLD(posF,uint8_t,CT::fnc,e_parF)
-	FLD(parL,sid_t,CT::fnc,e_posF)
-	FLD(posL,uint8_t,CT::fnc,e_parL)
-	FLD(pieF,sid_t,CT::fnc,e_posL)
-	FLD(pieL,sid_t,CT::fnc,e_pieF)
-	static constexpr uint32_t xbase = (e_pieL + 15u) & ~15u;
-	FLD(cdh,FCC,16,xbase)
-	FLD(cseq,sid_t,18*CT::seqcap,e_cdh)
-	FLD(ch,FCC,16,e_cseq)
-	FLD(acc,FCC,16,e_ch)
-	FLD(accerr,uint32_t,16,e_acc)
-	FLD(canderr,uint8_t,16*CT::maxs,e_accerr)
-	static_assert(fcmax(maxlen,CT::consrow) <= 255u,"canderr: the error of a candidate against one string is at most max(string,candidate), a byte");
-	FLD(consL,uint8_t,16*CT::consrow,e_canderr)
-	static constexpr uint32_t lscrbytes = static_cast<uint32_t>(CT::lscrids)*static_cast<uint32_t>(sizeof(typename CT::id_t));
-	FLD(lscr,uint8_t,lscrbytes,e_cseq)
-	FLD(siq,FSI,CT::siqcap,e_cseq)
-	static_assert(sizeof(FSI)*CT::siqcap <= lscrbytes,"the serial score interval heap shares the lane scratch");
-	// (the scratch tables of the stretch construction need 3 bytes per node: the region is at least that long)
-	static constexpr uint32_t alnbytes = 2u*8u*alw*(consmax+1u) + 2u*(consmax+1u) + 8u + (2u*consmax + 2u*64u + 8u) + 16u;      // alpv, almv, albot, alops
-	static constexpr uint32_t uB = fcmax(fcmax(fcmax(fcmax(e_consL,e_lscr),xbase + 3u*CT::ncap + 16u),xbase + (2u*CT::scap+2u)*static_cast<uint32_t>(sizeof(toff_t)) + 8u + 8u*CT::scap + 16u),CT::wide ? xbase + alnbytes : 0u);
-	static constexpr uint32_t xbytes = uB - xbase;
-	// raw stretches: over the pattern masks and weight offsets, which the feasibility writes later
-	FLD(tfirst,uint16_t,CT::scap,o_maskF)
-	FLD(tlast,uint16_t,CT::scap,e_tfirst)
-	FLD(tslen,uint16_t,CT::scap,e_tlast)
-	FLD(tlink,uint16_t,CT::scap,e_tslen)
-	FLD(skey,uint64_t,fcpow2(CT::scap),e_tlink)
-	static_assert(e_skey <= o_links,"raw stretches must fit the mask / offset arrays they borrow");
-	// scratch over [xbase,uB): candidate heap, sequences and lane scratch are written by the enumerations only
-	FLD(alpv,uint64_t,alw*(consmax+1),xbase)
-	FLD(almv,uint64_t,alw*(consmax+1),e_alpv)
-	FLD(albot,uint16_t,consmax+1,e_almv)
-	FLD(alops,uint8_t,2*consmax+2*64+8,e_albot)
-	static_assert(e_alops <= uB,"final alignment scratch");
-	FLD(toff,toff_t,2*CT::scap+2,xbase)
-	FLD(urec,uint32_t,2*CT::scap,e_toff)      // unit at position q of the processing order: lo | unit << 7
-	static_assert(e_urec <= uB,"feasibility tasks");
-	static_assert(3u*CT::ncap + 16u <= xbytes,"predecessor counts (a byte per node) and walking table must fit the scratch");
-	static_assert(3u*CT::ncap + 16u <= xbytes && 2u*CT::ncap + CT::scap + 8u <= xbytes,"interior node table / reachability scratch");
-	HDEV LDSQ uint32_t * xcnt32() const { return reinterpret_cast<LDSQ uint32_t *>(base + xbase); }
-	HDEV LDSQ uint16_t * xstep() const { return reinterpret_cast<LDSQ uint16_t *>(base + xbase + ((CT::ncap + 3u) & ~3u) + 8u); }
-	HDEV LDSQ uint16_t * xsid() const { return reinterpret_cast<LDSQ uint16_t *>(base + xbase); }
-	HDEV LDSQ uint8_t * xspos() const { return reinterpret_cast<LDSQ uint8_t *>(base + xbase + 2u*CT::ncap + 8u); }
-	HDEV LDSQ uint8_t * xreach() const { return reinterpret_cast<LDSQ uint8_t *>(base + xbase); }
-	// (more than 256 strings: the instances as they are generated, before they are split into the four sorted ranges of `pre`; behind both overlays)
-	FLD(pregen,uint64_t,(wides ? icap : 0u),((fcmax(uA,uB) + 15u) & ~15u))
-	// scratch behind the build overlay (gap filling): small in this layout, a window that needs more goes to the next tier
-	// (one-slab tier: nothing comes behind it but the generic engine, and the windows of noisy sequence that carry its long strings reach filter frequency 0
-	// more often than others -- a region of its own behind both overlays, 16384 records and as many candidates; where the build overlay is the longer
-	// one, as in tiers 14 and 17, the shared scratch has no room at all)
-	static constexpr uint32_t gfown = (oneslab && !wides) ? 32768u : 0u;
-	FLD(gfbuf,uint64_t,(gfown ? gfown : (uB > uA ? (uB-uA)/8 : 0u)),(gfown ? ((fcmax(uA,uB) + 15u) & ~15u) : uA))
-	static constexpr uint32_t gfcap = gfown ? gfown : (uB > uA ? (uB-uA)/8 : 0u);
-	static constexpr uint32_t uend = wides ? e_pregen : (gfown ? e_gfbuf : fcmax(uA,uB));
-	static constexpr uint32_t tabcap = 0x7FFFFFFFu;      // no LDS copy of the model table
-	HDEV static uint32_t bytes(uint32_t const, uint32_t const) { return (uend + 15u) & ~15u; }
-	// the global slab of a workgroup: forward weights, reverse weights (16 bytes per entry), spill of S; the walk slots of
-	// the stretch construction borrow the weight part
-	// (round 4) behind the spill image: the sorted k-mer instances and last k-mers of the current k, saved before the first
-	// traversal of a pass overwrites overlay A, so that the next filter frequency pass reloads them instead of sorting again
-	// (wides: the forward record is 32 bytes -- three 64 bit weights --, the reverse record stays 16)
-	static constexpr uint32_t recFbytes = wides ? 32u : 16u;
-	static constexpr uint32_t g_wF = 0, g_wR = recFbytes*CT::wcapg, g_spill = (recFbytes+16u)*CT::wcapg, g_inst = ((g_spill + sbytes + 255u) & ~255u),
-		g_bytes = g_inst + (((icap + keycap)*8u + 255u) & ~255u);
-	static_assert((o_pre & 15u) == 0 && (icap & 1u) == 0 && (keycap & 1u) == 0,"instance arrays are saved 16 bytes at a time");
-	static constexpr uint32_t xnslot = g_spill / 128u;
-	// device-memory tiers (CT::gmem): this layout itself sits behind the instance image, g_total bytes per workgroup in all
-	static constexpr uint32_t g_layout = g_bytes, g_total = CT::gmem ? g_bytes + ((((uend + 15u) & ~15u) + 255u) & ~255u) : g_bytes;
-	// one-slab tiers (FastTier<17>::oneslab): the layout comes FIRST -- base is the first byte of the workgroup's buffer -- and the g_* part follows it at g_base
-	// (processWindowFast: E.gslab = base + g_base); the buffer has the same g_total bytes
-	static constexpr uint32_t g_base = oneslab ? ((((uend + 15u) & ~15u) + 255u) & ~255u) : 0u;
-	static_assert(!oneslab || CT::gmem != 0,"a one-slab tier is a device-memory tier");
-};
-#undef FLD
-
-template<typename CT>
-HDEV FastCaps fastCapsOf(uint32_t const nrows, uint32_t const nsup)
-{
-	FastCaps C;
-	C.maxs = CT::maxs; C.precap = FastLds<CT>::icap; C.ncap = CT::ncap; C.scap = CT::scap; C.lcap = CT::lcap; C.wcap = CT::wcap; C.rccap = CT::rccap;
-	C.fcap = CT::fcap; C.siqcap = CT::siqcap; C.blcap = CT::blcap;
-	C.nrows = nrows; C.nsup = nsup;
-	C.ldsbytes = FastLds<CT>::bytes(nrows,nsup);
-	C.tabcap = FastLds<CT>::tabcap;
-	if constexpr ( CT::gw != 0 ) C.gbytes = FastLds<CT>::g_total; else C.gbytes = 0;
-	if constexpr ( FastOneSlab<CT>::value != 0 ) C.ldsbytes = C.gbytes;      // one buffer: layout, then weights, spill image, instance image
-	C.gmem = CT::gmem;
-	static_assert(CT::gmem == 0 || CT::gw != 0,"a layout in device memory is the gw layout");
-	return C;
-}
 
 struct FastBatch
 {
@@ -777,162 +101,6 @@ DEV void fast_load_tables(FastLds<CT> const & L, uint32_t const nrows, uint32_t 
 #define FW_THRES_FEAS 4294968ull        /* weight >= 1e-3 */
 #define FW_THRES_01   429496730ull      /* weight > 0.1 and weight >= 0.1 (no integer lies between) */
 #define FW_THRES_05   2147483648ull     /* weight >= 0.5 */
-
-#if defined(DACC_EMUL)
-// emulation only: per-window maxima of the variable-size structures (design aid, DACC_EMUL_STATS=<file>)
-struct FastStats { enum { N = 33 }; uint32_t v[N]; void clear() { for ( int i = 0; i < N; ++i ) v[i] = 0; } void mx(int i, uint32_t x) { if ( x > v[i] ) v[i] = x; } void add(int i, uint32_t x) { v[i] += x; } };
-static FastStats g_fstats;
-static inline void fstats_dump(int const tier)
-{
-	static FILE * sf = 0; static bool tried = false;
-	if ( !tried ) { tried = true; char const * fn = getenv("DACC_EMUL_STATS"); if ( fn ) sf = fopen(fn,"w"); }
-	if ( sf ) { fprintf(sf,"%d",tier); for ( int i = 0; i < FastStats::N; ++i ) fprintf(sf," %u",g_fstats.v[i]); fprintf(sf,"\n"); fflush(sf); }
-}
-static inline FILE * ftrav_file() { static FILE * f = 0; static bool tried = false; if ( !tried ) { tried = true; char const * fn = getenv("DACC_EMUL_TRAV"); if ( fn ) f = fopen(fn,"w"); } return f; }
-#define FSTAT_MX(i,x) g_fstats.mx(i,x)
-#define FSTAT_ADD(i,x) g_fstats.add(i,x)
-// design aid (DACC_EMUL_FEAS=<file>): per traversal the feasibility tasks' iteration counts, grouped as the 64 lanes would run them
-#include <vector>
-#include <algorithm>
-struct FeasIters { std::vector<uint32_t> it, ln; void clear() { it.clear(); ln.clear(); } };
-static FeasIters g_feasit;
-static inline void feasit_dump()
-{
-	static FILE * f = 0; static bool tried = false;
-	if ( !tried ) { tried = true; char const * fn = getenv("DACC_EMUL_FEAS"); if ( fn ) f = fopen(fn,"w"); }
-	if ( !f ) { g_feasit.clear(); return; }
-	std::vector<uint32_t> const & it = g_feasit.it; std::vector<uint32_t> const & ln = g_feasit.ln;
-	uint64_t tot = 0, lock = 0, locksorted = 0;
-	for ( size_t i = 0; i < it.size(); ++i ) tot += it[i];
-	for ( size_t i = 0; i < it.size(); i += 64 ) { uint32_t m = 0; for ( size_t q = i; q < it.size() && q < i+64; ++q ) m = std::max(m,it[q]); lock += m; }
-	std::vector< std::pair<uint32_t,uint32_t> > P; for ( size_t i = 0; i < it.size(); ++i ) P.push_back(std::make_pair(ln[i],it[i]));
-	std::stable_sort(P.begin(),P.end(),[](std::pair<uint32_t,uint32_t> const & a, std::pair<uint32_t,uint32_t> const & b){ return a.first > b.first; });
-	for ( size_t i = 0; i < P.size(); i += 64 ) { uint32_t m = 0; for ( size_t q = i; q < P.size() && q < i+64; ++q ) m = std::max(m,P[q].second); locksorted += m; }
-	uint64_t lockcls = 0;
-	{
-		std::vector< std::pair<uint32_t,uint32_t> > Q; for ( size_t i = 0; i < it.size(); ++i ) { uint32_t c = 0; while ( (2u<<c) <= ln[i] ) ++c; Q.push_back(std::make_pair(c,it[i])); }
-		std::stable_sort(Q.begin(),Q.end(),[](std::pair<uint32_t,uint32_t> const & a, std::pair<uint32_t,uint32_t> const & b){ return a.first > b.first; });
-		for ( size_t i = 0; i < Q.size(); i += 64 ) { uint32_t m = 0; for ( size_t q = i; q < Q.size() && q < i+64; ++q ) m = std::max(m,Q[q].second); lockcls += m; }
-	}
-	fprintf(f,"%zu %llu %llu %llu %llu\n",it.size(),(unsigned long long)tot,(unsigned long long)lock,(unsigned long long)locksorted,(unsigned long long)lockcls);
-	g_feasit.clear();
-}
-static inline bool feasit_on() { static int on = -1; if ( on < 0 ) on = getenv("DACC_EMUL_FEAS") ? 1 : 0; return on == 1; }      // single threaded design aid only
-#define FEAS_ITERS(t,len,n) { if ( feasit_on() && !feascount ) { g_feasit.it.push_back(n); g_feasit.ln.push_back(len); } }
-#define FEAS_DUMP() { if ( feasit_on() && !feascount ) feasit_dump(); }
-// test aid (DACC_EMUL_FEASCASES=<file>): per traversal of computeStretchFeasLanes one line of counters that say which situations of the unit
-// order, of the task rounds (as 64 lanes would run them, whatever the emulation's width) and of the node pipeline it went through
-// (tests/test_feas_pipeline.py asserts that its cases reach each of them).  One window at a time: the emulation of one context is sequential.
-struct FeasCases
-{
-	enum { NU = 0, NCU, NTASK, EMPTY_FIRST, EMPTY_MID, EMPTY_LAST, START_AT_ROUND, START_AT_ROUND_END, SPANS_ROUNDS, ROUNDS, LENMASK, MAXLEN, AT_CLAMP, PAST_CLAMP, MULTI, FAIL0, FAIL1, FAILLAST, NODES, N };
-	uint64_t v[N];
-	void clear() { for ( int i = 0; i < N; ++i ) v[i] = 0; }
-	// widths of the units in processing order, before they become offsets
-	template<typename PT> void units(PT W, uint32_t const nu)
-	{
-		clear();
-		v[NU] = nu;
-		uint32_t first = nu, last = 0;
-		for ( uint32_t q = 0; q < nu; ++q ) if ( W[q] ) { if ( first == nu ) first = q; last = q; }
-		uint64_t t = 0;
-		for ( uint32_t q = 0; q < nu; ++q )
-		{
-			uint32_t const w = W[q];
-			if ( !w ) { if ( q < first ) ++v[EMPTY_FIRST]; else if ( q > last ) ++v[EMPTY_LAST]; else ++v[EMPTY_MID]; continue; }
-			++v[NCU];
-			if ( t && t % 64 == 0 ) ++v[START_AT_ROUND];
-			if ( t % 64 == 63 ) ++v[START_AT_ROUND_END];
-			if ( t/64 != (t+w-1)/64 ) ++v[SPANS_ROUNDS];
-			t += w;
-		}
-		v[NTASK] = t; v[ROUNDS] = (t+63)/64;
-	}
-	void node(uint32_t const j, uint32_t const len, uint32_t const pp, uint32_t const nrows, uint32_t const f)
-	{
-		++v[NODES];
-		if ( j == 0 ) { v[LENMASK] |= 1ull << (len < 63 ? len : 63); if ( len > v[MAXLEN] ) v[MAXLEN] = len; }
-		if ( pp+1 == nrows ) ++v[AT_CLAMP];          // the table word fetched for the node behind this one is the clamp row's
-		if ( pp >= nrows ) ++v[PAST_CLAMP];         // a node's own position on or behind the clamp row
-		if ( f > 1 ) ++v[MULTI];
-	}
-	void fail(uint32_t const j, uint32_t const len) { if ( j == 0 ) ++v[FAIL0]; if ( j == 1 ) ++v[FAIL1]; if ( j+1 == len && len > 2 ) ++v[FAILLAST]; }
-	void dump(int const tier, uint32_t const nwF, uint32_t const nwR)
-	{
-		static FILE * f = 0; static bool tried = false;
-		if ( !tried ) { tried = true; char const * fn = getenv("DACC_EMUL_FEASCASES"); if ( fn ) f = fopen(fn,"w"); }
-		if ( !f ) return;
-		fprintf(f,"%d",tier); for ( int i = 0; i < N; ++i ) fprintf(f," %llu",(unsigned long long)v[i]); fprintf(f," %u %u\n",nwF,nwR); fflush(f);
-	}
-};
-static FeasCases g_feascases;
-#define FEAS_UNITS(W,nu) { if ( lane == 0 && !feascount ) g_feascases.units(W,nu); }
-#define FEAS_NODE(j,len,pp,nrows,f) { if ( !feascount ) g_feascases.node(j,len,pp,nrows,f); }
-#define FEAS_FAIL(j,len) { if ( !feascount ) g_feascases.fail(j,len); }
-#define FEAS_CASES_DUMP() { if ( lane == 0 && !feascount ) g_feascases.dump(int(CT::maxs),nwF,nwR); }
-// audit aid (DACC_EMUL_FEASNEED=<file>): which (stretch, direction, position) triples the filter of computeStretchFeasLanes left out of a
-// traversal, and how often the enumerations asked for one of them -- sfFind / csfFind at a left-out position, linkOk on a left-out reverse
-// unit.  The filter is exact iff that never happens (tests/test_feas_need.py asserts zero).  The file holds one line of running totals,
-// rewritten at every traversal and when the process ends: traversals, units with tasks and tasks without the filter, the same with it,
-// weight records written (forward, reverse), probes of left-out forward positions, of left-out reverse positions, links on left-out
-// reverse units; then the situations the traversals went through: first and last k-mer candidates strictly inside a stretch, middle
-// pieces, traversals with (lmax+1)/2 <= k, passes of the distance relaxation.  One window at a time, like the other aids.
-struct FeasNeedAudit
-{
-	enum { SCAP = 65536 };
-	uint64_t outF[SCAP][2], outR[SCAP][2];      // left-out start positions of stretch s, forward and reverse (128 bits each)
-	uint64_t ntrav, units0, tasks0, units1, tasks1, recF, recR, probeF, probeR, linkR, insF, insL, mids, hlek, passes;
-	FILE * f; bool tried;
-	bool on() { if ( !tried ) { tried = true; char const * fn = getenv("DACC_EMUL_FEASNEED"); if ( fn ) f = fopen(fn,"w"); } return f != 0; }
-	static void range(uint64_t * m, uint32_t const lo, uint32_t const hi) { for ( uint32_t p = lo; p < hi && p < 128u; ++p ) m[p>>6] |= 1ull << (p&63u); }
-	// unit (s,rev): start positions [lo0,hi0) without the filter, [lo1,hi1) with it
-	void unit(uint32_t const s, bool const rev, uint32_t const lo0, uint32_t const hi0, uint32_t const lo1, uint32_t const hi1)
-	{
-		if ( !on() || s >= SCAP ) return;
-		uint64_t * const m = rev ? outR[s] : outF[s];
-		m[0] = m[1] = 0; range(m,lo0,hi0);
-		uint64_t k[2] = {0,0}; range(k,lo1,hi1); m[0] &= ~k[0]; m[1] &= ~k[1];
-		if ( hi0 > lo0 ) { ++units0; tasks0 += hi0-lo0; }
-		if ( hi1 > lo1 ) { ++units1; tasks1 += hi1-lo1; }
-	}
-	static bool out(uint64_t const * m, uint32_t const p) { return p < 128u && ((m[p>>6] >> (p&63u)) & 1ull); }
-	void probe(uint32_t const s, bool const rev, uint32_t const p) { if ( f && s < SCAP && out(rev ? outR[s] : outF[s],p) ) ++(rev ? probeR : probeF); }
-	void link(uint32_t const a, uint32_t const b) { if ( f && a < SCAP && b < SCAP && ((outR[a][0]|outR[a][1]) || (outR[b][0]|outR[b][1])) ) ++linkR; }
-	void dump()
-	{
-		if ( !f ) return;
-		rewind(f);
-		fprintf(f,"%llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu\n",(unsigned long long)ntrav,(unsigned long long)units0,(unsigned long long)tasks0,(unsigned long long)units1,(unsigned long long)tasks1,
-			(unsigned long long)recF,(unsigned long long)recR,(unsigned long long)probeF,(unsigned long long)probeR,(unsigned long long)linkR,
-			(unsigned long long)insF,(unsigned long long)insL,(unsigned long long)mids,(unsigned long long)hlek,(unsigned long long)passes);
-		fflush(f);
-	}
-	~FeasNeedAudit() { dump(); }
-};
-static FeasNeedAudit g_feasneed;
-#define FEAS_NEED_UNIT(s,rev,lo0,hi0,lo1,hi1) { if ( !feascount ) g_feasneed.unit(s,rev,lo0,hi0,lo1,hi1); }
-#define FEAS_NEED_PROBE(s,rev,p) g_feasneed.probe(s,rev,p);
-#define FEAS_NEED_LINK(a,b) g_feasneed.link(a,b);
-#define FEAS_OVER() { if ( !feascount ) over(128); }
-#define FEAS_NEED_PASS() { if ( lane == 0 ) ++g_feasneed.passes; }
-#define FEAS_NEED_DUMP() { if ( lane == 0 && !feascount && g_feasneed.on() ) { FeasNeedAudit & A_ = g_feasneed; ++A_.ntrav; A_.recF += nwF; A_.recR += nwR; A_.mids += nmid; A_.hlek += (H <= static_cast<int64_t>(k)); \
-	for ( uint32_t c_ = 0; c_ < nF; ++c_ ) A_.insF += (L.fnode()[c_] != 0xFFFF && L.parF()[c_] != SNONE); for ( uint32_t c_ = 0; c_ < nL; ++c_ ) A_.insL += (L.lnode()[c_] != 0xFFFF && L.parL()[c_] != SNONE); A_.dump(); } }
-#else
-#define FEAS_ITERS(t,len,n)
-#define FEAS_DUMP()
-#define FEAS_UNITS(W,nu)
-#define FEAS_NODE(j,len,pp,nrows,f)
-#define FEAS_FAIL(j,len)
-#define FEAS_CASES_DUMP()
-#define FEAS_NEED_UNIT(s,rev,lo0,hi0,lo1,hi1)
-#define FEAS_NEED_PROBE(s,rev,p)
-#define FEAS_NEED_LINK(a,b)
-#define FEAS_NEED_DUMP()
-#define FEAS_NEED_PASS()
-#define FEAS_OVER() over(128);
-#define FSTAT_MX(i,x)
-#define FSTAT_ADD(i,x)
-#endif
 
 template<typename CT>
 struct FastEngine

@@ -2,7 +2,7 @@
  * The pipeline of LDS capacity tiers of the window stage, once and as data (host only, plain C++17: the planner, the launches
  * of capi.hip and the CPU emulation of the tests all read it from here).
  *
- * Every window runs through a chain of tiers (FastTier<N>, fast_window.hpp); which tiers, in which order, depends on the batch:
+ * Every window runs through a chain of tiers (FastTier<N>, fast_tiers.hpp); which tiers, in which order, depends on the batch:
  *
  *   shallow batches   slot 0: 0 -> 7 -> 1     slot 1: 6     slot 2: 10 -> 12 -> 3
  *   deep batches      slot 0: 4               slot 1: 2     slot 2: 11 -> 12 -> 3
@@ -128,7 +128,7 @@ enum : uint32_t { WORK_SLOT0 = 0, WORK_SLOT1 = 8, WORK_SLOT2 = 16, WORK_DENSE = 
 // column per stage); the rows added since stand behind it, TIER_NROWS counts all, and resolveTiers resolves them for a caller that says it holds them (`rows`).
 enum TierId { ID_T0, ID_T7, ID_SLOT0, ID_SLOT1, ID_DENSE, ID_DEEP, ID_SLOT2, ID_LAST, ID_VDEEP, ID_XDEEP, ID_LONG, TIER_NSTAGES, ID_FDEEP = TIER_NSTAGES, ID_WDEEP, TIER_NROWS };
 enum { TIER_NSLOTS = 3, TIER_NONE = 255, TIER_SHALLOW_FIRST = 1 };      // (the first slot's main tier of shallow batches: a batch whose windows mostly overflow its strings / instances is deep)
-enum : uint32_t { VDEEP_MINS = 250 };      // the very deep stage takes the windows with more strings than this (= FastTier<15>::mins = FastTier<13>::maxs, fast_window.hpp)
+enum : uint32_t { VDEEP_MINS = 250 };      // the very deep stage takes the windows with more strings than this (= FastTier<15>::mins = FastTier<13>::maxs; fast_tiers.hpp asserts this and the two below)
 enum : uint32_t { XDEEP_MINS = 1000 };     // the deepest stage is resolved for a batch with a window of more strings than this (= FastTier<15>::maxs); its tier takes what has more than VDEEP_MINS
 enum : uint32_t { FDEEP_MINS = 2000 };     // the full-depth stage is resolved for a batch with a window of more strings than this (= FastTier<16>::maxs); its tier takes what has more than VDEEP_MINS
 enum : uint64_t { TIER_GMEM_SLAB = 256ull << 20 };      // device memory the slabs of a device-memory tier's workgroups take together (tierGridGmem below)

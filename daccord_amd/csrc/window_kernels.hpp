@@ -1,6 +1,6 @@
 /*
  * The window kernels of libdaccord_hip.so, one translation unit each (k_fast_<tier>.hip for the tiers of DACC_KERNEL_TIERS,
- * tier_pipeline.hpp -- the table of the tiers is at the head of fast_window.hpp --, and k_generic.hip, which also holds tier 5): they are
+ * tier_pipeline.hpp -- the table of the tiers is fast_tiers.hpp --, and k_generic.hip, which also holds tier 5): they are
  * 150-260 KB of gfx950 code apiece and took 25 minutes to compile one after the other inside capi.hip; as separate objects they compile
  * side by side (daccord_amd/build.py).  This header holds what the units share: the work distribution, the kernel template of the LDS tiers (defined
  * here, instantiated explicitly in k_fast_<tier>.hip, declared `extern template` for capi.hip's launches) and the prototypes of the two

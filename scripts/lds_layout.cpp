@@ -4,7 +4,7 @@
 #include <vector>
 #include <algorithm>
 #include <cstdio>
-#include "../daccord_amd/csrc/fast_window.hpp"
+#include "../daccord_amd/csrc/fast_layout.hpp"
 using namespace dacc;
 template<int T> void dump()
 {

@@ -24,8 +24,9 @@ def _pow2(v):
 
 
 def test_probe_sorts_what_the_product_instantiates(P):
-    """the (CAP, R32) pairs of wv_sort_keys, read off the FastTier table (fast_window.hpp: wv_sort_keys<keycap>, <precap[,R32]>, <fcpow2(scap)>)"""
-    src = open(os.path.join(ROOT, "daccord_amd", "csrc", "fast_window.hpp")).read()
+    """the (CAP, R32) pairs of wv_sort_keys, read off the FastTier table (fast_tiers.hpp) and the engine's calls (fast_window.hpp:
+    wv_sort_keys<keycap>, <precap[,R32]>, <fcpow2(scap)>)"""
+    src = "".join(open(os.path.join(ROOT, "daccord_amd", "csrc", f)).read() for f in ("fast_tiers.hpp", "fast_window.hpp"))
     defs = dict(re.findall(r"^#define\s+(\w+)\s+(\d+)\s*$", src, re.M))
     tiers = re.findall(r"template<> struct FastTier<(\d+)> \{[^\n]*?enum : uint32_t \{([^}]*)\}", src)
     assert len(tiers) >= 15
