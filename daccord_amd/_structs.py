@@ -63,10 +63,17 @@ class DaccTimingFull(C.Structure):
 
 
 class DaccTimingWide(C.Structure):
-    """dacc_timing as it is since the wide deep stage: DaccTimingFull (208 bytes, unchanged) and the 16 bytes appended behind pad3_"""
+    """dacc_timing as it was with the wide deep stage: DaccTimingFull (208 bytes, unchanged) and the 16 bytes appended behind pad3_"""
     _fields_ = DaccTimingFull._fields_ + [
         # the wide deep stage (k_window_fast<19>: windows of 251 ... 1000 strings of a wide batch, behind the last stage and in front of k_window)
         ("wdeep_ms", C.c_float), ("wdeep_windows", C.c_uint32), ("wdeep_out", C.c_uint32), ("pad4_", C.c_uint32)]
+
+
+class DaccTimingW128(C.Structure):
+    """dacc_timing as it is since the stage of w = 128: DaccTimingWide (224 bytes, unchanged) and the 16 bytes appended behind pad4_"""
+    _fields_ = DaccTimingWide._fields_ + [
+        # the stage of a batch with w = 128 (k_window_fast<20>: every window of the batch, in front of k_window)
+        ("w128_ms", C.c_float), ("w128_windows", C.c_uint32), ("w128_out", C.c_uint32), ("pad5_", C.c_uint32)]
 
 
 TIMING_SIZE_V1 = 128

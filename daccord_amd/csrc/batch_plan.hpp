@@ -67,7 +67,7 @@ struct BatchPlan
 	uint32_t maxstrings(dacc_params const & par) const { uint64_t const nb = par.maxalign > 0 ? static_cast<uint64_t>(par.maxalign-1) : 0; return 1u + static_cast<uint32_t>(std::min<uint64_t>(maxdepth,nb)); }
 	uint64_t ndeepwin;        // windows with more strings / k-mer instances than the first tier of shallow batches holds
 	bool deep;                // most windows are deep: the chain of deep batches (many strings, small graph in the first slot)
-	bool wide;                // window size 64 ... 127: the chain of wide batches (round 6)
+	bool wide;                // window size 64 ... 128: the chain of wide batches (round 6); w = 128: its one stage (tier 20)
 
 	// Per pile results of the parallel pass of plan(): everything that does not depend on the piles in front of it
 	struct PileTmp
@@ -325,8 +325,9 @@ struct BatchPlan
 		// A batch whose windows are mostly too deep for tier 1 (coverage of 40x and more) starts in the deep tier instead
 		deep = 2*ndeepwin > nwindows;
 		// (round 6) wide windows: tier 8 (second slot, no hand-over list in front of it = all windows), tier 9, then the generic engine
-		wide = par.w > 63 && par.w <= 127;
-		for ( uint32_t i = 0; i < TIER_NROWS; ++i ) stageCaps(i) = tierCaps(stageTier(TIER_CHAIN[i],deep,wide),tab_nrows,tab_nsup);
+		// (w = 128: a wide batch whose chain is one stage, tier 20 -- resolveTiers; the rows for that window size alone take their capacities from it)
+		wide = par.w > 63 && par.w <= W128;
+		for ( uint32_t i = 0; i < TIER_NROWS; ++i ) stageCaps(i) = tierCaps(stageTier(TIER_CHAIN[i],deep,wide,par.w),tab_nrows,tab_nsup);
 		return DACC_OK;
 	}
 };

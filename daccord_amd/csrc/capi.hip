@@ -493,7 +493,9 @@ static StageCounters const STAGE_COUNTERS[] = {
 	{ ID_VDEEP, &dacc_timing::vdeep_ms, &dacc_timing::vdeep_windows, &dacc_timing::vdeep_out, true, VDEEP_MINS, WORK_VDEEP_COUNT },
 	{ ID_XDEEP, &dacc_timing::xdeep_ms, &dacc_timing::xdeep_windows, &dacc_timing::xdeep_out, true, VDEEP_MINS, WORK_XDEEP_COUNT },
 	{ ID_FDEEP, &dacc_timing::fdeep_ms, &dacc_timing::fdeep_windows, &dacc_timing::fdeep_out, true, VDEEP_MINS, WORK_FDEEP_COUNT },
-	{ ID_WDEEP, &dacc_timing::wdeep_ms, &dacc_timing::wdeep_windows, &dacc_timing::wdeep_out, true, VDEEP_MINS, WORK_WDEEP_COUNT } };
+	{ ID_WDEEP, &dacc_timing::wdeep_ms, &dacc_timing::wdeep_windows, &dacc_timing::wdeep_out, true, VDEEP_MINS, WORK_WDEEP_COUNT },
+	// (the stage of a w = 128 batch reads every window of the batch -- no list -- and its time runs from the end of the trace kernels: fetchStageCounters)
+	{ ID_W128, &dacc_timing::w128_ms, &dacc_timing::w128_windows, &dacc_timing::w128_out, false, 0, 0 } };
 
 // ---- the device pass (runDevice): one function per phase, in the order they run; they share the context and the state of the pass
 // DACC_DEBUG_SYNC=1: wait for every kernel of the generic-only path and say so on stderr (a device fault then names its kernel)
@@ -502,6 +504,9 @@ static void mark(dacc_ctx * c, char const * what) { if ( dbgSync() ) { hipError_
 // a stage's work counter (DACC_SCHED bit 0: the tiers pull their windows from a counter)
 static uint32_t * workCounter(dacc_ctx * c, uint32_t const off) { return (c->sched&1) ? c->d_work.p+off : static_cast<uint32_t *>(0); }
 static dacc_ctx::Stage * ranOf(dacc_ctx * c, TierId const id) { return c->st[id].ran ? &c->st[id] : static_cast<dacc_ctx::Stage *>(0); }
+// a batch of w = 128 in which no slot runs: the generic engine's launch geometry and events, as before the stage of w = 128 existed (its model table is one the
+// wide tiers' pipeline admits since then -- TP.usefast --, but no slot, no pre-scan and no second stream run), and that stage (ID_W128) in front of k_window where it is resolved
+static bool aloneBatch(dacc_ctx const * c) { return c->TP.usefast && !c->TP.anytier() && c->par.w == W128; }
 
 struct Pass
 {
@@ -848,7 +853,7 @@ static int scratchRetry(dacc_ctx * c, Pass & P)
 		uint32_t const g = boundByArena(c->retry_grid < 64 ? c->retry_grid : 64,BP.caps.bytes,4);
 		c->retry_grid = g; c->win_grid = g; if ( c->early_grid > g ) c->early_grid = g;     // later launches of this batch use the grown arenas
 		HIPCHK(c->d_arena.ensure(static_cast<size_t>(g)*BP.caps.bytes));
-		if ( c->TP.usefast ) HIPCHK(c->d_arena2.ensure(static_cast<size_t>(c->early_grid)*BP.caps.bytes));
+		if ( c->TP.usefast && !aloneBatch(c) ) HIPCHK(c->d_arena2.ensure(static_cast<size_t>(c->early_grid)*BP.caps.bytes));
 		HIPCHK(c->d_gearly.ensure(BP.nwindows+2)); HIPCHK(c->d_pregenlist.ensure(BP.nwindows+2)); HIPCHK(c->d_pregen.ensure((BP.nwindows+31)/32+2)); HIPCHK(c->d_pregen2.ensure((BP.nwindows+31)/32+2));
 		HIPCHK(hipMemsetAsync(c->d_err.p,0,4*sizeof(uint32_t),s));
 		HIPCHK(hipMemsetAsync(c->d_gearly.p,0,sizeof(uint32_t),s));
@@ -873,7 +878,8 @@ static int fetchStageCounters(dacc_ctx * c)
 	{
 		dacc_ctx::Stage const & S = c->st[K.id];
 		c->timing.*K.windows = 0; c->timing.*K.out = 0; if ( K.ms ) c->timing.*K.ms = 0;
-		if ( !S.ran || !S.in ) continue;
+		bool const alone = TIER_CHAIN[K.id].role == ROLE_ALONE;      // the stage of a w = 128 batch: all windows, no stage in front of it
+		if ( !S.ran || (!S.in && !alone) ) continue;
 		uint32_t cnt[2] = {0,0};      // what it read, what it handed on
 		if ( K.deeper )
 		{
@@ -882,12 +888,17 @@ static int fetchStageCounters(dacc_ctx * c)
 			HIPCHK(hipMemcpyAsync(cnt,c->d_work.p+K.countwords,sizeof(cnt),hipMemcpyDeviceToHost,s));
 			HIPCHK(hipStreamSynchronize(s));
 		}
-		else { HIPCHK(hipMemcpy(&cnt[0],S.in,sizeof(uint32_t),hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&cnt[1],S.handon.p,sizeof(uint32_t),hipMemcpyDeviceToHost)); }
+		else
+		{
+			if ( S.in ) HIPCHK(hipMemcpy(&cnt[0],S.in,sizeof(uint32_t),hipMemcpyDeviceToHost)); else cnt[0] = static_cast<uint32_t>(BP.nwindows);
+			HIPCHK(hipMemcpy(&cnt[1],S.handon.p,sizeof(uint32_t),hipMemcpyDeviceToHost));
+		}
 		c->timing.*K.out = cnt[1]; c->timing.*K.windows = cnt[0] > cnt[1] ? cnt[0] - cnt[1] : 0u;
-		if ( K.ms ) { float sms = 0; hipEventElapsedTime(&sms,from,S.done); c->timing.*K.ms = sms; from = S.done; }
+		if ( K.ms && alone ) { float sms = 0; hipEventElapsedTime(&sms,c->ev[1],S.done); c->timing.*K.ms = sms; }
+		else if ( K.ms ) { float sms = 0; hipEventElapsedTime(&sms,from,S.done); c->timing.*K.ms = sms; from = S.done; }
 	}
 	// the long string stage (wide batches, second stream): what it read is what the second stream read (long_windows), what it handed on is what k_window_long ran
-	c->timing.longstr_ms = 0; c->timing.longstr_windows = 0; c->timing.longstr_out = 0; c->timing.pad2_ = 0; c->timing.pad3_ = 0; c->timing.pad4_ = 0;
+	c->timing.longstr_ms = 0; c->timing.longstr_windows = 0; c->timing.longstr_out = 0; c->timing.pad2_ = 0; c->timing.pad3_ = 0; c->timing.pad4_ = 0; c->timing.pad5_ = 0;
 	if ( !(TP.usefast && BP.nwindows && TP.anytier()) ) c->longran[0] = c->longran[1] = false;
 	for ( int i = 0; i < 2; ++i )
 		if ( c->longran[i] )
@@ -946,7 +957,7 @@ static void eventTimes(dacc_ctx * c)
 	hipEventElapsedTime(&ms,c->ev[0],c->ev[1]); c->timing.trace_ms = ms;
 	hipEventElapsedTime(&ms,c->ev[1],c->ev[2]); c->timing.window_ms = ms;
 	for ( int i = 0; i < 3; ++i ) c->timing.tier_ms[i] = 0;
-	if ( TP.usefast && BP.nwindows ) for ( int i = 0; i < 3; ++i ) { hipEventElapsedTime(&ms,i ? c->evslot[i-1] : c->ev[1],c->evslot[i]); c->timing.tier_ms[i] = ms; }
+	if ( TP.usefast && !aloneBatch(c) && BP.nwindows ) for ( int i = 0; i < 3; ++i ) { hipEventElapsedTime(&ms,i ? c->evslot[i-1] : c->ev[1],c->evslot[i]); c->timing.tier_ms[i] = ms; }
 	c->timing.tier0_ms = 0; c->timing.tier7_ms = 0; c->timing.pad_ = 0; c->timing.tier10_ms = 0; c->timing.tier10_ran = fD ? 1u : 0u;
 	if ( f0 ) { hipEventElapsedTime(&ms,c->ev[1],f0->done); c->timing.tier0_ms = ms; }
 	if ( f7 ) { hipEventElapsedTime(&ms,f0->done,f7->done); c->timing.tier7_ms = ms; }
@@ -989,8 +1000,21 @@ static int runDevice(dacc_ctx * c)
 		else
 		{
 			HIPCHK(hipMemsetAsync(c->d_work.p,0,WORK_WORDS*sizeof(uint32_t),s));
-			hipLaunchKernelGGL(k_window,dim3(c->win_grid),dim3(64),0,s,P.WB,c->d_err.p,static_cast<uint32_t const *>(0),(c->sched&2) ? c->d_work.p+WORK_GENERIC : static_cast<uint32_t *>(0));
-			mark(c,"k_window (all windows)");
+			uint32_t const * glist = 0;      // what the generic engine reads (0: all windows)
+			if ( TP.ok[ID_W128] )
+			{
+				// a batch of w = 128: every window runs in the stage's tier first (layout in its own slab, no LDS, no pre-scan map and no early list: a string
+				// of more than 255 bases is handed on like a table that overflowed), the generic engine runs what it hands on
+				dacc_ctx::Stage & S = c->st[ID_W128];
+				FastBatch FZ = stageBatch(c,P.WB,ID_W128,false); handsOn(FZ,S.handon.p,S.slab.p);
+				HIPCHK(hipMemsetAsync(S.handon.p,0,sizeof(uint32_t),s));
+				hipLaunchKernelGGL(fastKernel(TP.tier[ID_W128]),dim3(S.grid),dim3(64),0,s,FZ,static_cast<uint32_t const *>(0),workCounter(c,TIER_CHAIN[ID_W128].work));
+				mark(c,"k_window_fast (w = 128 stage)");
+				HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = 0;
+				glist = S.handon.p;
+			}
+			hipLaunchKernelGGL(k_window,dim3(c->win_grid),dim3(64),0,s,P.WB,c->d_err.p,glist,(c->sched&2) ? c->d_work.p+WORK_GENERIC : static_cast<uint32_t *>(0));
+			mark(c,glist ? "k_window (what the w = 128 stage handed on)" : "k_window (all windows)");
 		}
 	}
 	HIPCHK(hipEventRecord(c->ev[2],s));
@@ -1082,7 +1106,9 @@ static int dacc_submit_piles_body(dacc_ctx * c, dacc_pile const * piles, uint64_
 	// which LDS tiers this batch runs (tier_pipeline.hpp); none: the generic engine alone
 	c->TP = resolveTiers(c->sw,!c->sw.nofast && fits32,BP.deep,BP.wide,c->H.nrows,c->H.nsup,c->par.w,[&](uint32_t const id) -> FastCaps & { return BP.stageCaps(id); },BP.maxstrings(c->par),TIER_NROWS);
 	TierPipeline const & TP = c->TP;
-	if ( TP.usefast )
+	// (a batch of w = 128 in which no slot runs: the generic engine's geometry, as before its stage existed, and the stage's list and slab beside it)
+	bool const alone = aloneBatch(c);
+	if ( TP.usefast && !alone )
 	{
 		for ( int t = 0; t < TIER_NSLOTS; ++t ) HIPCHK(c->d_retry[t].ensure(BP.nwindows+2));
 		// the stages of the chain: launch geometry, hand-on lists of the front tiers (and the pre-pass's list of small windows), global slab
@@ -1145,6 +1171,21 @@ static int dacc_submit_piles_body(dacc_ctx * c, dacc_pile const * piles, uint64_
 		c->retry_grid = c->win_grid; c->early_grid = 0;
 		HIPCHK(c->d_work.ensure(WORK_WORDS));
 		HIPCHK(c->d_arena.ensure(static_cast<size_t>(c->win_grid)*BP.caps.bytes));
+		if ( alone && TP.ok[ID_W128] )
+		{
+			// the stage of a w = 128 batch: its hand-on list (what k_window reads) and its slab, grid x gbytes <= TIER_GMEM_SLAB.  Optional like a trailing stage's:
+			// a device that cannot spare them, and a retry after an allocation failure (dacc_drop_hand), run the batch in the generic engine alone
+			dacc_ctx::Stage & S = c->st[ID_W128]; FastCaps const & F = BP.stageCaps(ID_W128);
+			S.grid = tierGridGmem(F.gbytes,BP.nwindows,TIER_CHAIN[ID_W128].slab);
+			if ( c->noslab ) { S.slab.release(); c->TP.ok[ID_W128] = false; }
+			else
+			{
+				hipError_t e = S.handon.ensure(BP.nwindows+2);
+				if ( e == hipSuccess ) e = S.slab.ensure(static_cast<size_t>(S.grid)*F.gbytes + 256);
+				if ( e == hipErrorOutOfMemory ) { (void)hipGetLastError(); S.slab.release(); c->TP.ok[ID_W128] = false; }
+				else HIPCHK(e);
+			}
+		}
 	}
 	HIPCHK(c->d_wrec.ensure((BP.nwindows+1)*static_cast<size_t>(DACC_WREC_OF(c->par.w)))); HIPCHK(c->d_wout.ensure(BP.nwindows+1));
 	HIPCHK(c->d_has.ensure(BP.npos+1)); HIPCHK(c->d_oc.ensure(BP.npos+1)); HIPCHK(c->d_ld0.ensure(BP.npos+1)); HIPCHK(c->d_ocs.ensure(BP.npos+1));
@@ -1179,7 +1220,7 @@ void dacc_release(dacc_ctx * c) { if ( c ) { c->frags.clear(); c->bases.clear();
 // dacc_last_timing: the record as it was when the call got its signature (everything in front of deep_ms), so that a caller compiled against
 // that header is not overrun; dacc_last_timing2 copies as much of today's record as the caller says it has room for
 static_assert(offsetof(dacc_timing,deep_ms) == DACC_TIMING_SIZE_V1,"dacc_last_timing fills the record in front of deep_ms");
-static_assert(offsetof(dacc_timing,vdeep_ms) == 160 && offsetof(dacc_timing,longstr_ms) == DACC_TIMING_SIZE_V2 && DACC_TIMING_SIZE_V2 == 176 && offsetof(dacc_timing,fdeep_ms) == DACC_TIMING_SIZE_V3 && DACC_TIMING_SIZE_V3 == 192 && offsetof(dacc_timing,wdeep_ms) == DACC_TIMING_SIZE_V4 && DACC_TIMING_SIZE_V4 == 208 && offsetof(dacc_timing,wdeep_windows) == 212 && offsetof(dacc_timing,wdeep_out) == 216 && sizeof(dacc_timing) == 224,"the very deep stage's fields are appended behind last_*, the long string stage's 16 bytes behind emit_ms, the full-depth stage's 16 bytes behind those, the wide deep stage's 16 bytes behind those");
+static_assert(offsetof(dacc_timing,vdeep_ms) == 160 && offsetof(dacc_timing,longstr_ms) == DACC_TIMING_SIZE_V2 && DACC_TIMING_SIZE_V2 == 176 && offsetof(dacc_timing,fdeep_ms) == DACC_TIMING_SIZE_V3 && DACC_TIMING_SIZE_V3 == 192 && offsetof(dacc_timing,wdeep_ms) == DACC_TIMING_SIZE_V4 && DACC_TIMING_SIZE_V4 == 208 && offsetof(dacc_timing,wdeep_windows) == 212 && offsetof(dacc_timing,wdeep_out) == 216 && offsetof(dacc_timing,w128_ms) == DACC_TIMING_SIZE_V5 && DACC_TIMING_SIZE_V5 == 224 && offsetof(dacc_timing,w128_windows) == 228 && offsetof(dacc_timing,w128_out) == 232 && sizeof(dacc_timing) == 240,"the 16 bytes of the stage of w = 128 are appended behind the wide deep stage's; the very deep stage's fields are appended behind last_*, the long string stage's 16 bytes behind emit_ms, the full-depth stage's 16 bytes behind those, the wide deep stage's 16 bytes behind those");
 static_assert(offsetof(dacc_timing,xdeep_ms) == 140 && offsetof(dacc_timing,xdeep_windows) == 156 && offsetof(dacc_timing,xdeep_out) == 124,"the deepest stage's fields take the pad words: the record keeps its size");
 static_assert(offsetof(dacc_timing,emit_ms) == 172,"emit_ms is the last word of the first 176 bytes, where the very deep stage's pad word was");
 int dacc_last_timing(dacc_ctx * c, dacc_timing * t)
@@ -1194,7 +1235,8 @@ int dacc_last_timing2(dacc_ctx * c, dacc_timing * t, size_t size)
 	// the long string stage's 16 bytes behind emit_ms go only to a caller that has room for all of them: a caller built with the 176 byte record that
 	// passes a larger size (its record inside a larger buffer) gets the 176 bytes it knows, as before the record grew; the full-depth stage's 16 bytes behind
 	// those follow the same rule: a size in [192, 208) copies 192 bytes; so do the wide deep stage's 16 bytes behind pad3_: a size in [208, 224) copies 208 bytes
-	size_t const n = size >= sizeof(dacc_timing) ? sizeof(dacc_timing) : (size >= DACC_TIMING_SIZE_V4 ? static_cast<size_t>(DACC_TIMING_SIZE_V4) : (size >= DACC_TIMING_SIZE_V3 ? static_cast<size_t>(DACC_TIMING_SIZE_V3) : (size < DACC_TIMING_SIZE_V2 ? size : static_cast<size_t>(DACC_TIMING_SIZE_V2))));
+	// and the 16 bytes of the stage of w = 128 behind pad4_: a size in [224, 240) copies 224 bytes
+	size_t const n = size >= sizeof(dacc_timing) ? sizeof(dacc_timing) : (size >= DACC_TIMING_SIZE_V5 ? static_cast<size_t>(DACC_TIMING_SIZE_V5) : size >= DACC_TIMING_SIZE_V4 ? static_cast<size_t>(DACC_TIMING_SIZE_V4) : (size >= DACC_TIMING_SIZE_V3 ? static_cast<size_t>(DACC_TIMING_SIZE_V3) : (size < DACC_TIMING_SIZE_V2 ? size : static_cast<size_t>(DACC_TIMING_SIZE_V2))));
 	std::memcpy(static_cast<void *>(t),&c->timing,n);
 	return DACC_OK;
 }
@@ -1316,13 +1358,13 @@ static bool dacc_drop_hand(dacc_ctx * c)
 	if ( !c || !c->oom ) return false;
 	c->oom = false;
 	bool slabs = false;
-	for ( uint32_t i = 0; i < TIER_NROWS; ++i ) slabs = slabs || (TIER_CHAIN[i].slab && c->st[i].slab.p);
+	for ( uint32_t i = 0; i < TIER_NROWS; ++i ) slabs = slabs || ((TIER_CHAIN[i].slab || TIER_CHAIN[i].role == ROLE_ALONE) && c->st[i].slab.p);
 	if ( !c->d_hand.p && !slabs ) return false;
 	(void)hipGetLastError(); hipSetDevice(c->device); (void)hipDeviceSynchronize(); (void)hipGetLastError();
 	if ( c->d_hand.p ) { c->d_hand.release(); c->handcap = 0; c->handwant = 0; c->nohand = true; }
 	if ( slabs )
 	{
-		for ( uint32_t i = 0; i < TIER_NROWS; ++i ) if ( TIER_CHAIN[i].slab ) { c->st[i].slab.release(); c->TP.ok[i] = false; }
+		for ( uint32_t i = 0; i < TIER_NROWS; ++i ) if ( TIER_CHAIN[i].slab || TIER_CHAIN[i].role == ROLE_ALONE ) { c->st[i].slab.release(); c->TP.ok[i] = false; }
 		c->noslab = true;
 	}
 	return true;

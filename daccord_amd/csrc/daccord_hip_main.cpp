@@ -549,7 +549,7 @@ int main(int argc, char ** argv)
 	});
 	std::string fatal; bool stopall = false;           // both under mu
 	double gpu_s = 0; uint64_t nbatches = 0;            // under mu
-	struct { uint64_t nwindows, tier_out[3], deep_windows, deep_out, last_windows, last_out, vdeep_windows, vdeep_out, xdeep_windows, xdeep_out, fdeep_windows, fdeep_out, wdeep_windows, wdeep_out, longstr_windows, longstr_out; double window_ms, tier_ms[3], deep_ms, last_ms, vdeep_ms, xdeep_ms, fdeep_ms, wdeep_ms, emit_ms, longstr_ms; } tstat = {};      // under mu: dacc_timing summed over the batches (-V)
+	struct { uint64_t nwindows, tier_out[3], deep_windows, deep_out, last_windows, last_out, vdeep_windows, vdeep_out, xdeep_windows, xdeep_out, fdeep_windows, fdeep_out, wdeep_windows, wdeep_out, w128_windows, w128_out, longstr_windows, longstr_out; double window_ms, tier_ms[3], deep_ms, last_ms, vdeep_ms, xdeep_ms, fdeep_ms, wdeep_ms, w128_ms, emit_ms, longstr_ms; } tstat = {};      // under mu: dacc_timing summed over the batches (-V)
 	// every batch (also an empty one, the end marker and a failed one) hands the writer an Out with its sequence number: the
 	// writer needs an unbroken sequence.  An output slot is always available within bounded time: at most one Out per worker is
 	// in flight besides those queued for the writer, and there are 2*nwork+1 slots.
@@ -599,6 +599,7 @@ int main(int argc, char ** argv)
 							tstat.xdeep_ms += tm.xdeep_ms; tstat.xdeep_windows += tm.xdeep_windows; tstat.xdeep_out += tm.xdeep_out;
 							tstat.fdeep_ms += tm.fdeep_ms; tstat.fdeep_windows += tm.fdeep_windows; tstat.fdeep_out += tm.fdeep_out;
 							tstat.wdeep_ms += tm.wdeep_ms; tstat.wdeep_windows += tm.wdeep_windows; tstat.wdeep_out += tm.wdeep_out;
+							tstat.w128_ms += tm.w128_ms; tstat.w128_windows += tm.w128_windows; tstat.w128_out += tm.w128_out;
 							tstat.longstr_ms += tm.longstr_ms; tstat.longstr_windows += tm.longstr_windows; tstat.longstr_out += tm.longstr_out;
 							for ( int i = 0; i < 3; ++i ) { tstat.tier_out[i] += tm.tier_out[i]; tstat.tier_ms[i] += tm.tier_ms[i]; }
 						}
@@ -640,6 +641,7 @@ int main(int argc, char ** argv)
 			"deepest stage (1001 ... 2000 strings) %.1f ms, %llu windows finished, %llu handed on; "
 			"full-depth stage (2001 ... 5001 strings) %.1f ms, %llu windows finished, %llu handed on to the generic engine; "
 			"wide deep stage (wide batches, 251 ... 1000 strings) wdeep_ms %.1f ms, wdeep_windows %llu finished, wdeep_out %llu handed on to the generic engine; "
+			"stage of -w 128 (every window of such a batch) w128_ms %.1f ms, w128_windows %llu finished, w128_out %llu handed on to the generic engine; "
 			"long string stage (wide batches, strings of 129 ... 255 bases, second stream) %.1f ms, %llu windows finished, %llu handed on to the generic engine; "
 			"consensus -> A alignment of the tiers' windows (k_emit, in front of the vote) %.1f ms\n",
 			static_cast<unsigned long long>(tstat.nwindows),tstat.window_ms,tstat.tier_ms[0],tstat.tier_ms[1],tstat.tier_ms[2],
@@ -650,6 +652,7 @@ int main(int argc, char ** argv)
 			tstat.xdeep_ms,static_cast<unsigned long long>(tstat.xdeep_windows),static_cast<unsigned long long>(tstat.xdeep_out),
 			tstat.fdeep_ms,static_cast<unsigned long long>(tstat.fdeep_windows),static_cast<unsigned long long>(tstat.fdeep_out),
 			tstat.wdeep_ms,static_cast<unsigned long long>(tstat.wdeep_windows),static_cast<unsigned long long>(tstat.wdeep_out),
+			tstat.w128_ms,static_cast<unsigned long long>(tstat.w128_windows),static_cast<unsigned long long>(tstat.w128_out),
 			tstat.longstr_ms,static_cast<unsigned long long>(tstat.longstr_windows),static_cast<unsigned long long>(tstat.longstr_out),tstat.emit_ms);
 	}
 	for ( int g = 0; g < nwork; ++g ) dacc_destroy(ctxs[g]);

@@ -115,24 +115,24 @@ static FeasCases g_feascases;
 struct FeasNeedAudit
 {
 	enum { SCAP = 65536 };
-	uint64_t outF[SCAP][2], outR[SCAP][2];      // left-out start positions of stretch s, forward and reverse (128 bits each)
+	uint64_t outF[SCAP][3], outR[SCAP][3];      // left-out start positions of stretch s, forward and reverse (192 bits each: the table of w = 128 has row 128)
 	uint64_t ntrav, units0, tasks0, units1, tasks1, recF, recR, probeF, probeR, linkR, insF, insL, mids, hlek, passes;
 	FILE * f; bool tried;
 	bool on() { if ( !tried ) { tried = true; char const * fn = getenv("DACC_EMUL_FEASNEED"); if ( fn ) f = fopen(fn,"w"); } return f != 0; }
-	static void range(uint64_t * m, uint32_t const lo, uint32_t const hi) { for ( uint32_t p = lo; p < hi && p < 128u; ++p ) m[p>>6] |= 1ull << (p&63u); }
+	static void range(uint64_t * m, uint32_t const lo, uint32_t const hi) { for ( uint32_t p = lo; p < hi && p < 192u; ++p ) m[p>>6] |= 1ull << (p&63u); }
 	// unit (s,rev): start positions [lo0,hi0) without the filter, [lo1,hi1) with it
 	void unit(uint32_t const s, bool const rev, uint32_t const lo0, uint32_t const hi0, uint32_t const lo1, uint32_t const hi1)
 	{
 		if ( !on() || s >= SCAP ) return;
 		uint64_t * const m = rev ? outR[s] : outF[s];
-		m[0] = m[1] = 0; range(m,lo0,hi0);
-		uint64_t k[2] = {0,0}; range(k,lo1,hi1); m[0] &= ~k[0]; m[1] &= ~k[1];
+		m[0] = m[1] = m[2] = 0; range(m,lo0,hi0);
+		uint64_t k[3] = {0,0,0}; range(k,lo1,hi1); m[0] &= ~k[0]; m[1] &= ~k[1]; m[2] &= ~k[2];
 		if ( hi0 > lo0 ) { ++units0; tasks0 += hi0-lo0; }
 		if ( hi1 > lo1 ) { ++units1; tasks1 += hi1-lo1; }
 	}
-	static bool out(uint64_t const * m, uint32_t const p) { return p < 128u && ((m[p>>6] >> (p&63u)) & 1ull); }
+	static bool out(uint64_t const * m, uint32_t const p) { return p < 192u && ((m[p>>6] >> (p&63u)) & 1ull); }
 	void probe(uint32_t const s, bool const rev, uint32_t const p) { if ( f && s < SCAP && out(rev ? outR[s] : outF[s],p) ) ++(rev ? probeR : probeF); }
-	void link(uint32_t const a, uint32_t const b) { if ( f && a < SCAP && b < SCAP && ((outR[a][0]|outR[a][1]) || (outR[b][0]|outR[b][1])) ) ++linkR; }
+	void link(uint32_t const a, uint32_t const b) { if ( f && a < SCAP && b < SCAP && ((outR[a][0]|outR[a][1]|outR[a][2]) || (outR[b][0]|outR[b][1]|outR[b][2])) ) ++linkR; }
 	void dump()
 	{
 		if ( !f ) return;

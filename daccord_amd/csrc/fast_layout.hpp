@@ -43,11 +43,12 @@ struct FastLds<CT,false>
 	static_assert(CT::maxs <= 256,"the legacy layout has 8 bit node frequencies and string ids");
 	static_assert((CT::precap & (CT::precap-1)) == 0,"precap must be a power of two: the bitonic sorts pad to one");
 	static_assert(sizeof(typename CT::id_t) > 1 || (CT::fcap <= 256 && CT::rccap <= 256),"pool slots are recorded as id_t (pout)");
-	static_assert(CT::blcap <= 128 && (CT::blcap & 7) == 0,"base length buckets: two 64 bit occupancy words, cleared 8 at a time");
+	static_assert(CT::blcap <= (FastRows3<CT>::value ? 192u : 128u) && (CT::blcap & 7) == 0,"base length buckets: two 64 bit occupancy words (three in the tier of w = 128, FastRows3), cleared 8 at a time");
 	// ---- live during the whole window ----
 	static_assert(CT::lstr == 64 || CT::lstr == 128 || CT::lstr == 256,"string stride: one, two or four 64 bit words per pattern mask");
 	static constexpr uint32_t pw = CT::lstr/64;      // words per pattern mask
 	static constexpr uint32_t maxlen = CT::lstr < 256u ? static_cast<uint32_t>(CT::lstr) : 255u;      // longest string the layout holds
+	static constexpr uint32_t maskrows = 64u, supcap = static_cast<uint32_t>(FSUPCAP);      // one word per position mask, the narrow table copy
 	typedef uint8_t sid_t;      // stretch ids are 8 bits in the legacy layout
 	static_assert(sizeof(typename CT::sid_t) == 1,"16 bit stretch ids need the gw layout");
 	FLD(str,uint8_t,CT::maxs*CT::lstr,0)
@@ -247,11 +248,15 @@ struct FastLds<CT,true>
 	// (precap need not be a power of two in this layout: the sorts touch only the n keys there are; the padding of the overlap
 	// sort at the start of a window is checked against it)
 	static_assert(sizeof(typename CT::id_t) > 1 || (CT::fcap <= 256 && CT::rccap <= 256),"pool slots are recorded as id_t (pout)");
-	static_assert(CT::blcap <= 128 && (CT::blcap & 7) == 0,"base length buckets: two 64 bit occupancy words, cleared 8 at a time");
+	static_assert(CT::blcap <= (FastRows3<CT>::value ? 192u : 128u) && (CT::blcap & 7) == 0,"base length buckets: two 64 bit occupancy words (three in the tier of w = 128, FastRows3), cleared 8 at a time");
 	static_assert(CT::lstr == 64 || CT::lstr == 128 || CT::lstr == 256,"the gw layout holds strings of up to 64 bases in one word per pattern mask, of up to 128 in two (round 6), of up to 255 in four (tier 17)");
 	static constexpr uint32_t pw = CT::lstr/64;
 	static constexpr uint32_t maxlen = CT::lstr < 256u ? static_cast<uint32_t>(CT::lstr) : 255u;      // longest string the layout holds: its length is a byte
-	static constexpr bool oneslab = FastOneSlab<CT>::value != 0;      // FastTier<17>: layout and slab in one buffer, the layout first
+	static constexpr bool oneslab = FastOneSlab<CT>::value != 0;      // FastTier<17> / <20>: layout and slab in one buffer, the layout first
+	// FastTier<20>, w = 128: three 64 bit words per position mask (model tables of up to 192 rows; w = 128 has 129), rows of 192 symbols for candidates and consensus
+	static constexpr bool rows3 = FastRows3<CT>::value != 0;
+	static_assert(!rows3 || CT::wide != 0,"three-word position masks extend the two words of a wide tier");
+	static constexpr uint32_t maskrows = CT::wide ? (rows3 ? 192u : 128u) : 64u;      // rows of the model table the position masks of a stretch can name
 	typedef typename CT::sid_t sid_t;      // stretch ids: 8 bits (at most 250 stretches) or 16 bits
 	// more than 256 strings (tier 15): 16 bit node frequencies capped at fqmax, 32 bit first-instance offsets, a 32 byte forward weight record
 	static constexpr bool wides = CT::maxs > 256;
@@ -291,8 +296,9 @@ struct FastLds<CT,true>
 	FLD(midB,uint8_t,8,e_midA)
 	FLD(nv,uint32_t,CT::ncap,e_midB)
 	FLD(npred,sid_t,CT::ncap,e_nv)
-	// longest consensus / candidate of this tier: MAXCONS, 128 in the wide tier (consensus of a window of up to 127 bases)
-	static constexpr uint32_t consmax = CT::wide ? 128u : static_cast<uint32_t>(MAXCONS);
+	// longest consensus / candidate of this tier: MAXCONS, 128 in the wide tier (consensus of a window of up to 127 bases), 192 in the tier of w = 128
+	static constexpr uint32_t consmax = CT::wide ? (rows3 ? 192u : 128u) : static_cast<uint32_t>(MAXCONS);
+	static_assert(!rows3 || 2u + 2u*(DACC_WMAX+2u) + DACC_WMAX + consmax <= static_cast<uint32_t>(WRECW),"the wide record holds the group offsets and the symbols of a window of 128 bases: one symbol per A position and at most consmax consensus symbols");
 	static constexpr uint32_t alw = CT::wide ? 2u : 1u;      // 64 bit words per column of the consensus -> A alignment
 	FLD(bestL,uint8_t,consmax,e_npred)
 	static constexpr uint32_t sbase = (e_bestL + 15u) & ~15u;
@@ -367,7 +373,9 @@ struct FastLds<CT,true>
 	FLD(maskR,uint64_t,CT::scap,e_maskF)
 	FLD(maskFh,uint64_t,(CT::wide ? CT::scap : 0u),e_maskR)      // wide tier: start positions 64 ... 127
 	FLD(maskRh,uint64_t,(CT::wide ? CT::scap : 0u),e_maskFh)
-	FLD(woffF,toff_t,CT::scap,e_maskRh)      // (toff_t: 16 bits, wcap <= 65535; more than 1024 strings: 32 bits)
+	FLD(maskFx,uint64_t,(rows3 ? CT::scap : 0u),e_maskRh)      // tier of w = 128: start positions 128 ... 191 (the table of w = 128 has row 128)
+	FLD(maskRx,uint64_t,(rows3 ? CT::scap : 0u),e_maskFx)
+	FLD(woffF,toff_t,CT::scap,e_maskRx)      // (toff_t: 16 bits, wcap <= 65535; more than 1024 strings: 32 bits)
 	FLD(woffR,toff_t,CT::scap,e_woffF)
 	static_assert(sizeof(toff_t) == 4 || CT::wcap <= 65535u,"weight offsets of 16 bits");
 	FLD(links,uint16_t,CT::lcap,e_woffR)

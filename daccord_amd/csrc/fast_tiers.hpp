@@ -1,5 +1,5 @@
 /*
- * The capacity tiers of the window fast path (fast_window.hpp), as compile-time data: one row FastTier<N> per tier of DACC_ALL_TIERS
+ * The capacity tiers of the window fast path (fast_window.hpp), as compile-time data: one row FastTier<N> per tier of DACC_EVERY_TIER
  * (tier_pipeline.hpp).  Plain C++17, no device code: the planner, the launches, the emulation and the engine all read the rows from here.
  * The engine is instantiated once per row; the layout FastLds<CT> (fast_layout.hpp) is a compile time constant, so every LDS access has
  * an immediate offset.  Which of the tiers a batch runs, in which order and behind which switches, is written down once, in tier_pipeline.hpp.
@@ -25,6 +25,7 @@
  *     17  second stream, wide batches: strings of 129 ... 255 bases   gw      16 / 16 bit       no LDS
  *     18  full-depth stage, shallow and deep: 2001 ... 5001 strings   gw      16 / 16 bit       no LDS
  *     19  wide deep stage, wide batches: 251 ... 1000 strings         gw      16 / 16 bit       no LDS
+ *     20  w = 128: every window of such a batch, strings up to 255     gw      16 / 16 bit       no LDS
  *
  * A window that does not fit its tier leaves it through processWindowFast (fast_window.hpp), which returns
  * FW_NEXT when a window overflows a tier (flags say what overflowed: 1 instances, 2 nodes, 8 candidates, 16 walk,
@@ -32,7 +33,7 @@
  * 0x20000 popped paths, 0x40000 score intervals), 1024 introsort's depth limit reached in the replayed std::sort (the tiers
  * stop there; the generic engine finishes such a range with libstdc++'s heapsort fallback), 2048 base length, 4096 candidate
  * length / sequence, 8192 gap filling) and FW_GENERIC for shapes the tier does not support (a window wider than it holds, a string
- * longer than its string stride lstr: 64 or 128 bases, tier 17: longer than 255); those go to tier 5 / tier 17 / the generic engine (dbg_window.hpp).
+ * longer than its string stride lstr: 64 or 128 bases, tiers 17 and 20: longer than 255); those go to tier 5 / tier 17 / the generic engine (dbg_window.hpp).
  */
 #ifndef DACC_FAST_TIERS_HPP
 #define DACC_FAST_TIERS_HPP
@@ -230,9 +231,27 @@ static_assert(uint32_t(FastTier<18>::mins) == VDEEP_MINS && uint32_t(FastTier<16
 template<> struct FastTier<19> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 4000, gw = 1, wcapg = 98304, rch = 64, fch = 16, fnw = 4, fnc = 72, idmax = 8000, rpstcap = 768, lstr = 128, maxs = 1000, precap = 16384, ncap = 8190, scap = 4096, lcap = 16384, wcap = 98304, rccap = 16384, fcap = 2048, siqcap = 512, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 16384, wide = 1, mins = 250, gmem = 1 }; };
 static_assert(uint32_t(FastTier<19>::mins) == VDEEP_MINS && uint32_t(FastTier<14>::maxs) == VDEEP_MINS && uint32_t(FastTier<19>::maxs) == FastTier<15>::maxs,"the wide deep stage takes what the last stage of a wide batch refuses at its string count");
 template<> struct FastTier<17> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 1000, gw = 1, wcapg = 16384, rch = 16, fch = 16, fnw = 8, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 256, maxs = 250, precap = 16384, ncap = 6144, scap = 1024, lcap = 8192, wcap = 16384, rccap = 4096, fcap = 4096, siqcap = 512, blcap = 128, seqcap = 96, psiq = 10, consrow = 128, lscrids = 4096, wide = 1, mins = 0, gmem = 1, oneslab = 1 }; };
-// (only tier 17 names the enumerator: for every other tier FastOneSlab<CT>::value is 0)
+// tier 20: the stage of a batch with w = 128 (tier_pipeline.hpp: ID_W128), in front of the generic engine, which used to run every window of such a batch.  Tier 17's row -- four
+// words per pattern mask, strings of up to 255 bases, one slab, its gap filling region and forward pool -- with the three widths that w = 128 needs and no tier below it has
+// (rows3: FastRows3<CT>, every other tier keeps its fields and its instruction stream):
+//  - position masks of THREE 64 bit words (maskF / maskFh / maskFx): the model table of w = 128 has w + 1 = 129 rows, a stretch's feasible start positions are rows 0 ... w;
+//    three words hold tables of up to 192 rows;
+//  - candidates and a consensus of up to 192 symbols (consrow, FastLds<CT>::consmax): on deletion-rich reads the consensus of a window of 128 bases is longer than
+//    128 symbols more often than not (123 ... 133 seen); the wide record holds 2 + 2 x 130 + 128 + 192 = 582 of its 640 bytes;
+//  - blcap = 192 base lengths (three occupancy words, as the forward base lengths FBLMAX = 191 have had).
+// One table is not tier 17's: the reverse pool.  With tier 17's 4096 paths in chunks of 16 -- an enumeration's 32 chunk ids name 512 paths -- 76 of 364 windows of the
+// even error mix at k = 10 and 15 of 364 of the deletion-rich mix overflow it (flags 0x4200; emulation, tests/w128_cases.py shapes E and D): a window of 128 bases has
+// reverse paths of twice the stretches.  Tier 19's pool instead: 16384 paths in 256 chunks of rch = 64, 2048 paths per enumeration, and lscrids = 16384, so that the retry
+// of a pending-path heap on the whole scratch holds every path of the pool.
+// A feasible stretch has up to 129 nodes of frequency at most 255: its weight stays below 2^48, the 16 bit high part (FastEngine: SROWS).
+// Strings of more than 255 bases are FFAIL(4) = FW_GENERIC, more than 250 strings and table overflows FW_NEXT: the generic engine runs them.
+template<> struct FastTier<20> { typedef uint16_t id_t; typedef uint16_t sid_t; enum : uint32_t { smax = 1000, gw = 1, wcapg = 16384, rch = 64, fch = 16, fnw = 8, fnc = 72, idmax = 4000, rpstcap = 768, lstr = 256, maxs = 250, precap = 16384, ncap = 6144, scap = 1024, lcap = 8192, wcap = 16384, rccap = 16384, fcap = 4096, siqcap = 512, blcap = 192, seqcap = 96, psiq = 10, consrow = 192, lscrids = 16384, wide = 1, mins = 0, gmem = 1, oneslab = 1, rows3 = 1 }; };
+// (only tiers 17 and 20 name the enumerator: for every other tier FastOneSlab<CT>::value is 0)
 template<typename CT, typename = void> struct FastOneSlab { enum : uint32_t { value = 0 }; };
 template<typename CT> struct FastOneSlab<CT,decltype(void(CT::oneslab))> { enum : uint32_t { value = (CT::oneslab != 0) ? 1u : 0u }; };
+// (only tier 20 names this one: three words per position mask, 192 symbol rows, 192 base lengths)
+template<typename CT, typename = void> struct FastRows3 { enum : uint32_t { value = 0 }; };
+template<typename CT> struct FastRows3<CT,decltype(void(CT::rows3))> { enum : uint32_t { value = (CT::rows3 != 0) ? 1u : 0u }; };
 
 }
 #endif

@@ -603,6 +603,9 @@ struct FastEngine
 	DEV void levelSuccessors2()
 	{
 		uint32_t const s = 2;
+		// (positions here are bytes: the ranges of nrange, the candidate's position under its k-mer (& 0xFF), the instance's position clamped to min(position, nsup) --
+		// rows 0 ... 128 of the table of w = 128 and its read offsets fit as those of every narrower table do)
+		static_assert(FastLds<CT>::maskrows <= 255u && FastLds<CT>::supcap <= 255u,"gap filling: a feasible position (a row of the model table, up to 129 at w = 128) and a clamped read offset are bytes");
 		LDSQ uint64_t * REC = L.gfbuf();          // records (from<<48 | to<<32 | cv)
 		uint32_t const cap = FastLds<CT>::gfcap/2;    // second half holds the (cv,pos) candidates
 		LDSQ uint64_t * ANE = L.gfbuf() + cap;
@@ -1191,6 +1194,9 @@ struct FastEngine
 		static_assert(sizeof(toff_t) == 2 || 2ull*CT::scap*128ull <= TOFFMAX,"task offsets: every (stretch, direction, position) triple can be named");
 		// (legacy layout: 16 bit records over the bytes of ulo / uhi, at most 511 units; gw layout: 32 bit records)
 		auto const urec = unitRecords();
+		// (start position field of a unit record: 7 bits, positions up to 127; the tier of w = 128 -- rows 0 ... 128 -- takes 8, its 2 x scap units leave room in the 32 bit record)
+		enum : uint32_t { ULOB = FastRows3<CT>::value ? 8u : 7u, ULOMASK = (1u << ULOB) - 1u };
+		static_assert(!FastRows3<CT>::value || (GW && 2ull*CT::scap < (1ull << (32u-ULOB))),"unit records of the three-word tier: 8 bit start position under the unit number");
 		// (the four words of unit cc*WSZ + lane: registers, every loop over the chunks is unrolled.  More than 2048 strings -- 384 chunks --: words of device
 		// memory instead, in the bytes of the generation's instance array, which nothing reads between two builds of the instances; a lane reads back
 		// only what it wrote itself)
@@ -1248,6 +1254,7 @@ struct FastEngine
 				{
 				if ( rev ) { L.maskR()[s] = 0; L.woffR()[s] = 0; } else { L.maskF()[s] = 0; L.woffF()[s] = 0; }
 				if constexpr ( CT::wide != 0 ) { if ( rev ) L.maskRh()[s] = 0; else L.maskFh()[s] = 0; }
+				if constexpr ( FastRows3<CT>::value != 0 ) { if ( rev ) L.maskRx()[s] = 0; else L.maskFx()[s] = 0; }
 				}
 			}
 			ulo_r[cc] = lo_; uw_r[cc] = w; ucls_r[cc] = cls; upos_r[cc] = 0;
@@ -1282,7 +1289,7 @@ struct FastEngine
 				uint32_t const usel = (need && !filt) ? 8u : 0u, umask = need ? 0xFFu : ~0u;
 				uint32_t const wsel = (uw_r[cc] >> usel) & umask, lsel = (ulo_r[cc] >> usel) & umask;
 				FEAS_NEED_UNIT(sfrom + (u >= ns ? u-ns : u),u >= ns,need ? (ulo_r[cc] >> 8) : lsel,need ? (ulo_r[cc] >> 8) + (uw_r[cc] >> 8) : lsel+wsel,lsel,lsel+wsel)
-				urec[upos_r[cc]] = lsel | (u << 7); L.toff()[upos_r[cc]] = static_cast<toff_t>(wsel);
+				urec[upos_r[cc]] = lsel | (u << ULOB); L.toff()[upos_r[cc]] = static_cast<toff_t>(wsel);
 			}
 		}
 		wv_sync();
@@ -1325,10 +1332,10 @@ struct FastEngine
 				ubase += dacc_popc64(starts);          // a start at c+WSZ (bit WSZ-1) is the next round's first task
 			}
 			uint32_t const ur = act ? urec[u] : 0u;          // u = position in the processing order
-			uint32_t const uu = ur >> 7;
+			uint32_t const uu = ur >> ULOB;
 			bool const rev = uu >= ns; uint32_t const s = sfrom + (rev ? uu-ns : uu);
 			uint32_t const t0 = act ? L.toff()[u] : 0u;
-			uint32_t const P = act ? ((ur & 127u) + (t-t0)) : 0u;
+			uint32_t const P = act ? ((ur & ULOMASK) + (t-t0)) : 0u;
 			bool ok = act;
 			uint64_t sum = 0, f1 = 0, fl = 0;
 			if ( act )
@@ -1400,7 +1407,17 @@ struct FastEngine
 					uint32_t const tend = L.toff()[u+1];
 					uint32_t const lastlane = (tend-c < WSZ) ? (tend-c) : static_cast<uint32_t>(WSZ);     // exclusive
 					uint64_t const span = (lastlane-firstlane >= 64) ? ~0ull : ((1ull << (lastlane-firstlane))-1ull);
-					if constexpr ( CT::wide != 0 )
+					if constexpr ( FastRows3<CT>::value != 0 )
+					{
+						// start positions up to 191: the round's bits (at most 64, from position P on) lie in word P/64 and, shifted out of it, in the next one.
+						// All three words in unconditional selects: which word a bit goes to is data, not control flow
+						uint64_t const seg = (okb >> firstlane) & span;
+						uint32_t const wd = P >> 6, sh = P & 63u;
+						uint64_t const lo_ = seg << sh, hi_ = sh ? (seg >> (64u-sh)) : 0ull;
+						uint64_t const b0 = wd == 0 ? lo_ : 0ull, b1 = wd == 1 ? lo_ : (wd == 0 ? hi_ : 0ull), b2 = wd == 2 ? lo_ : (wd == 1 ? hi_ : 0ull);
+						if ( rev ) { L.maskR()[s] |= b0; L.maskRh()[s] |= b1; L.maskRx()[s] |= b2; } else { L.maskF()[s] |= b0; L.maskFh()[s] |= b1; L.maskFx()[s] |= b2; }
+					}
+					else if constexpr ( CT::wide != 0 )
 					{
 						// start positions up to 127: the round's bits (at most 64, from position P on) may straddle the two words
 						uint64_t const seg = (okb >> firstlane) & span;
@@ -1431,12 +1448,12 @@ struct FastEngine
 	// of that tier holds whole 64 bit words, the reverse record's third word 18 + 12 bits)
 	// (the nodes of a feasible stretch: one per row of the model table the tier admits -- nrows <= 128 in a wide tier, 64 otherwise (resolveTiers).  A wide tier of
 	// more than 256 strings, fqmax = 1023 at 128 nodes: stretch weight < 2^49, 17 bit high part, the reverse record's third word 17 + 10 bits; the wide tiers of
-	// up to 250 strings, fqmax = 255 at 128 nodes, stay below 2^47 and keep their 16 bits)
+	// up to 250 strings, fqmax = 255 at 128 nodes, stay below 2^47 and keep their 16 bits; so does the tier of w = 128, 129 nodes of at most 255: SROWS = 192 there, 192 x 255 < 2^16)
 	enum : uint32_t { FQMAX = FastLds<CT>::fqmax, NWHB = FQMAX <= 255u ? 8u : (FQMAX <= 1023u ? 10u : 12u), NWHMASK = (1u << NWHB) - 1u,
-		SROWS = CT::wide ? 128u : 64u,
+		SROWS = FastLds<CT>::maskrows,
 		SWHB = FQMAX <= 1023u ? ((SROWS*FQMAX) >> 16 ? 17u : 16u) : 18u, SWHMASK = (1u << SWHB) - 1u };
 	static_assert((static_cast<uint64_t>(FQMAX)*0xFFFFFFFFull) >> (32u+NWHB) == 0,"high part of a node weight: fqmax table words");
-	static_assert((static_cast<uint64_t>(SROWS)*static_cast<uint64_t>(FQMAX)*0xFFFFFFFFull) >> (32u+SWHB) == 0,"high part of a stretch weight: SROWS nodes of fqmax table words each, SROWS = 128 rows of the model table in a wide tier and 64 otherwise");
+	static_assert((static_cast<uint64_t>(SROWS)*static_cast<uint64_t>(FQMAX)*0xFFFFFFFFull) >> (32u+SWHB) == 0,"high part of a stretch weight: SROWS nodes of fqmax table words each, SROWS = the rows of the model table the tier's position masks name: 64, 128 in a wide tier, 192 in the tier of w = 128 (whose table has 129: 129 x 255 table words < 2^47, and 192 x 255 still < 2^48, the 16 bit high part)");
 	static_assert(!FastLds<CT>::xwides || CT::wide == 0,"more than 1024 strings in a wide tier: 128 x 4095 table words need a 19 bit high part");
 	static_assert(SWHB + NWHB <= 32u,"reverse record: both high parts in its third word");
 	static_assert(SWHB == 16u || FastLds<CT>::wides,"a stretch weight of more than 48 bits needs the 32 byte forward record");
@@ -1538,10 +1555,29 @@ struct FastEngine
 	{
 		return p < 64u ? dacc_popc64(m0 & ((1ull<<p)-1ull)) : dacc_popc64(m0) + dacc_popc64(m1 & ((1ull<<(p-64u))-1ull));
 	}
+	// (tier of w = 128) the same over three words (m2: positions 128-191); the words are chosen by selects
+	DEV static bool mask3Test(uint64_t const m0, uint64_t const m1, uint64_t const m2, uint32_t const p)
+	{
+		uint32_t const wd = p >> 6; uint64_t const m = wd == 0 ? m0 : (wd == 1 ? m1 : m2);
+		return ((m >> (p & 63u)) & 1ull) != 0;
+	}
+	DEV static uint32_t mask3Rank(uint64_t const m0, uint64_t const m1, uint64_t const m2, uint32_t const p)
+	{
+		uint32_t const wd = p >> 6; uint64_t const below = (1ull << (p & 63u)) - 1ull;
+		uint64_t const m = wd == 0 ? m0 : (wd == 1 ? m1 : m2);
+		return (wd >= 1 ? dacc_popc64(m0) : 0u) + (wd >= 2 ? dacc_popc64(m1) : 0u) + dacc_popc64(m & below);
+	}
 	DEV int32_t sfFind(uint32_t const s, uint32_t const p) const
 	{
 		FEAS_NEED_PROBE(s,false,p)
-		if constexpr ( CT::wide != 0 )
+		if constexpr ( FastRows3<CT>::value != 0 )
+		{
+			if ( p >= 192 ) return -1;
+			uint64_t const m0 = L.maskF()[s], m1 = L.maskFh()[s], m2 = L.maskFx()[s];
+			if ( !mask3Test(m0,m1,m2,p) ) return -1;
+			return L.woffF()[s] + mask3Rank(m0,m1,m2,p);
+		}
+		else if constexpr ( CT::wide != 0 )
 		{
 			if ( p >= 128 ) return -1;
 			uint64_t const m0 = L.maskF()[s], m1 = L.maskFh()[s];
@@ -1556,7 +1592,14 @@ struct FastEngine
 	DEV int32_t csfFind(uint32_t const s, uint32_t const p) const
 	{
 		FEAS_NEED_PROBE(s,true,p)
-		if constexpr ( CT::wide != 0 )
+		if constexpr ( FastRows3<CT>::value != 0 )
+		{
+			if ( p >= 192 ) return -1;
+			uint64_t const m0 = L.maskR()[s], m1 = L.maskRh()[s], m2 = L.maskRx()[s];
+			if ( !mask3Test(m0,m1,m2,p) ) return -1;
+			return L.woffR()[s] + mask3Rank(m0,m1,m2,p);
+		}
+		else if constexpr ( CT::wide != 0 )
 		{
 			if ( p >= 128 ) return -1;
 			uint64_t const m0 = L.maskR()[s], m1 = L.maskRh()[s];
@@ -1573,7 +1616,35 @@ struct FastEngine
 	{
 		FEAS_NEED_LINK(i,b)
 		uint32_t const shift = L.sslen()[b]-1;
-		if constexpr ( CT::wide != 0 )
+		if constexpr ( FastRows3<CT>::value != 0 )
+		{
+			if ( shift >= 192 ) return false;
+			uint64_t const a0 = L.maskR()[i], a1 = L.maskRh()[i], a2 = L.maskRx()[i], b0 = L.maskR()[b], b1 = L.maskRh()[b], b2 = L.maskRx()[b];
+			// (b0,b1,b2) << shift over 192 bits: by whole words first, then by the bits left, every word in a select
+			uint32_t const wsh = shift >> 6, bsh = shift & 63u;
+			uint64_t const w0 = wsh == 0 ? b0 : 0ull, w1 = wsh == 0 ? b1 : (wsh == 1 ? b0 : 0ull), w2 = wsh == 0 ? b2 : (wsh == 1 ? b1 : b0);
+			uint64_t const s0 = w0 << bsh;
+			uint64_t const s1 = (w1 << bsh) | (bsh ? (w0 >> (64u-bsh)) : 0ull);
+			uint64_t const s2 = (w2 << bsh) | (bsh ? (w1 >> (64u-bsh)) : 0ull);
+			uint64_t c0 = a0 & s0, c1 = a1 & s1, c2 = a2 & s2;
+			uint64_t weight = 0;
+			while ( c0 | c1 | c2 )
+			{
+				uint32_t const wd = c0 ? 0u : (c1 ? 1u : 2u);
+				uint64_t const cw = wd == 0 ? c0 : (wd == 1 ? c1 : c2);
+				uint32_t const pa = 64u*wd + static_cast<uint32_t>(__builtin_ctzll(cw));
+				uint64_t const cn = cw & (cw-1);
+				c0 = wd == 0 ? cn : c0; c1 = wd == 1 ? cn : c1; c2 = wd == 2 ? cn : c2;
+				uint32_t const ia = L.woffR()[i] + mask3Rank(a0,a1,a2,pa);
+				uint32_t const pb = pa-shift;
+				uint32_t const ib = L.woffR()[b] + mask3Rank(b0,b1,b2,pb);
+				WR const ra = recR(ia);
+				uint64_t const lweight = wuR(ib) + (ra.w - ra.w1);
+				weight = lweight > weight ? lweight : weight;
+			}
+			return weight >= FW_THRES_01;
+		}
+		else if constexpr ( CT::wide != 0 )
 		{
 			if ( shift >= 128 ) return false;
 			uint64_t const a0 = L.maskR()[i], a1 = L.maskRh()[i], b0 = L.maskR()[b], b1 = L.maskRh()[b];
@@ -3679,7 +3750,7 @@ struct FastEngine
 		{
 		uint32_t const m = P.w;
 		enum { PW = FastLds<CT>::pw };
-		static_assert(PW >= 2,"the A window of a wide tier (string 0, stride PW) has at least two words per pattern mask: w <= 127 uses words 0 and 1");
+		static_assert(PW >= 2,"the A window of a wide tier (string 0, stride PW) has at least two words per pattern mask: w <= 128 uses words 0 and 1");
 		LDSQ uint64_t const * PEQ = L.peq();      // string 0 = the A window: word q of symbol c at PW*c + q
 		uint64_t const mask1 = (m == 128) ? ~0ull : ((1ull<<(m-64))-1);
 		uint64_t Pv0 = ~0ull, Mv0 = 0, Pv1 = mask1, Mv1 = 0; uint32_t score = m;
@@ -3881,7 +3952,7 @@ DEV int processWindowFast(FastBatch const & FB, uint64_t const widx, LDSQ uint8_
 	WindowOut out; out.status = WS_INSUFFICIENT; out.mao = 0; out.elength = 0; out.k = 0; out.filterfreq = -1; out.conslen = 0; out.minrate = 0; out.flags = 0;
 	uint8_t * rec = B.wrec + widx*(CT::wide ? DACC_WREC_OF(B.P.w) : static_cast<uint32_t>(WREC));
 	if ( lane == 0 ) rec[0] = 0;
-	if ( B.P.w > (CT::wide ? 127u : 63u) ) { FFAIL(1) }
+	if ( B.P.w > (CT::wide ? (FastRows3<CT>::value ? 128u : 127u) : 63u) ) { FFAIL(1) }      // (rows 0 ... w of the model table: 64, 128 or 192 positions per mask)
 
 	DevOvl const * ov = B.ovl + pile.first_ovl;
 	uint32_t nact = 0, mao = 0, toolong = 0;

@@ -9,7 +9,9 @@
  *   wide batches                              slot 1: 8     slot 2: 9
  *   shallow and deep  tier 5 on the second stream (k_window_long), in front of the generic engine there
  *   wide batches      the LONG STRING stage on the second stream: tier 17 (strings of 129 ... 255 bases, layout in device memory), in front of the generic engine there
- *   every batch       the TRAILING stages, each once, behind the slots and in front of the generic engine: tier 13 (shallow, deep) / tier 14 (wide), then in
+ *   w = 128           ONE stage, tier 20 (three words per position mask: the model table has 129 rows; strings of up to 255 bases, layout in device memory), over every window
+ *                     of the batch, in front of the generic engine; no slot, no trailing stage and no second stream run there
+ *   every other batch the TRAILING stages, each once, behind the slots and in front of the generic engine: tier 13 (shallow, deep) / tier 14 (wide), then in
  *                     shallow and deep batches tier 15, tier 16 and tier 18 and in wide batches tier 19, each only in a batch with a window deep enough for it
  *
  * (TIER_CHAIN below: one row per stage, one column per batch shape.)
@@ -45,6 +47,12 @@
  *                                          8, 9 and 14 refuse at their string count; those                      or deep batch keeps tier 3)
  *                                          of at most 250 passed on
  *
+ * The stage of w = 128 (ID_W128, ROLE_ALONE) runs tier 20 -- tier 17 with three words per position mask, rows of 192 symbols and tier 19's reverse pool -- over every window of a batch
+ * with a window of 128 bases, with a kernel of its own, k_window_fast<20>, a hand-on list and a slab of its own (optional like a trailing stage's), and k_window runs what it hands on:
+ * more than 250 strings, a string of more than 255 bases, a table that overflowed.  DACC_W128_TIER=0 removes it: such a batch is the generic engine alone, as before the stage.
+ * DACC_W128_AS_SLOT2=1 (tests) makes tier 20 the third slot's main tier and the second stream's tier of such a batch instead and switches the stage off: a harness that walks the
+ * three slots and ROLE_LONG then runs every window in the tier, those with a string of more than 128 bases through the second stream's path.  It counts in TierSwitches::conflict.
+ *
  * The LONG STRING stage (ID_LONG in a wide batch, ROLE_LONG) runs tier 17 -- tier 14 with four words per pattern mask, strings of up to 255 bases -- over the
  * two lists of the second stream (the pre-scan's: a B string of more than 128 bases; the first tier's generic-only windows) with a kernel of its own,
  * k_window_fast<17>, in front of k_window_long, which then runs the generic engine alone over what the tier handed on (a string of more than 255 bases,
@@ -76,6 +84,12 @@ enum : uint32_t { T0INST_DEFAULT = 576, T7INST_DEFAULT = 704 };      // a window
 // The tiers.  KERNEL: those with a kernel of their own (k_window_fast<N>, window_kernels.hpp); tier 5 runs inside k_window_long.
 #define DACC_KERNEL_TIERS(X) X(0) X(1) X(2) X(3) X(4) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19)
 #define DACC_ALL_TIERS(X) DACC_KERNEL_TIERS(X) X(5)
+// (the two lists above are the tiers whose layout sizes are recorded, tests/golden/fast_layout_sizes.txt: one line per tier of DACC_ALL_TIERS.  A tier added since has a
+// kernel of its own like those of DACC_KERNEL_TIERS and stands in a list of its own, with its own recorded line -- tier 20: tests/golden/w128_layout_sizes.txt.  Whatever
+// walks every kernel tier walks DACC_EVERY_KERNEL_TIER, whatever walks every tier DACC_EVERY_TIER)
+#define DACC_W128_TIERS(X) X(20)
+#define DACC_EVERY_KERNEL_TIER(X) DACC_KERNEL_TIERS(X) DACC_W128_TIERS(X)
+#define DACC_EVERY_TIER(X) DACC_ALL_TIERS(X) DACC_W128_TIERS(X)
 
 // From a run-time tier number to its compile-time capacities: f is called with a TierTag<N>, whose `type` is FastTier<N>
 template<int TIER> struct FastTier;
@@ -83,12 +97,12 @@ template<int TIER> struct TierTag { typedef FastTier<TIER> type; };
 template<typename F> static inline auto withTier(uint32_t const tier, F && f) -> decltype(f(TierTag<0>()))
 {
 #define DACC_TIER_CASE(N) case N: return f(TierTag<N>());
-	switch ( tier ) { DACC_ALL_TIERS(DACC_TIER_CASE) }
+	switch ( tier ) { DACC_EVERY_TIER(DACC_TIER_CASE) }
 #undef DACC_TIER_CASE
 	std::abort();
 }
 
-enum TierRole { ROLE_FRONT, ROLE_MAIN, ROLE_LONG, ROLE_LAST };      // front tier of a slot, the slot's main tier, tier 5 / tier 17 on the second stream, the device-memory tier behind the slots
+enum TierRole { ROLE_FRONT, ROLE_MAIN, ROLE_LONG, ROLE_LAST, ROLE_ALONE };      // front tier of a slot, the slot's main tier, tier 5 / tier 17 on the second stream, the device-memory tier behind the slots, the one stage of a batch no slot runs in (w = 128)
 // What switches a stage off, beside its bit of DACC_TIERS, its LDS size (at most the 160 KiB of a CU) and a batch shape it has no tier
 // for (TIER_NONE: "not in a wide batch", "not in a deep batch").  A front tier also needs the main tier of its slot.
 enum : uint32_t
@@ -100,6 +114,7 @@ enum : uint32_t
 	GATE_PREV_SLOT = 16,  // needs the main tier of the slot in front as well (the dense tiers need slots 1 and 2)
 	GATE_DEEP = 128,      // DACC_DEEP_TIER=0 switches it off (windows of more than 96 strings run in the generic engine, as before the deep-window tier)
 	GATE_TRAILING = 256,  // a trailing stage: its row's DACC_*_TIER=0 or DACC_*_AS_SLOT2=1 switches it off; needs a slot that ran and a window of more strings than its row's minstrings in the batch
+	GATE_ALONE = 512,     // the stage of a w = 128 batch: its row's DACC_*_TIER=0 or DACC_*_AS_SLOT2=1 switches it off; needs no slot (none runs there)
 	GATE_LONGSTR = 2048,  // DACC_LONGSTR_TIER=0 switches it off in a wide batch (the second stream of a wide batch is then the generic engine alone); no gate in the other shapes
 	STAGE_PREPASS = 32,   // (no gate) fed by the size-class pre-pass instead of the list in front of it
 	STAGE_ADAPTIVE = 64   // (no gate) switches itself off for the rest of a context when it hands on too much (DACC_T7_ADAPT)
@@ -119,14 +134,15 @@ enum : uint32_t { WORK_SLOT0 = 0, WORK_SLOT1 = 8, WORK_SLOT2 = 16, WORK_DENSE = 
 	WORK_WDEEP_COUNT = 144,    // two words: windows of more than VDEEP_MINS strings the wide deep stage read / handed on (for dacc_timing)
 	// (everything above is the first stream's and cleared at the start of every pass; the second stream clears what follows in front of its launches)
 	WORK_LONGSTR = 152,        // the long string stage's launch over the pre-scan list, WORK_LONGSTR + 8: its launch over the first tier's generic-only list
-	WORK_WORDS = 168 };
+	WORK_W128 = 168,           // the stage of a w = 128 batch (no slot, no second stream there: cleared with the whole array in front of its launch)
+	WORK_WORDS = 176 };
 
 // The stages, in the order they run (ID_FDEEP runs behind ID_XDEEP and ID_WDEEP behind that: the trailing stages run in the order of their rows, and no row between them is one; in a
 // wide batch ID_WDEEP stands directly behind ID_LAST, the rows between them have no wide tier); their
 // place in this table is their place in BatchPlan::stageCaps, TierPipeline and dacc_ctx::st.  TIER_NSTAGES counts the rows up to ID_LONG, which is what a caller
 // that holds one capacity record per stage in an array of TIER_NSTAGES walks (the emulation harness, tests/tiers/tier_resolution.cpp and its recording of one
 // column per stage); the rows added since stand behind it, TIER_NROWS counts all, and resolveTiers resolves them for a caller that says it holds them (`rows`).
-enum TierId { ID_T0, ID_T7, ID_SLOT0, ID_SLOT1, ID_DENSE, ID_DEEP, ID_SLOT2, ID_LAST, ID_VDEEP, ID_XDEEP, ID_LONG, TIER_NSTAGES, ID_FDEEP = TIER_NSTAGES, ID_WDEEP, TIER_NROWS };
+enum TierId { ID_T0, ID_T7, ID_SLOT0, ID_SLOT1, ID_DENSE, ID_DEEP, ID_SLOT2, ID_LAST, ID_VDEEP, ID_XDEEP, ID_LONG, TIER_NSTAGES, ID_FDEEP = TIER_NSTAGES, ID_WDEEP, ID_W128, TIER_NROWS };
 enum { TIER_NSLOTS = 3, TIER_NONE = 255, TIER_SHALLOW_FIRST = 1 };      // (the first slot's main tier of shallow batches: a batch whose windows mostly overflow its strings / instances is deep)
 enum : uint32_t { VDEEP_MINS = 250 };      // the very deep stage takes the windows with more strings than this (= FastTier<15>::mins = FastTier<13>::maxs; fast_tiers.hpp asserts this and the two below)
 enum : uint32_t { XDEEP_MINS = 1000 };     // the deepest stage is resolved for a batch with a window of more strings than this (= FastTier<15>::maxs); its tier takes what has more than VDEEP_MINS
@@ -146,7 +162,16 @@ struct TierStage
 	bool slot2wide = false;                // does its AS_SLOT2 switch apply to a wide batch (else that keeps tier 9)
 	bool slot2narrow = true;               // does it apply to a shallow or deep batch (else that keeps tier 3)
 	uint64_t slab = 0;                     // bytes of device memory its workgroups' slabs may take together (0: TIER_GMEM_SLAB)
+	uint32_t onlyw = 0;                    // the row (its stage and its AS_SLOT2 switch) is for batches of this window size alone (0: any)
 };
+#if !defined(DACC_W128_SLAB_MB)
+#define DACC_W128_SLAB_MB 1024
+#endif
+// The budget of the stage of w = 128: tier 20's slab is 1 788 416 B per workgroup, 144 workgroups in the common 256 MiB -- and the stage runs EVERY window of its batch:
+// measured on an MI355X, 300 reads of 10 kb (92 988 windows) take 14.4 s with 144 workgroups and 3.8 s with the 600 of 1 GiB (profiles/w128_measurements.md).  The slab is
+// allocated for the grid, a workgroup per window of the batch up to that, and is optional like the others
+enum : uint64_t { W128_GMEM_SLAB = static_cast<uint64_t>(DACC_W128_SLAB_MB) << 20 };
+enum : uint32_t { W128 = 128 };      // the window size whose model table has 129 rows: three words per position mask (FastTier<20>)
 static TierStage const TIER_CHAIN[TIER_NROWS] = {
 	{ { 0, TIER_NONE, TIER_NONE }, 0, ROLE_FRONT, 3, STAGE_PREPASS, WORK_T0 },
 	{ { 7, TIER_NONE, TIER_NONE }, 0, ROLE_FRONT, 4, STAGE_PREPASS|STAGE_ADAPTIVE|GATE_PREV_FRONT|GATE_T7_ABOVE_T0, WORK_T7 },
@@ -164,17 +189,24 @@ static TierStage const TIER_CHAIN[TIER_NROWS] = {
 	// (behind TIER_NSTAGES; it runs behind ID_XDEEP)
 	{ { 18, 18, TIER_NONE }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_TRAILING, WORK_FDEEP, "DACC_FDEEP_TIER", "DACC_FDEEP_AS_SLOT2", FDEEP_MINS, false },
 	// (the wide batches' very deep stage: behind ID_LAST's tier 14 there.  The wide column of ID_VDEEP stays empty: a caller that walks TIER_NSTAGES rows resolves what it resolved)
-	{ { TIER_NONE, TIER_NONE, 19 }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_TRAILING, WORK_WDEEP, "DACC_WDEEP_TIER", "DACC_WDEEP_AS_SLOT2", VDEEP_MINS, true, false, WDEEP_GMEM_SLAB } };
+	{ { TIER_NONE, TIER_NONE, 19 }, 2, ROLE_LAST, -1, GATE_TABFIT|GATE_TRAILING, WORK_WDEEP, "DACC_WDEEP_TIER", "DACC_WDEEP_AS_SLOT2", VDEEP_MINS, true, false, WDEEP_GMEM_SLAB },
+	// (a batch of w = 128: no slot, no trailing stage and no second stream run there -- the stage takes every window of the batch and hands on to the generic engine.
+	// DACC_W128_AS_SLOT2=1 makes its tier the third slot's main tier AND the second stream's tier of such a batch instead: resolveTiers)
+	{ { TIER_NONE, TIER_NONE, 20 }, 2, ROLE_ALONE, -1, GATE_TABFIT|GATE_ALONE, WORK_W128, "DACC_W128_TIER", "DACC_W128_AS_SLOT2", 0, true, false, W128_GMEM_SLAB, W128 } };
 static TierId const TIER_MAIN[TIER_NSLOTS] = { ID_SLOT0, ID_SLOT1, ID_SLOT2 };
 // does the stage run in a batch of this shape, and the tier whose capacities the plan holds for it (a stage that does not run keeps
 // those of the nearest shape: the first slot of a wide batch has tier 1's or tier 4's)
 static inline bool stageRuns(TierStage const & st, bool const deep, bool const wide) { return st.tier[wide ? 2 : deep] != TIER_NONE; }
 // DACC_*_AS_SLOT2=1 of a trailing stage's row: the third slot's main tier is that stage's tier (read by the planner and by resolveTiers alike, so once per call)
 static inline bool stageAsSlot2(TierStage const & st) { char const * const e = st.slot2switch ? getenv(st.slot2switch) : 0; return e && e[0] == '1'; }
-static inline uint32_t stageTier(TierStage const & st, bool const deep, bool const wide)
+// (w: the batch's window size, for the rows that are for one size alone (TierStage::onlyw); a caller that leaves it out sees none of them.  Such a row's AS_SLOT2 switch
+// names the second stream's tier as well: the long string stage of that batch is its tier)
+static inline uint32_t stageTier(TierStage const & st, bool const deep, bool const wide, uint32_t const w = 0)
 {
 	TierStage const * t = &st;
-	if ( &st == &TIER_CHAIN[ID_SLOT2] ) for ( TierStage const & r : TIER_CHAIN ) if ( stageAsSlot2(r) && (wide ? r.slot2wide : r.slot2narrow) ) { t = &r; break; }
+	if ( &st == &TIER_CHAIN[ID_SLOT2] || &st == &TIER_CHAIN[ID_LONG] )
+		for ( TierStage const & r : TIER_CHAIN )
+			if ( (r.onlyw ? (r.onlyw == w) : (&st == &TIER_CHAIN[ID_SLOT2])) && stageAsSlot2(r) && (wide ? r.slot2wide : r.slot2narrow) ) { t = &r; break; }
 	// (a row with a wide tier only -- ID_WDEEP -- keeps that tier's capacities in the other shapes, where it does not run)
 	return (wide && t->tier[2] != TIER_NONE) ? t->tier[2] : (t->tier[deep] != TIER_NONE ? t->tier[deep] : (t->tier[0] != TIER_NONE ? t->tier[0] : t->tier[2]));
 }
@@ -257,23 +289,29 @@ static inline TierPipeline resolveTiers(TierSwitches const & S, bool const fastp
 	uint32_t const maxstrings = 0, uint32_t const rows = TIER_NSTAGES)
 {
 	TierPipeline R;
-	// wide windows, w = 64 ... 127 (model table of up to 128 rows): DACC_WIDE_TIER=0 leaves them to the generic engine, w = 128 always
-	R.widetier = wide && S.widetier && nrows <= 128 && nsup <= FSUPCAPW;
+	// wide windows, w = 64 ... 127 (model table of up to 128 rows: two words per position mask): DACC_WIDE_TIER=0 leaves them to the generic engine.
+	// w = 128 (BatchPlan::wide covers it; 129 rows, 0 ... w: three words per position mask, up to 192 rows) is a batch of its own: none of the wide tiers holds its
+	// table, so no slot, no trailing stage and no second stream run -- its stage (ID_W128, tier 20) alone, or, with DACC_W128_AS_SLOT2=1, that tier as the third slot's
+	// main tier and the second stream's tier
+	bool const w128 = wide && w == W128;
+	bool const w128slot = w128 && S.as_slot2[ID_W128];
+	R.widetier = wide && S.widetier && nrows <= (w128 ? 192u : 128u) && nsup <= FSUPCAPW;
 	R.usefast = fastpath && (R.widetier || (nrows <= 64 && nsup <= FSUPCAP && w <= 63));
 	R.handover = S.hand && !R.widetier;
 	R.handwords = (deep ? 2048u + 128u : 1024u + 64u) + 4u;
 	auto const gated = [&](uint32_t const i) -> bool
 	{
 		TierStage const & st = TIER_CHAIN[i]; FastCaps const & F = capsOf(i);
-		return R.usefast && stageRuns(st,deep,wide) && (F.gmem || F.ldsbytes <= TIER_LDS_CU) && (st.tiersbit < 0 || ((S.tiers >> st.tiersbit) & 1))
+		return R.usefast && stageRuns(st,deep,wide) && (st.onlyw ? st.onlyw == w : (!w128 || (w128slot && (i == ID_SLOT2 || i == ID_LONG)))) && (F.gmem || F.ldsbytes <= TIER_LDS_CU) && (st.tiersbit < 0 || ((S.tiers >> st.tiersbit) & 1))
 			&& (!(st.flags & GATE_TABFIT) || static_cast<uint64_t>(nrows+1)*(nsup+1) <= F.tabcap)
 			&& (!(st.flags & GATE_T7_ABOVE_T0) || S.t7inst > S.t0inst) && (!(st.flags & GATE_DENSE) || S.dense) && (!(st.flags & GATE_DEEP) || S.deepwin)
 			&& (!(st.flags & GATE_TRAILING) || (!S.off[i] && !S.as_slot2[i] && (!st.minstrings || maxstrings > st.minstrings)))
+			&& (!(st.flags & GATE_ALONE) || (!S.off[i] && !S.as_slot2[i]))
 			&& (!(st.flags & GATE_LONGSTR) || !wide || S.longstr);
 	};
 	{ FastCaps & F = capsOf(ID_SLOT0); if ( S.lds_t1 > F.ldsbytes && S.lds_t1 <= TIER_LDS_CU ) F.ldsbytes = S.lds_t1; }
 	{ FastCaps & F = capsOf(ID_T0); if ( S.lds_t0 > F.ldsbytes && S.lds_t0 <= TIER_LDS_CU ) F.ldsbytes = S.lds_t0; }
-	for ( uint32_t i = 0; i < rows; ++i ) { R.tier[i] = stageTier(TIER_CHAIN[i],deep,wide); if ( TIER_CHAIN[i].role != ROLE_FRONT ) R.ok[i] = gated(i); }
+	for ( uint32_t i = 0; i < rows; ++i ) { R.tier[i] = stageTier(TIER_CHAIN[i],deep,wide,w); if ( TIER_CHAIN[i].role != ROLE_FRONT ) R.ok[i] = gated(i); }
 	// a trailing stage reads what a slot handed on: no slot, no such stage (generic-only configurations stay generic-only)
 	for ( uint32_t i = 0; i < rows; ++i ) if ( TIER_CHAIN[i].role == ROLE_LAST ) R.ok[i] = R.ok[i] && R.anytier();
 	// the front tiers, in chain order (a front tier stands before the main tier of its slot)

@@ -1,5 +1,5 @@
 /*
- * The window kernels of libdaccord_hip.so, one translation unit each (k_fast_<tier>.hip for the tiers of DACC_KERNEL_TIERS,
+ * The window kernels of libdaccord_hip.so, one translation unit each (k_fast_<tier>.hip for the tiers of DACC_EVERY_KERNEL_TIER,
  * tier_pipeline.hpp -- the table of the tiers is fast_tiers.hpp --, and k_generic.hip, which also holds tier 5): they are
  * 150-260 KB of gfx950 code apiece and took 25 minutes to compile one after the other inside capi.hip; as separate objects they compile
  * side by side (daccord_amd/build.py).  This header holds what the units share: the work distribution, the kernel template of the LDS tiers (defined
@@ -100,14 +100,14 @@ __global__ void __launch_bounds__(64) DACC_WPE(TIER) k_window_fast(FastBatch FB,
 #if !defined(DACC_INSTANTIATE_TIER)
 // every unit but k_fast_<tier>.hip: the tiers' kernels are instantiated elsewhere
 #define DACC_EXTERN_TIER(N) extern template __global__ void k_window_fast<N>(FastBatch, uint32_t const *, uint32_t *);
-DACC_KERNEL_TIERS(DACC_EXTERN_TIER)
+DACC_EVERY_KERNEL_TIER(DACC_EXTERN_TIER)
 #undef DACC_EXTERN_TIER
 // the kernel of a run-time tier number (launches and hipFuncSetAttribute of capi.hip)
 typedef void (*FastKernel)(FastBatch, uint32_t const *, uint32_t *);
 static inline FastKernel fastKernel(uint32_t const tier)
 {
 #define DACC_KERNEL_CASE(N) case N: return k_window_fast<N>;
-	switch ( tier ) { DACC_KERNEL_TIERS(DACC_KERNEL_CASE) }
+	switch ( tier ) { DACC_EVERY_KERNEL_TIER(DACC_KERNEL_CASE) }
 #undef DACC_KERNEL_CASE
 	return 0;
 }

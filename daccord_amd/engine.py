@@ -9,7 +9,7 @@ fails loudly if the HIP library is missing."""
 import ctypes as C
 import os
 import numpy as np
-from ._structs import (DaccParams, DaccOverlap, DaccPile, DaccFragment, DaccTiming, DaccTimingLong, DaccTimingFull, DaccTimingWide, DaccWindowResult, default_params)
+from ._structs import (DaccParams, DaccOverlap, DaccPile, DaccFragment, DaccTiming, DaccTimingLong, DaccTimingFull, DaccTimingWide, DaccTimingW128, DaccWindowResult, default_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("DACC_LIB") or os.path.join(_HERE, "libdaccord_hip.so")
@@ -50,7 +50,7 @@ def lib():
         L.dacc_pile_select.argtypes = [vp, C.c_uint64, C.c_int, C.c_uint64, vp, vp]
         L.dacc_last_timing.argtypes = [vp, C.POINTER(DaccTiming)]
         if hasattr(L, "dacc_last_timing2"):            # (variant libraries of earlier rounds, DACC_LIB, lack it)
-            L.dacc_last_timing2.argtypes = [vp, vp, C.c_size_t]      # (a DaccTiming, a DaccTimingLong, a DaccTimingFull or a DaccTimingWide, with its size)
+            L.dacc_last_timing2.argtypes = [vp, vp, C.c_size_t]      # (a DaccTiming, a DaccTimingLong, a DaccTimingFull, a DaccTimingWide or a DaccTimingW128, with its size)
         L.dacc_rerun_resident.argtypes = [vp]
         L.dacc_debug_windows.argtypes = [vp, vp, C.c_uint64, vp]
         L.dacc_debug_tables.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
@@ -170,9 +170,17 @@ class Engine:
 
     def timing_wide(self):
         """The timing record of the last run with the wide deep stage's fields behind those of the full-depth stage (wdeep_ms, wdeep_windows,
-        wdeep_out): the 224 bytes of today's dacc_timing.  timing(), timing_long() and timing_full() keep returning the first 176, 192 and 208."""
+        wdeep_out): the first 224 bytes of today's dacc_timing.  timing(), timing_long() and timing_full() keep returning the first 176, 192 and 208."""
         t = DaccTimingWide()
         self._chk(self.L.dacc_last_timing2(self.h, C.byref(t), C.sizeof(DaccTimingWide)))
+        return t
+
+    def timing_w128(self):
+        """The timing record of the last run with the fields of the stage of w = 128 behind those of the wide deep stage (w128_ms, w128_windows,
+        w128_out): the 240 bytes of today's dacc_timing.  timing(), timing_long(), timing_full() and timing_wide() keep returning the first 176,
+        192, 208 and 224."""
+        t = DaccTimingW128()
+        self._chk(self.L.dacc_last_timing2(self.h, C.byref(t), C.sizeof(DaccTimingW128)))
         return t
 
     def debug_windows(self):

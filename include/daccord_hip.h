@@ -241,18 +241,29 @@ typedef struct dacc_timing {
 	uint32_t wdeep_out;      /* windows of more than 250 strings it handed on to k_window (more than 1000 strings, a k-mer seen more than 1023 times, a table beyond its capacities);
 	                            where it ran, wdeep_windows + wdeep_out are the windows of more than 250 strings the last stage handed on: those the second stream does not have */
 	uint32_t pad4_;
+	/* ---- everything above: 224 bytes, the record before the stage of w = 128 ---- */
+	/* the stage of a batch with -w 128: k_window_fast<20> (layout in device memory, strings of up to 255 bases, up to 250 strings, a consensus of up to 192 symbols) runs
+	   every window of such a batch in front of k_window; the slots, the trailing stages and the second stream do not run there (tier_ms[], last_ms, long_windows are 0);
+	   window_ms stays the whole window stage */
+	float w128_ms;           /* its kernel; 0 if it did not run (w != 128, DACC_W128_TIER=0, DACC_W128_AS_SLOT2=1, DACC_WIDE_TIER=0, DACC_NOFAST=1, no memory for its slab) */
+	uint32_t w128_windows;   /* windows of the batch that finished in it */
+	uint32_t w128_out;       /* windows it handed on to k_window (more than 250 strings, a string of more than 255 bases, a table beyond its capacities); where it ran,
+	                            w128_windows + w128_out == nwindows */
+	uint32_t pad5_;
 } dacc_timing;
 #define DACC_TIMING_SIZE_V1 128
 #define DACC_TIMING_SIZE_V2 176   /* the record in front of longstr_ms */
 #define DACC_TIMING_SIZE_V3 192   /* the record in front of fdeep_ms */
 #define DACC_TIMING_SIZE_V4 208   /* the record in front of wdeep_ms */
+#define DACC_TIMING_SIZE_V5 224   /* the record in front of w128_ms */
 /* dacc_last_timing fills the first DACC_TIMING_SIZE_V1 bytes only (the record as it was when the call was introduced: a caller built against
  * an older header is never overrun).  dacc_last_timing2 copies min(size, sizeof(dacc_timing)) bytes: pass sizeof(dacc_timing) of the header
  * the caller was compiled with; fields the library does not know stay as the caller set them.  The 16 bytes behind emit_ms (the long string
  * stage) are copied only when size covers all of them: a size in [DACC_TIMING_SIZE_V2, DACC_TIMING_SIZE_V3) copies DACC_TIMING_SIZE_V2
  * bytes, so that a caller of the 176 byte record who passes the size of a larger buffer of its own gets what it got before.  The same rule holds
  * for the 16 bytes behind pad2_ (the full-depth stage): a size in [DACC_TIMING_SIZE_V3, DACC_TIMING_SIZE_V4) copies DACC_TIMING_SIZE_V3 bytes; and for
- * the 16 bytes behind pad3_ (the wide deep stage): a size in [DACC_TIMING_SIZE_V4, sizeof(dacc_timing)) copies DACC_TIMING_SIZE_V4 bytes. */
+ * the 16 bytes behind pad3_ (the wide deep stage): a size in [DACC_TIMING_SIZE_V4, DACC_TIMING_SIZE_V5) copies DACC_TIMING_SIZE_V4 bytes; and for the 16 bytes
+ * behind pad4_ (the stage of -w 128): a size in [DACC_TIMING_SIZE_V5, sizeof(dacc_timing)) copies DACC_TIMING_SIZE_V5 bytes. */
 int  dacc_last_timing(dacc_ctx *ctx, dacc_timing *t);
 int  dacc_last_timing2(dacc_ctx *ctx, dacc_timing *t, size_t size);
 

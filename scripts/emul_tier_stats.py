@@ -3,7 +3,8 @@ windows each capacity tier hands on and why (DACC_EMUL_OVER lines).  No GPU need
 The harness runs the slots of the chain: with DACC_LAST_AS_SLOT2=1 in the environment the third slot is the device-memory tier (13, wide
 batches 14), so its lines say what the last stage still hands on to the generic engine; with DACC_VDEEP_AS_SLOT2=1 it is tier 15 (windows of
 251 ... 1000 strings, tier 12 in front of it), with DACC_XDEEP_AS_SLOT2=1 tier 16 (up to 2000 strings), with DACC_FDEEP_AS_SLOT2=1 tier 18 (up to 5001 strings);
-in a wide run (STAT_W=64 ... 127) with DACC_WDEEP_AS_SLOT2=1 it is tier 19 (251 ... 1000 strings) in place of tier 9."""
+in a wide run (STAT_W=64 ... 127) with DACC_WDEEP_AS_SLOT2=1 it is tier 19 (251 ... 1000 strings) in place of tier 9; in a run with STAT_W=128 and
+DACC_W128_AS_SLOT2=1 it is tier 20, which is the second stream's tier there as well (without the switch such a run is the generic engine alone)."""
 import os, sys, re, subprocess, collections, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -19,6 +20,7 @@ if os.environ.get("DACC_EMUL_OVER") is None and "--child" not in sys.argv:
             print(l)
     # the key of a line is maxs * 10000 + ncap of the tier that overflowed: the tiers that share their string count with none
     names = {2502048: " (tier 12)", 2504096: " (tier 13, device memory)", 2506144: " (tier 14, device memory, wide)", 10004096: " (tier 15, device memory, 251 ... 1000 strings)", 20008190: " (tier 16, device memory, 1001 ... 2000 strings)", 50026384: " (tier 18, device memory, 2001 ... 5001 strings)", 10008190: " (tier 19, device memory, wide, 251 ... 1000 strings)"}
+    # (tier 20, w = 128, shares maxs and ncap with tiers 14 and 17: its lines carry their key, 2506144)
     for key, v in sorted(cnt.items()):
         print("tier maxs=%d%s bits=%s line=%d : %d" % (key[0], names.get(key[0], ""), key[1], key[2], v))
     sys.exit(p.returncode)

@@ -1,6 +1,6 @@
 """Registers / scratch / LDS of every kernel in the built library (from the metadata notes of its gfx950 code objects: one per
-translation unit that holds kernels, csrc/window_kernels.hpp; k_window_fast<N> for every tier of DACC_KERNEL_TIERS, the deep-window
-tier k_window_fast<12> and the device-memory tiers k_window_fast<13> / <14> / <15> / <16> / <17> / <18> / <19> -- group segment 0, their layout is in a slab -- among them, and `k_emit`, the consensus -> A alignment at one lane per window, whose columns are per-lane scratch: a template instance shows as _Z13k_window_fastILi<N>EE... where llvm-cxxfilt is missing).
+translation unit that holds kernels, csrc/window_kernels.hpp; k_window_fast<N> for every tier of DACC_EVERY_KERNEL_TIER, the deep-window
+tier k_window_fast<12> and the device-memory tiers k_window_fast<13> / <14> / <15> / <16> / <17> / <18> / <19> / <20> -- group segment 0, their layout is in a slab -- among them, and `k_emit`, the consensus -> A alignment at one lane per window, whose columns are per-lane scratch: a template instance shows as _Z13k_window_fastILi<N>EE... where llvm-cxxfilt is missing).
 usage: python scripts/kernel_resources.py [lib.so]"""
 import os, struct, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
