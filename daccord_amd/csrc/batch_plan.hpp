@@ -100,7 +100,7 @@ struct BatchPlan
 			uint64_t bsum = 0; uint32_t bmax = 0;
 			for ( int64_t b = 0; b < nblk; ++b ) { uint32_t const bl = tv(o.trace_off+2*b+1); bsum += bl; if ( bl > bmax ) bmax = bl; }
 			if ( static_cast<int64_t>(bsum) != o.bepos-o.bbpos ) { bad = "trace B lengths do not sum to bepos-bbpos"; break; }
-			// what the LDS column stores of the trace kernels hold at 8 lanes per wavefront (capi.hip: k_trace_wide<4> for
+			// what the LDS column stores of the trace kernels hold at 8 lanes per wavefront (launch_geometry.hpp: traceGeometry; k_trace_wide<4> for
 			// tspace <= 256, <8> beyond); only two byte trace values can say more, and such a block is no alignment: the
 			// pile is dropped
 			if ( bmax > (tsv <= 256 ? 4096u : 2048u) ) { bad = "a trace block spans too many B bases"; break; }
@@ -300,7 +300,7 @@ struct BatchPlan
 		// scratch capacities
 		uint64_t const depthcap = std::min<uint64_t>(static_cast<uint64_t>(maxdepth)+1, par.maxalign ? par.maxalign : 1);
 		// strings per window of the generic engine: as deep as the batch is, up to 8192 (the default -D keeps 5000 overlaps
-		// per read; the number of wavefronts is bounded by the arena budget, capi.hip: boundByArena)
+		// per read; the number of wavefronts is bounded by the arena budget, launch_geometry.hpp: boundByArena)
 		caps.maxs = std::max<uint32_t>(2,static_cast<uint32_t>(std::min<uint64_t>(depthcap,8192)));
 		// k-mer instances per string: 72 covers the windows the LDS tiers take (w <= 63 and the usual B strings); a wide window
 		// (w in 65..128) has w-k+1 instances in its A string and about as many per B string (maxspan bounds them), so its first

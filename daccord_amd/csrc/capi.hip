@@ -1,6 +1,7 @@
 /*
  * libdaccord_hip.so: C ABI (include/daccord_hip.h) + gfx950 kernels.
- * Host side: the context and what it owns on the device (context.hpp), batch planning, the device pass as a sequence of phases (runDevice), HIP-event timing.
+ * Host side: the context and what it owns on the device (context.hpp), batch planning, the batch setup (dacc_submit_piles_body; its arithmetic: launch_geometry.hpp)
+ * and the device pass (runDevice), each a sequence of phases, HIP-event timing.
  * There is no CPU fallback anywhere in this file: no device => DACC_ENODEV.
  */
 #include <hip/hip_runtime.h>
@@ -15,6 +16,7 @@
 #include "host_tables.hpp"
 #include "window_kernels.hpp"
 #include "trace_kernel.hpp"
+#include "launch_geometry.hpp"
 #include "vote_kernel.hpp"
 #include "emit_record.hpp"
 #include "context.hpp"
@@ -82,16 +84,6 @@ __global__ void __launch_bounds__(64) k_trace_wide(TraceBatch B, uint32_t const 
 	if ( threadIdx.x < nl )
 		for ( uint64_t task = static_cast<uint64_t>(blockIdx.x)*nl + threadIdx.x; task < B.nblocks; task += static_cast<uint64_t>(gridDim.x)*nl )
 			traceBlockWide<NW>(B,task,st);
-}
-
-// The generic engine's per-wavefront arena grows with the deepest pile of the batch (7 MB at depth 32, 200 MB at 1000,
-// 800 MB at the default -D of 5000): the number of wavefronts is bounded so that one batch's arenas stay below 32 GB
-// instead of failing the batch for want of 400 GB.
-static inline uint32_t boundByArena(uint64_t grid, uint64_t const bytes, uint64_t const mingrid)
-{
-	uint64_t const budget = 32ull << 30;
-	while ( grid > mingrid && grid*bytes > budget ) grid >>= 1;
-	return static_cast<uint32_t>(grid < 1 ? 1 : grid);
 }
 
 // Before the LDS tiers: one wavefront per overlap scans its rows of the window tables for B strings that the first slot's tiers (strings of
@@ -391,12 +383,11 @@ int dacc_create(dacc_ctx ** out, dacc_params const * p)
 	if ( !c ) return DACC_ENOMEM;
 	c->par = *p; c->device = p->device;
 	c->sw = readTierSwitches();      // DACC_NOFAST, DACC_TIERS, DACC_WIDE_TIER, DACC_DENSE_TIER, DACC_DEEP_TIER, the trailing stages' DACC_*_TIER and DACC_*_AS_SLOT2, DACC_LONGSTR_TIER, DACC_LONG128, DACC_HAND, DACC_T0INST, DACC_T7INST, DACC_LDS_T1, DACC_LDS_T0
-	char const * sc = getenv("DACC_SCHED"); c->env_sched = sc ? atoi(sc) : 1;      // bit 0: LDS tiers pull work from a counter, bit 1: generic engine too
-	{ char const * td = getenv("DACC_TRACE_DYN"); c->env_trdyn = !(td && td[0] == '0'); }      // 0: k_trace walks its blocks with a fixed stride
-	char const * ta = getenv("DACC_T7_ADAPT"); c->env_t7adapt = !(ta && ta[0] == '0');      // 0: tier 7 stays on whatever it hands on
-	char const * dr = getenv("DACC_DEBUG_RETRY"); c->env_dbgretry = (dr && dr[0] == '1');
-	{ char const * fn = getenv("DACC_FEAS_NEED"); c->env_feasneed = (fn && fn[0] == '0') ? 0u : 1u; }
-	{ char const * tf = getenv("DACC_TIE_FAST"); c->env_tiefast = (tf && tf[0] == '0') ? 0u : 1u; }
+	c->env_sched = static_cast<int>(envNum("DACC_SCHED",1));      // bit 0: LDS tiers pull work from a counter, bit 1: generic engine too
+	c->env_trdyn = !envOff("DACC_TRACE_DYN");      // 0: k_trace walks its blocks with a fixed stride
+	c->env_t7adapt = !envOff("DACC_T7_ADAPT");      // 0: tier 7 stays on whatever it hands on
+	c->env_dbgretry = envOn("DACC_DEBUG_RETRY");
+	c->env_feasneed = envOff("DACC_FEAS_NEED") ? 0u : 1u; c->env_tiefast = envOff("DACC_TIE_FAST") ? 0u : 1u;
 	// (a failure from here on: `delete c` destroys what has been created)
 	if ( hipStreamCreate(&c->stream.h) != hipSuccess ) { delete c; return DACC_EHIP; }
 	{ int lo = 0, hi = 0; hipDeviceGetStreamPriorityRange(&lo,&hi); if ( hipStreamCreateWithPriority(&c->stream2.h,hipStreamNonBlocking,hi) != hipSuccess ) { delete c; return DACC_EHIP; } }
@@ -542,6 +533,32 @@ static FastBatch stageBatch(dacc_ctx * c, WindowBatch const & WB, uint32_t const
 }
 // where the record's stage hands on, and its slab (one stride of the stage's gbytes per workgroup)
 static void handsOn(FastBatch & FB, uint32_t * const handon, uint8_t * const slab) { FB.retry = handon; FB.gslab = slab; FB.gstride = FB.F.gbytes; }
+// The launch of stage `id` on the main stream: its tier's kernel over `in` (0: all windows) with the record FB, no LDS for a layout in device memory.  A trailing stage and
+// the stage of w = 128 own their hand-on list and clear it here; a front tier's holds the pre-pass's windows by now and a main tier's the pre-scan's (enqueueSlot,
+// enqueuePrescan).  A main tier is done at its slot's event (runDevice), every other stage at its own.  what: the launch's name for DACC_DEBUG_SYNC
+static int launchStage(dacc_ctx * c, uint32_t const id, FastBatch const & FB, uint32_t const * const in, char const * const what = 0)
+{
+	dacc_ctx::Stage & S = c->st[id]; TierStage const & R = TIER_CHAIN[id]; hipStream_t const s = c->stream;
+	if ( R.role == ROLE_LAST || R.role == ROLE_ALONE ) HIPCHK(hipMemsetAsync(S.handon.p,0,sizeof(uint32_t),s));
+	hipLaunchKernelGGL(fastKernel(c->TP.tier[id]),dim3(S.grid),dim3(64),FB.F.gmem ? 0u : FB.F.ldsbytes,s,FB,in,workCounter(c,R.work));
+	if ( what ) mark(c,what);
+	if ( R.role != ROLE_MAIN ) { HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = in; }      // (a main tier keeps no run state: its slot's event and list say it)
+	return DACC_OK;
+}
+// The stages whose slab an allocation failure gives back (dacc_drop_hand) and that the retried call and the rest of the context run without (`noslab`): a row with a slab
+// budget of its own, and the stage of w = 128 whatever its budget (a build with DACC_W128_SLAB_MB=0 gives it the common one, and `.slab` alone would then miss it)
+static bool ownSlab(uint32_t const id) { return TIER_CHAIN[id].slab || TIER_CHAIN[id].role == ROLE_ALONE; }
+// The hand-on list (what the next stage or the generic engine reads) and the slab, grid x gbytes, of an optional device-memory stage: a trailing stage, the stage of
+// w = 128, the long string stage.  Optional like the hand-over buffer: a device that cannot spare them runs the batch without the stage, on the route it had before
+static int reserveStage(dacc_ctx * c, uint32_t const id, DevBuf<uint32_t> & handon, DevBuf<uint8_t> & slab, uint32_t const grid)
+{
+	if ( ownSlab(id) && c->noslab ) { slab.release(); c->TP.ok[id] = false; return DACC_OK; }
+	hipError_t e = handon.ensure(c->BP.nwindows+2);
+	if ( e == hipSuccess ) e = slab.ensure(static_cast<size_t>(grid)*c->BP.stageCaps(id).gbytes + 256);
+	if ( e == hipErrorOutOfMemory ) { (void)hipGetLastError(); slab.release(); c->TP.ok[id] = false; return DACC_OK; }
+	HIPCHK(e);
+	return DACC_OK;
+}
 
 // 1. second use of this context: now the hand-over buffer pays (dacc_submit_piles); an optimisation only -- if the device cannot spare it, halve it, and in the end do without
 static void growHandOver(dacc_ctx * c)
@@ -573,7 +590,7 @@ static int enqueuePrepAndTrace(dacc_ctx * c)
 		TB.piles = c->d_piles.p; TB.ovl = c->d_ovl.p; TB.ovl_pile = c->d_ovl_pile.p; TB.trace = c->d_trace.p;
 		TB.blk_ovl = c->d_blk_ovl.p; TB.blk_b0 = c->d_blk_b0.p; TB.nblocks = BP.nblocks; TB.wt_b = c->d_wt_b.p; TB.wt_e = c->d_wt_e.p;
 		TB.maxcols = BP.maxcols; TB.trace_bytes = c->trace_bytes; TB.errflag = c->d_err.p + 2; TB.slab = c->d_trslab.p;
-		TB.work = (c->env_trdyn && BP.nblocks < 0xFFFFFF00ull) ? c->d_work.p + WORK_TRACE : static_cast<uint32_t *>(0);
+		TB.work = (c->env_trdyn && traceCounterHolds(BP.nblocks)) ? c->d_work.p + WORK_TRACE : static_cast<uint32_t *>(0);
 		if ( TB.work ) HIPCHK(hipMemsetAsync(TB.work,0,sizeof(uint32_t),s));
 		if ( c->tr_words == 2 ) hipLaunchKernelGGL(k_trace,dim3(c->tr_grid),dim3(64),c->tr_lds,s,TB);
 		else if ( c->tr_words == 4 ) hipLaunchKernelGGL(k_trace_wide<4>,dim3(c->tr_grid),dim3(64),c->tr_lds,s,TB,c->tr_lanes);
@@ -614,7 +631,7 @@ static int enqueuePrescan(dacc_ctx * c, Pass & P)
 // slot, then its main tier; it takes the windows the slot in front handed over (P.list = 0: all windows)
 static int enqueueSlot(dacc_ctx * c, Pass & P, uint32_t const slot)
 {
-	BatchPlan & BP = c->BP; TierPipeline & TP = c->TP; hipStream_t const s = c->stream;
+	BatchPlan & BP = c->BP; TierPipeline & TP = c->TP; hipStream_t const s = c->stream; int rc;
 	if ( !TP.slotok(slot) ) return DACC_OK;
 	int const m = TIER_MAIN[slot];
 	FastBatch FB = stageBatch(c,P.WB,m); handsOn(FB,c->d_retry[slot].p,c->d_gslab.p);
@@ -644,14 +661,11 @@ static int enqueueSlot(dacc_ctx * c, Pass & P, uint32_t const slot)
 	}
 	for ( uint32_t k = 0; k < nfr; ++k )
 	{
-		dacc_ctx::Stage & S = c->st[fr[k]];
-		FastBatch FF = FB; FF.F = BP.stageCaps(fr[k]); handsOn(FF,S.handon.p,FB.gslab);
-		hipLaunchKernelGGL(fastKernel(TP.tier[fr[k]]),dim3(S.grid),dim3(64),FF.F.gmem ? 0u : FF.F.ldsbytes,s,FF,in,workCounter(c,TIER_CHAIN[fr[k]].work));
-		HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = in;
-		in = S.handon.p;
+		FastBatch FF = FB; FF.F = BP.stageCaps(fr[k]); handsOn(FF,c->st[fr[k]].handon.p,FB.gslab);
+		if ( (rc = launchStage(c,fr[k],FF,in)) ) return rc;
+		in = c->st[fr[k]].handon.p;
 	}
-	// (a device-memory tier in a slot, DACC_LAST_AS_SLOT2=1: no LDS)
-	hipLaunchKernelGGL(fastKernel(TP.tier[m]),dim3(c->st[m].grid),dim3(64),FB.F.gmem ? 0u : FB.F.ldsbytes,s,FB,in,workCounter(c,TIER_CHAIN[m].work));
+	if ( (rc = launchStage(c,m,FB,in)) ) return rc;      // (a device-memory tier in a slot, DACC_LAST_AS_SLOT2=1: no LDS)
 	P.list = c->d_retry[slot].p; P.lastslot = static_cast<int>(slot);
 	if ( !P.early )
 	{
@@ -668,16 +682,14 @@ static int enqueueSlot(dacc_ctx * c, Pass & P, uint32_t const slot)
 // kernel has read its list)
 static int enqueueTrailingStages(dacc_ctx * c, Pass & P)
 {
-	TierPipeline & TP = c->TP; hipStream_t const s = c->stream;
+	TierPipeline & TP = c->TP; int rc;
 	for ( uint32_t i = 0; i < TIER_NROWS; ++i )
 		if ( TIER_CHAIN[i].role == ROLE_LAST && TP.ok[i] && P.list && P.lastslot >= 0 )
 		{
 			dacc_ctx::Stage & S = c->st[i];
 			FastBatch FZ = stageBatch(c,P.WB,i); handsOn(FZ,S.handon.p,S.slab.p);
 			FZ.W.pregen = (TP.late_long || TP.widetier) ? c->d_pregen2.p : c->d_pregen.p;
-			HIPCHK(hipMemsetAsync(S.handon.p,0,sizeof(uint32_t),s));
-			hipLaunchKernelGGL(fastKernel(TP.tier[i]),dim3(S.grid),dim3(64),0,s,FZ,P.list,workCounter(c,TIER_CHAIN[i].work));
-			HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = P.list;
+			if ( (rc = launchStage(c,i,FZ,P.list)) ) return rc;
 			P.list = S.handon.p;
 		}
 	return DACC_OK;
@@ -711,16 +723,14 @@ static int launchLong(dacc_ctx * c, FastBatch & FL, uint32_t const * const lst, 
 	if ( TP.ok[ID_LONG] && TP.tier[ID_LONG] != 5 )
 	{
 		// the long string stage of a wide batch (tier 17: strings of up to 255 bases, layout in device memory): a kernel of its own over the list, no
-		// LDS, a slab of grid x gbytes and a hand-on list, both allocated here, where the list is known not to be empty (the second stream is idle: the
-		// copy above has been waited for).  Optional like the last stage's slab: without memory for it the batch runs without the stage
+		// LDS, a slab of grid x gbytes and a hand-on list, both reserved here, where the list is known not to be empty (the second stream is idle: the
+		// copy above has been waited for)
 		FastCaps const & F = BP.stageCaps(ID_LONG);
 		uint32_t const grid = tierGridGmem(F.gbytes,nlist);
-		hipError_t e = c->d_longhand[which].ensure(BP.nwindows+2);
-		if ( e == hipSuccess ) e = c->d_longslab.ensure(static_cast<size_t>(grid)*F.gbytes + 256);
-		if ( e == hipErrorOutOfMemory ) { (void)hipGetLastError(); c->d_longslab.release(); TP.ok[ID_LONG] = false; }
-		else
+		int const rc = reserveStage(c,ID_LONG,c->d_longhand[which],c->d_longslab,grid); if ( rc ) return rc;
+		if ( TP.ok[ID_LONG] )
 		{
-			HIPCHK(e);
+			// (not launchStage: the second stream, a grid that follows the list, a counter per list and events on both sides of the launch)
 			FastBatch FS = FL; FS.F = F; handsOn(FS,c->d_longhand[which].p,c->d_longslab.p);
 			uint32_t * const wk = (c->sched&1) ? c->d_work.p + TIER_CHAIN[ID_LONG].work + 8u*which : static_cast<uint32_t *>(0);
 			HIPCHK(hipMemsetAsync(FS.retry,0,sizeof(uint32_t),c->stream2));
@@ -1007,10 +1017,7 @@ static int runDevice(dacc_ctx * c)
 				// of more than 255 bases is handed on like a table that overflowed), the generic engine runs what it hands on
 				dacc_ctx::Stage & S = c->st[ID_W128];
 				FastBatch FZ = stageBatch(c,P.WB,ID_W128,false); handsOn(FZ,S.handon.p,S.slab.p);
-				HIPCHK(hipMemsetAsync(S.handon.p,0,sizeof(uint32_t),s));
-				hipLaunchKernelGGL(fastKernel(TP.tier[ID_W128]),dim3(S.grid),dim3(64),0,s,FZ,static_cast<uint32_t const *>(0),workCounter(c,TIER_CHAIN[ID_W128].work));
-				mark(c,"k_window_fast (w = 128 stage)");
-				HIPCHK(hipEventRecord(S.done,s)); S.ran = true; S.in = 0;
+				if ( (rc = launchStage(c,ID_W128,FZ,0,"k_window_fast (w = 128 stage)")) ) return rc;
 				glist = S.handon.p;
 			}
 			hipLaunchKernelGGL(k_window,dim3(c->win_grid),dim3(64),0,s,P.WB,c->d_err.p,glist,(c->sched&2) ? c->d_work.p+WORK_GENERIC : static_cast<uint32_t *>(0));
@@ -1029,18 +1036,13 @@ static int runDevice(dacc_ctx * c)
 	return DACC_OK;
 }
 
-static int dacc_submit_piles_body(dacc_ctx * c, dacc_pile const * piles, uint64_t npiles, dacc_overlap const * ovl, uint64_t novl,
-	void const * trace, uint64_t ntrace, int trace_bytes)
+// ---- the batch setup (dacc_submit_piles_body): one function per phase, in the order they run.  The device allocations and the hipFuncSetAttribute calls keep their
+// order from phase to phase and inside each: it decides which allocation meets an out-of-memory first, and so which optional buffer is given up (dacc_drop_hand)
+
+// 1. the error flags and profile counters, then the planned batch and its trace points go up; the tables the trace kernels fill
+static int uploadBatch(dacc_ctx * c, void const * trace, uint64_t const ntrace, int const trace_bytes)
 {
-	if ( !c ) return DACC_EINVAL;
-	if ( !c->haveprofile || !c->havedb ) { c->err = "dacc_set_error_profile and dacc_load_db must precede dacc_submit_piles"; return DACC_ESTATE; }
-	if ( (npiles && !piles) || (novl && (!ovl || !trace)) ) return DACC_EINVAL;
-	hipSetDevice(c->device);
-	c->havebatch = false;
-	BatchPlan & BP = c->BP;
-	int rc = BP.plan(c->par,piles,npiles,ovl,novl,trace,ntrace,trace_bytes,c->h_rlen.data(),c->h_rlen.size(),c->err,c->H.nrows,c->H.nsup);
-	if ( rc ) return rc;
-	hipStream_t const s = c->stream;
+	BatchPlan & BP = c->BP; hipStream_t const s = c->stream; int rc;
 	HIPCHK(c->d_err.ensure(4));
 	HIPCHK(c->d_prof.ensure(DACC_PROFW*4096)); HIPCHK(hipMemsetAsync(c->d_prof.p,0,DACC_PROFW*4096*sizeof(uint64_t),s));   // one row of counters per workgroup (no contention)
 	HIPCHK(hipEventRecord(c->ev[5],s));
@@ -1051,147 +1053,124 @@ static int dacc_submit_piles_body(dacc_ctx * c, dacc_pile const * piles, uint64_
 	if ( (rc = upload(c,c->d_fragbase,BP.fragbase.data(),BP.fragbase.size())) ) return rc;
 	HIPCHK(c->d_blk_ovl.ensure(BP.nblocks+1)); HIPCHK(c->d_blk_b0.ensure(BP.nblocks+1));
 	HIPCHK(c->d_wt_b.ensure(BP.nwt+1)); HIPCHK(c->d_wt_e.ensure(BP.nwt+1));
-	// trace kernel geometry: one wavefront per workgroup, as many workgroups per CU as their LDS column stores allow,
-	// a few rounds of blocks per workgroup
-	{
-		c->trace_bytes = trace_bytes;
-		// two word columns for tspace <= 128 while every lane's column store fits (blocks of up to 928 B bases: always with
-		// one byte trace values); a batch with a longer block runs the four word kernel, which sizes its lanes to the LDS
-		c->tr_words = (c->par.tspace <= 128 && BP.maxcols <= 928) ? 2 : (c->par.tspace <= 256 ? 4 : 8);
-		c->tr_lanes = 64;
-		if ( c->tr_words == 2 ) c->tr_lds = TRACE2_LDS;
-		else
-		{
-			// wide blocks: as many lanes per wavefront as have room for their column checkpoints
-			uint32_t const perlane = c->tr_words == 4 ? traceWideBytesPerLane<4>(BP.maxcols) : traceWideBytesPerLane<8>(BP.maxcols);
-			while ( c->tr_lanes > 8 && static_cast<uint64_t>(c->tr_lanes)*perlane > 160*1024 ) c->tr_lanes >>= 1;
-			c->tr_lds = c->tr_lanes*perlane;
-		}
-		if ( c->tr_lds > 160*1024 ) { c->err = "a trace block spans too many B bases for the trace kernel's LDS column store"; return DACC_ENOTSUP; }
-		if ( c->tr_lds > 64*1024 )
-		{
-			if ( c->tr_words == 2 ) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_trace),hipFuncAttributeMaxDynamicSharedMemorySize,c->tr_lds));
-			else if ( c->tr_words == 4 ) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_trace_wide<4>),hipFuncAttributeMaxDynamicSharedMemorySize,c->tr_lds));
-			else HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_trace_wide<8>),hipFuncAttributeMaxDynamicSharedMemorySize,c->tr_lds));
-		}
-		// resident workgroups per CU: LDS is handed out in granules of 1280 bytes (measured, round 5); k_trace holds 92 registers = 5 wavefronts per SIMD
-		uint64_t percu = (160*1024) / ((((c->tr_lds ? c->tr_lds : 1) + 1279u)/1280u)*1280u); if ( percu > (c->tr_words == 2 ? 20u : 8u) ) percu = (c->tr_words == 2 ? 20u : 8u); if ( percu < 1 ) percu = 1;
-		if ( char const * e = getenv("DACC_TR_PERCU") ) { uint64_t const v = strtoull(e,0,10); if ( v >= 1 && v <= 32 ) percu = v; }
-		// two word kernel: exactly the resident workgroups (grid stride over the blocks), so that the checkpoint slabs
-		// (53 KB per workgroup at a B span of 160) stay in the L2 / Infinity Cache
-		uint64_t g = (BP.nblocks+c->tr_lanes-1)/c->tr_lanes, gmax = 256*percu*(c->tr_words == 2 ? 1 : 4);
-		if ( g > gmax ) g = gmax;
-		if ( g < 1 ) g = 1;
-		c->tr_grid = g;
-		if ( c->tr_words == 2 )
-		{
-			// the checkpoint slabs of the resident workgroups are meant to stay in the Infinity Cache (256 MB): one block with a
-			// long B span makes every workgroup's slab large (300 KB at the 928 columns this kernel takes), so the grid gives way
-			// before the slabs outgrow 192 MB, down to one workgroup per CU
-			uint64_t const slabbytes = static_cast<uint64_t>(traceSlabWords(BP.maxcols))*sizeof(uint64_t);
-			while ( g > 256 && g*slabbytes > (192ull<<20) ) g -= 256;
-			c->tr_grid = g;
-			HIPCHK(c->d_trslab.ensure(static_cast<size_t>(g)*traceSlabWords(BP.maxcols)));
-		}
-	}
-	// window kernel geometry + arenas
-	Arena Atmp; BP.caps.bytes = arena_carve(Atmp,0,BP.caps,c->par.w);
-	uint64_t wg = ((BP.nwindows+7)/8)*8;
-	uint64_t const maxwg = 256*8;
-	if ( wg > maxwg ) wg = maxwg;
-	if ( wg < 8 ) wg = 8;
+	c->trace_bytes = trace_bytes;
+	return DACC_OK;
+}
+
+static void const * traceKernel(uint32_t const words)
+{
+	return words == 2 ? reinterpret_cast<void const *>(k_trace) : words == 4 ? reinterpret_cast<void const *>(k_trace_wide<4>) : reinterpret_cast<void const *>(k_trace_wide<8>);
+}
+// 2. the trace kernels' launch (launch_geometry.hpp: traceGeometry), the LDS attribute of a wide kernel and the two word kernel's checkpoint slabs
+static int setupTrace(dacc_ctx * c)
+{
+	BatchPlan & BP = c->BP;
+	TraceGeometry G = traceGeometry(c->par.tspace,BP.maxcols,BP.nblocks,0);
+	c->tr_words = G.words; c->tr_lanes = G.lanes; c->tr_lds = G.lds;
+	if ( !G.fits ) { c->err = "a trace block spans too many B bases for the trace kernel's LDS column store"; return DACC_ENOTSUP; }
+	if ( G.lds > 64*1024 ) HIPCHK(hipFuncSetAttribute(traceKernel(G.words),hipFuncAttributeMaxDynamicSharedMemorySize,G.lds));
+	if ( char const * e = getenv("DACC_TR_PERCU") ) G = traceGeometry(c->par.tspace,BP.maxcols,BP.nblocks,strtoull(e,0,10));      // (moves the workgroups per CU and the grid alone)
+	c->tr_grid = G.grid;
+	if ( G.words == 2 ) HIPCHK(c->d_trslab.ensure(static_cast<size_t>(G.grid)*traceSlabWords(BP.maxcols)));
+	return DACC_OK;
+}
+
+// 3. which LDS tiers this batch runs (tier_pipeline.hpp); none: the generic engine alone
+static void resolveBatchTiers(dacc_ctx * c)
+{
+	BatchPlan & BP = c->BP;
 	c->sched = c->env_sched;
 	bool fits32 = true;
 	for ( size_t i = 0; i < c->H.dpsq_vst.size(); ++i ) if ( c->H.dpsq_vst[i] >> 32 ) fits32 = false; // table must fit 32 bits
-	// which LDS tiers this batch runs (tier_pipeline.hpp); none: the generic engine alone
 	c->TP = resolveTiers(c->sw,!c->sw.nofast && fits32,BP.deep,BP.wide,c->H.nrows,c->H.nsup,c->par.w,[&](uint32_t const id) -> FastCaps & { return BP.stageCaps(id); },BP.maxstrings(c->par),TIER_NROWS);
-	TierPipeline const & TP = c->TP;
-	// (a batch of w = 128 in which no slot runs: the generic engine's geometry, as before its stage existed, and the stage's list and slab beside it)
-	bool const alone = aloneBatch(c);
-	if ( TP.usefast && !alone )
+}
+
+// 4. the stages: launch geometry, the slots' hand-on lists and those of the front tiers (and the pre-pass's list of small windows), the global slab of the gw tiers
+// (weights, spill: one per workgroup, the tiers run one after the other and share the buffer), and list and slab of every optional device-memory stage (reserveStage).
+// chain: slots run, every row is visited; else the row of the stage of w = 128 alone -- a batch of w = 128 in which no slot runs (aloneBatch), behind the
+// generic engine's arenas
+static int reserveStages(dacc_ctx * c, bool const chain)
+{
+	BatchPlan & BP = c->BP; TierPipeline const & TP = c->TP; int rc;
+	if ( chain ) for ( int t = 0; t < TIER_NSLOTS; ++t ) HIPCHK(c->d_retry[t].ensure(BP.nwindows+2));
+	for ( uint32_t i = 0; i < TIER_NROWS; ++i )
 	{
-		for ( int t = 0; t < TIER_NSLOTS; ++t ) HIPCHK(c->d_retry[t].ensure(BP.nwindows+2));
-		// the stages of the chain: launch geometry, hand-on lists of the front tiers (and the pre-pass's list of small windows), global slab
-		// of the gw tiers (weights, spill): one per workgroup, the tiers run one after the other and share the buffer
-		for ( uint32_t i = 0; i < TIER_NROWS; ++i )
-		{
-			FastCaps const & F = BP.stageCaps(i);
-			c->st[i].grid = F.gmem ? tierGridGmem(F.gbytes,BP.nwindows,TIER_CHAIN[i].slab) : tierGrid(F.ldsbytes,BP.nwindows);
-			if ( !TP.ok[i] || TIER_CHAIN[i].role == ROLE_LONG ) continue;
-			if ( TIER_CHAIN[i].role == ROLE_LAST )
-			{
-				// a trailing stage: its own hand-on list (what the next one or k_window reads) and its own slab, grid x gbytes <= TIER_GMEM_SLAB (or the row's own budget, TierStage::slab).  Both are optional
-				// like the hand-over buffer: a device that cannot spare them runs the batch without the stage, on the route it had before
-				DevBuf<uint8_t> & slab = c->st[i].slab;
-				if ( TIER_CHAIN[i].slab && c->noslab ) { slab.release(); c->TP.ok[i] = false; continue; }      // a retry after an allocation failure: no slab budget beyond the common one (dacc_drop_hand)
-				hipError_t e = c->st[i].handon.ensure(BP.nwindows+2);
-				if ( e == hipSuccess ) e = slab.ensure(static_cast<size_t>(c->st[i].grid)*F.gbytes + 256);
-				if ( e == hipErrorOutOfMemory ) { (void)hipGetLastError(); slab.release(); c->TP.ok[i] = false; }
-				else HIPCHK(e);
-				continue;
-			}
-			if ( TIER_CHAIN[i].role == ROLE_FRONT ) HIPCHK(c->st[i].handon.ensure(BP.nwindows+2));
-			if ( TIER_CHAIN[i].flags & STAGE_PREPASS ) HIPCHK(c->d_small.ensure(BP.nwindows+2));
-			if ( F.gbytes ) HIPCHK(c->d_gslab.ensure(static_cast<size_t>(c->st[i].grid)*F.gbytes + 256));
-			if ( !F.gmem && F.ldsbytes > 64*1024 ) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(fastKernel(TP.tier[i])),hipFuncAttributeMaxDynamicSharedMemorySize,F.ldsbytes));
-		}
-		{
-			// hand-over slots (sorted instances of a window that overflowed a tier's node table, picked up by the next tier): header +
-			// the instance capacity of the tiers that hand on + their last k-mer lists; as many slots as a third of the windows, within
-			// 16 GB (config 2: 1.6 M hand-overs of 10 M windows).  DACC_HAND=0 switches the mechanism off (every hand-over restarts).
-			// The buffer is an optimisation for contexts that live: the driver clears device memory it hands out (16 GB = half a
-			// second on some boxes), which a single pass does not earn back, so the FIRST pass of a context runs without it and the
-			// buffer is allocated when the context is used again (growHandOver).
-			uint64_t cap = BP.nwindows/3 + 4096; uint64_t const maxcap = (16ull<<30) / (static_cast<uint64_t>(TP.handwords)*8ull);
-			if ( cap > maxcap ) cap = maxcap;
-			if ( c->par.klow != c->par.khigh ) cap = 0;
-			if ( c->nohand ) cap = 0;      // a retry after an allocation failure: no optional buffer (dacc_drop_hand)
-			if ( !TP.handover ) cap = 0;   // DACC_HAND=0, or a wide batch: nothing to hand the sorted instances to
-			c->handwant = cap;
-			HIPCHK(c->d_handctr.ensure(4));
-			if ( c->d_hand.cap < static_cast<size_t>(cap)*TP.handwords ) c->handcap = static_cast<uint32_t>(c->d_hand.cap / TP.handwords);     // what an earlier batch left
-			else c->handcap = static_cast<uint32_t>(cap);
-		}
+		TierStage const & R = TIER_CHAIN[i]; dacc_ctx::Stage & S = c->st[i]; FastCaps const & F = BP.stageCaps(i);
+		if ( !chain && !(R.role == ROLE_ALONE && TP.ok[i]) ) continue;      // without a chain: the stage of w = 128 alone, and only where it is resolved (with one it never is)
+		S.grid = F.gmem ? tierGridGmem(F.gbytes,BP.nwindows,R.slab) : tierGrid(F.ldsbytes,BP.nwindows);      // (a slab within TIER_GMEM_SLAB, or the row's own budget, TierStage::slab)
+		if ( !TP.ok[i] || R.role == ROLE_LONG ) continue;
+		if ( R.role == ROLE_LAST || R.role == ROLE_ALONE ) { if ( (rc = reserveStage(c,i,S.handon,S.slab,S.grid)) ) return rc; continue; }
+		if ( R.role == ROLE_FRONT ) HIPCHK(S.handon.ensure(BP.nwindows+2));
+		if ( R.flags & STAGE_PREPASS ) HIPCHK(c->d_small.ensure(BP.nwindows+2));
+		if ( F.gbytes ) HIPCHK(c->d_gslab.ensure(static_cast<size_t>(S.grid)*F.gbytes + 256));
+		if ( !F.gmem && F.ldsbytes > 64*1024 ) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(fastKernel(TP.tier[i])),hipFuncAttributeMaxDynamicSharedMemorySize,F.ldsbytes));
+	}
+	return DACC_OK;
+}
+
+// 5. the hand-over buffer's size (launch_geometry.hpp: handOverCapacity); DACC_HAND=0 switches the mechanism off (every hand-over restarts).
+// The buffer is an optimisation for contexts that live: the driver clears device memory it hands out (16 GB = half a second on some boxes), which a single pass
+// does not earn back, so the FIRST pass of a context runs without it and the buffer is allocated when the context is used again (growHandOver).
+static int sizeHandOver(dacc_ctx * c)
+{
+	TierPipeline const & TP = c->TP;
+	uint64_t const cap = handOverCapacity(c->BP.nwindows,TP.handwords,c->par.klow != c->par.khigh,c->nohand,TP.handover);
+	c->handwant = cap;
+	HIPCHK(c->d_handctr.ensure(4));
+	if ( c->d_hand.cap < static_cast<size_t>(cap)*TP.handwords ) c->handcap = static_cast<uint32_t>(c->d_hand.cap / TP.handwords);     // what an earlier batch left
+	else c->handcap = static_cast<uint32_t>(cap);
+	return DACC_OK;
+}
+
+// 6. the generic engine: its grids (launch_geometry.hpp: genericGeometry) and arenas; with a chain in front of it the second stream's kernel, lists and arena as well
+static int setupGenericEngine(dacc_ctx * c, bool const chain)
+{
+	BatchPlan & BP = c->BP; TierPipeline const & TP = c->TP;
+	Arena Atmp; BP.caps.bytes = arena_carve(Atmp,0,BP.caps,c->par.w);
+	GenericGeometry const G = genericGeometry(BP.nwindows,BP.caps.bytes,chain);
+	c->retry_grid = G.retry_grid; c->win_grid = G.win_grid; c->early_grid = G.early_grid;
+	if ( chain )
+	{
 		if ( TP.ok[ID_LONG] && TP.tier[ID_LONG] == 5 && BP.stageCaps(ID_LONG).ldsbytes > 64*1024 ) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_window_long),hipFuncAttributeMaxDynamicSharedMemorySize,BP.stageCaps(ID_LONG).ldsbytes));
-		c->retry_grid = boundByArena(wg < 512 ? wg : 512,BP.caps.bytes,8);
-		c->win_grid = c->retry_grid;
-		// generic engine on the second stream (windows with a string of more than 64 bases): a wavefront per window as far
-		// as the arenas stay below 8 GB (the handful of such windows of config 2 took the generic engine up to 6.6 s each next to
-		// the 8.2 s of the LDS tiers; tier 5 takes them now)
-		c->early_grid = c->retry_grid < 256 ? c->retry_grid : 256;
-		while ( c->early_grid > 16 && static_cast<uint64_t>(c->early_grid)*BP.caps.bytes > (8ull<<30) ) c->early_grid >>= 1;
 		HIPCHK(c->d_gearly.ensure(BP.nwindows+2)); HIPCHK(c->d_pregenlist.ensure(BP.nwindows+2)); HIPCHK(c->d_pregen.ensure((BP.nwindows+31)/32+2)); HIPCHK(c->d_pregen2.ensure((BP.nwindows+31)/32+2));
 		HIPCHK(c->d_arena2.ensure(static_cast<size_t>(c->early_grid)*BP.caps.bytes));
-		HIPCHK(c->d_work.ensure(WORK_WORDS));
-		HIPCHK(c->d_arena.ensure(static_cast<size_t>(c->retry_grid)*BP.caps.bytes));
 	}
-	else
-	{
-		c->win_grid = boundByArena(wg,BP.caps.bytes,8);
-		c->retry_grid = c->win_grid; c->early_grid = 0;
-		HIPCHK(c->d_work.ensure(WORK_WORDS));
-		HIPCHK(c->d_arena.ensure(static_cast<size_t>(c->win_grid)*BP.caps.bytes));
-		if ( alone && TP.ok[ID_W128] )
-		{
-			// the stage of a w = 128 batch: its hand-on list (what k_window reads) and its slab, grid x gbytes <= TIER_GMEM_SLAB.  Optional like a trailing stage's:
-			// a device that cannot spare them, and a retry after an allocation failure (dacc_drop_hand), run the batch in the generic engine alone
-			dacc_ctx::Stage & S = c->st[ID_W128]; FastCaps const & F = BP.stageCaps(ID_W128);
-			S.grid = tierGridGmem(F.gbytes,BP.nwindows,TIER_CHAIN[ID_W128].slab);
-			if ( c->noslab ) { S.slab.release(); c->TP.ok[ID_W128] = false; }
-			else
-			{
-				hipError_t e = S.handon.ensure(BP.nwindows+2);
-				if ( e == hipSuccess ) e = S.slab.ensure(static_cast<size_t>(S.grid)*F.gbytes + 256);
-				if ( e == hipErrorOutOfMemory ) { (void)hipGetLastError(); S.slab.release(); c->TP.ok[ID_W128] = false; }
-				else HIPCHK(e);
-			}
-		}
-	}
+	HIPCHK(c->d_work.ensure(WORK_WORDS));
+	HIPCHK(c->d_arena.ensure(static_cast<size_t>(c->retry_grid)*BP.caps.bytes));
+	return DACC_OK;
+}
+
+// 7. window records and results, the vote's buffers, what comes back
+static int ensureResultBuffers(dacc_ctx * c)
+{
+	BatchPlan & BP = c->BP;
 	HIPCHK(c->d_wrec.ensure((BP.nwindows+1)*static_cast<size_t>(DACC_WREC_OF(c->par.w)))); HIPCHK(c->d_wout.ensure(BP.nwindows+1));
 	HIPCHK(c->d_has.ensure(BP.npos+1)); HIPCHK(c->d_oc.ensure(BP.npos+1)); HIPCHK(c->d_ld0.ensure(BP.npos+1)); HIPCHK(c->d_ocs.ensure(BP.npos+1));
 	HIPCHK(c->d_outsym.ensure(2*BP.npos + 64*BP.piles.size() + 64));
 	HIPCHK(c->d_nfrag.ensure(BP.piles.size()+1)); HIPCHK(c->d_frags.ensure(BP.nfragslots+1)); HIPCHK(c->d_pilebad.ensure(BP.piles.size()+1));
-	hipEventRecord(c->h2dend,s);
+	return DACC_OK;
+}
+
+static int dacc_submit_piles_body(dacc_ctx * c, dacc_pile const * piles, uint64_t npiles, dacc_overlap const * ovl, uint64_t novl,
+	void const * trace, uint64_t ntrace, int trace_bytes)
+{
+	if ( !c ) return DACC_EINVAL;
+	if ( !c->haveprofile || !c->havedb ) { c->err = "dacc_set_error_profile and dacc_load_db must precede dacc_submit_piles"; return DACC_ESTATE; }
+	if ( (npiles && !piles) || (novl && (!ovl || !trace)) ) return DACC_EINVAL;
+	hipSetDevice(c->device);
+	c->havebatch = false;
+	int rc = c->BP.plan(c->par,piles,npiles,ovl,novl,trace,ntrace,trace_bytes,c->h_rlen.data(),c->h_rlen.size(),c->err,c->H.nrows,c->H.nsup);
+	if ( rc ) return rc;
+	if ( (rc = uploadBatch(c,trace,ntrace,trace_bytes)) ) return rc;
+	if ( (rc = setupTrace(c)) ) return rc;
+	resolveBatchTiers(c);
+	bool const chain = c->TP.usefast && !aloneBatch(c);      // slots and a second stream run; else the generic engine alone, or behind the stage of w = 128
+	if ( chain && (rc = reserveStages(c,true)) ) return rc;
+	if ( chain && (rc = sizeHandOver(c)) ) return rc;
+	if ( (rc = setupGenericEngine(c,chain)) ) return rc;
+	if ( !chain && (rc = reserveStages(c,false)) ) return rc;
+	if ( (rc = ensureResultBuffers(c)) ) return rc;
+	hipEventRecord(c->h2dend,c->stream);
 	rc = runDevice(c);
 	float ms = 0; hipEventElapsedTime(&ms,c->ev[5],c->h2dend); c->timing.h2d_ms = ms;
 	if ( rc ) return rc;
@@ -1232,12 +1211,8 @@ int dacc_last_timing(dacc_ctx * c, dacc_timing * t)
 int dacc_last_timing2(dacc_ctx * c, dacc_timing * t, size_t size)
 {
 	if ( !c || !t ) return DACC_EINVAL;
-	// the long string stage's 16 bytes behind emit_ms go only to a caller that has room for all of them: a caller built with the 176 byte record that
-	// passes a larger size (its record inside a larger buffer) gets the 176 bytes it knows, as before the record grew; the full-depth stage's 16 bytes behind
-	// those follow the same rule: a size in [192, 208) copies 192 bytes; so do the wide deep stage's 16 bytes behind pad3_: a size in [208, 224) copies 208 bytes
-	// and the 16 bytes of the stage of w = 128 behind pad4_: a size in [224, 240) copies 224 bytes
-	size_t const n = size >= sizeof(dacc_timing) ? sizeof(dacc_timing) : (size >= DACC_TIMING_SIZE_V5 ? static_cast<size_t>(DACC_TIMING_SIZE_V5) : size >= DACC_TIMING_SIZE_V4 ? static_cast<size_t>(DACC_TIMING_SIZE_V4) : (size >= DACC_TIMING_SIZE_V3 ? static_cast<size_t>(DACC_TIMING_SIZE_V3) : (size < DACC_TIMING_SIZE_V2 ? size : static_cast<size_t>(DACC_TIMING_SIZE_V2))));
-	std::memcpy(static_cast<void *>(t),&c->timing,n);
+	// each stage's 16 bytes behind the first 176 go only to a caller that has room for all of them (launch_geometry.hpp: TIMING_SIZES)
+	std::memcpy(static_cast<void *>(t),&c->timing,timingCopySize(size));
 	return DACC_OK;
 }
 
@@ -1358,13 +1333,13 @@ static bool dacc_drop_hand(dacc_ctx * c)
 	if ( !c || !c->oom ) return false;
 	c->oom = false;
 	bool slabs = false;
-	for ( uint32_t i = 0; i < TIER_NROWS; ++i ) slabs = slabs || ((TIER_CHAIN[i].slab || TIER_CHAIN[i].role == ROLE_ALONE) && c->st[i].slab.p);
+	for ( uint32_t i = 0; i < TIER_NROWS; ++i ) slabs = slabs || (ownSlab(i) && c->st[i].slab.p);
 	if ( !c->d_hand.p && !slabs ) return false;
 	(void)hipGetLastError(); hipSetDevice(c->device); (void)hipDeviceSynchronize(); (void)hipGetLastError();
 	if ( c->d_hand.p ) { c->d_hand.release(); c->handcap = 0; c->handwant = 0; c->nohand = true; }
 	if ( slabs )
 	{
-		for ( uint32_t i = 0; i < TIER_NROWS; ++i ) if ( TIER_CHAIN[i].slab || TIER_CHAIN[i].role == ROLE_ALONE ) { c->st[i].slab.release(); c->TP.ok[i] = false; }
+		for ( uint32_t i = 0; i < TIER_NROWS; ++i ) if ( ownSlab(i) ) { c->st[i].slab.release(); c->TP.ok[i] = false; }
 		c->noslab = true;
 	}
 	return true;

@@ -172,6 +172,10 @@ struct TierStage
 // allocated for the grid, a workgroup per window of the batch up to that, and is optional like the others
 enum : uint64_t { W128_GMEM_SLAB = static_cast<uint64_t>(DACC_W128_SLAB_MB) << 20 };
 enum : uint32_t { W128 = 128 };      // the window size whose model table has 129 rows: three words per position mask (FastTier<20>)
+// an environment switch: set to 0 (a default that is on), set to 1 (a default that is off), a number
+static inline bool envOff(char const * const name) { char const * const e = getenv(name); return e && e[0] == '0'; }
+static inline bool envOn(char const * const name) { char const * const e = getenv(name); return e && e[0] == '1'; }
+static inline uint32_t envNum(char const * const name, uint32_t const dflt) { char const * const e = getenv(name); return e ? static_cast<uint32_t>(atoi(e)) : dflt; }
 static TierStage const TIER_CHAIN[TIER_NROWS] = {
 	{ { 0, TIER_NONE, TIER_NONE }, 0, ROLE_FRONT, 3, STAGE_PREPASS, WORK_T0 },
 	{ { 7, TIER_NONE, TIER_NONE }, 0, ROLE_FRONT, 4, STAGE_PREPASS|STAGE_ADAPTIVE|GATE_PREV_FRONT|GATE_T7_ABOVE_T0, WORK_T7 },
@@ -198,7 +202,7 @@ static TierId const TIER_MAIN[TIER_NSLOTS] = { ID_SLOT0, ID_SLOT1, ID_SLOT2 };
 // those of the nearest shape: the first slot of a wide batch has tier 1's or tier 4's)
 static inline bool stageRuns(TierStage const & st, bool const deep, bool const wide) { return st.tier[wide ? 2 : deep] != TIER_NONE; }
 // DACC_*_AS_SLOT2=1 of a trailing stage's row: the third slot's main tier is that stage's tier (read by the planner and by resolveTiers alike, so once per call)
-static inline bool stageAsSlot2(TierStage const & st) { char const * const e = st.slot2switch ? getenv(st.slot2switch) : 0; return e && e[0] == '1'; }
+static inline bool stageAsSlot2(TierStage const & st) { return st.slot2switch && envOn(st.slot2switch); }
 // (w: the batch's window size, for the rows that are for one size alone (TierStage::onlyw); a caller that leaves it out sees none of them.  Such a row's AS_SLOT2 switch
 // names the second stream's tier as well: the long string stage of that batch is its tier)
 static inline uint32_t stageTier(TierStage const & st, bool const deep, bool const wide, uint32_t const w = 0)
@@ -230,15 +234,13 @@ struct TierSwitches
 };
 static inline TierSwitches readTierSwitches()
 {
-	auto const off = [](char const * const name) { char const * const e = getenv(name); return e && e[0] == '0'; };
-	auto const num = [](char const * const name, uint32_t const dflt) { char const * const e = getenv(name); return e ? static_cast<uint32_t>(atoi(e)) : dflt; };
 	TierSwitches S;
-	{ char const * const e = getenv("DACC_NOFAST"); S.nofast = e && e[0] == '1'; }
-	S.tiers = num("DACC_TIERS",31);
-	S.widetier = !off("DACC_WIDE_TIER"); S.dense = !off("DACC_DENSE_TIER"); S.deepwin = !off("DACC_DEEP_TIER"); S.longstr = !off("DACC_LONGSTR_TIER"); S.long128 = !off("DACC_LONG128"); S.hand = !off("DACC_HAND");
-	for ( uint32_t i = 0; i < TIER_NROWS; ++i ) { TierStage const & st = TIER_CHAIN[i]; S.off[i] = st.offswitch && off(st.offswitch); S.as_slot2[i] = stageAsSlot2(st); }
-	S.t0inst = num("DACC_T0INST",T0INST_DEFAULT); S.t7inst = num("DACC_T7INST",T7INST_DEFAULT);
-	S.lds_t1 = num("DACC_LDS_T1",0); S.lds_t0 = num("DACC_LDS_T0",0);
+	S.nofast = envOn("DACC_NOFAST");
+	S.tiers = envNum("DACC_TIERS",31);
+	S.widetier = !envOff("DACC_WIDE_TIER"); S.dense = !envOff("DACC_DENSE_TIER"); S.deepwin = !envOff("DACC_DEEP_TIER"); S.longstr = !envOff("DACC_LONGSTR_TIER"); S.long128 = !envOff("DACC_LONG128"); S.hand = !envOff("DACC_HAND");
+	for ( uint32_t i = 0; i < TIER_NROWS; ++i ) { TierStage const & st = TIER_CHAIN[i]; S.off[i] = st.offswitch && envOff(st.offswitch); S.as_slot2[i] = stageAsSlot2(st); }
+	S.t0inst = envNum("DACC_T0INST",T0INST_DEFAULT); S.t7inst = envNum("DACC_T7INST",T7INST_DEFAULT);
+	S.lds_t1 = envNum("DACC_LDS_T1",0); S.lds_t0 = envNum("DACC_LDS_T0",0);
 	return S;
 }
 

@@ -21,6 +21,7 @@
 #include "wave.hpp"
 #include "dev_types.hpp"
 #include "window_main.hpp"
+#include "launch_geometry.hpp"
 
 namespace dacc {
 
@@ -104,20 +105,13 @@ struct TCol { uint64_t pv0, mv0, pv1, mv1; };
 // all, and the segment's first column (slot 0 of the old layout) is not needed.  The decisions are the same by construction: the old test
 // `D[i-1][j-1] + (A[i-1] != B[j-1]) == D[i][j]` is the DIAG bit.  k_trace was the one kernel of the step near its instruction bound
 // (VALU 55 % of the SIMDs' slots at 8 wavefronts per CU): 64 k -> 45 k VALU instructions per wavefront and block round.
-enum { TRS = 16 };      // wide kernels (k_trace_wide): checkpoints and segment in LDS
+// (TRS, T2C, T2S and the sizes that follow from them: launch_geometry.hpp, which the host's launch arithmetic reads without this file)
+// wide kernels (k_trace_wide): checkpoints every TRS columns and a segment of TRS columns, both in LDS
 // two word kernel: T2C columns between checkpoints (global slab), T2S columns per segment (LDS).  The traceback enters a segment by
 // recomputing from the checkpoint at or before it: the columns in front of the segment are stepped over without being stored.
 // T2S < T2C trades recomputed columns for LDS bytes = resident wavefronts.
 // Measured with the old column format (profiles/r06p, 3000 reads of config 2, 5.4 M blocks): segments of 8 / 4 / 2 columns = 8 / 14 / 16
 // wavefronts per CU: 16.3 / 13.9 / 17.7 ms (checkpoints every 4 columns with segments of 4: 15.9 ms -- twice the slab traffic for the same LDS).
-#if !defined(DACC_T2C)
-#define DACC_T2C 8
-#endif
-#if !defined(DACC_T2S)
-#define DACC_T2S 4
-#endif
-enum { T2C = DACC_T2C, T2S = DACC_T2S };
-static_assert(T2C % T2S == 0 && T2C <= 16,"segments tile the checkpoint groups; a group's B symbols are kept packed in 32 bits");
 // segment slots of the 64 lanes of a wavefront interleaved in 32 bit units: field f (0-3: DIAG bits 0-31, 32-63, 64-95, 96-127; 4-7: Pv) of
 // slot u of lane l at (u*8+f)*64 + l (no bank conflicts whatever slot and row a lane is at); slot u = column g*T2S+1+u
 struct TraceStoreGL
@@ -156,10 +150,6 @@ struct TraceStoreMem
 	uint32_t segDiag(uint32_t const u, uint32_t const r) const { return static_cast<uint32_t>(seg[4*u + (r>>6)] >> (32*((r>>5)&1))); }
 	uint32_t segPv(uint32_t const u, uint32_t const r) const { return static_cast<uint32_t>(seg[4*u + 2 + (r>>6)] >> (32*((r>>5)&1))); }
 };
-HDEV uint32_t traceSlots(uint32_t const maxcols) { return maxcols/TRS + 1 + TRS; }     // wide kernels: checkpoints 0,TRS,2*TRS,.. + one segment
-HDEV uint32_t traceCheckpoints(uint32_t const maxcols) { return maxcols/T2C + 1; }     // two word kernel: checkpoints per lane (global slab)
-HDEV uint32_t traceSlabWords(uint32_t const maxcols) { return traceCheckpoints(maxcols)*4u*64u; }      // 64 bit words per workgroup
-enum : uint32_t { TRACE2_LDS = T2S*64*32 };      // LDS bytes of a wavefront of k_trace
 
 // Myers / Hyyro column step: C = column c -> column c+1 for B symbol tc.  DIAGS: also the traceback's decision bits of the new column
 // (dg0 / dg1, see above).  No masking of the rows beyond the block's m: carries only travel upwards and no row >= m is ever read.
@@ -309,7 +299,6 @@ struct TraceStoreW
 		c.score = sc[e*nl+lane]; return c;
 	}
 };
-template<int NW> HDEV uint32_t traceWideBytesPerLane(uint32_t const maxcols) { return traceSlots(maxcols)*(16u*NW+2u); }
 // word `idx` (run time) of a register array: a select chain over the compile time indices (no scratch)
 template<int NW> DEV uint64_t traceWord(uint64_t const (&a)[NW], uint32_t const idx)
 {
